@@ -18,11 +18,19 @@ every base of the share exactly once and the inputs of every timed region are re
 `--shard r/N` runs rank r's share of an N-rank run in ONE process on one GPU (no process group): the way one shard
 of configs[3] is measured on a single-GPU box.  `--scaling weak` gives every rank its own full-size set instead.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome 3e9 --shard r/N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--genome 3e9 --shard r/N] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (before any GPU call).
 Prints ONE JSON line on rank 0 (fields: README / DESIGN.md section 6).
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`); `roofline` and
+`cpu_baseline` are null and `extras` holds only figures of the run itself.  `--full` adds everything else measured or
+checked after the timed steps: the scan-kernel roofline, the accuracy against the generator's truth, the CPU baseline and
+the PCIe / host-feed / CLI / configs[4] extras (`--no-cpu`, `--no-extras`, `--only-pcie` trim those as before).
+`--dump-outputs DIR` writes what the last timed step computed (write_outputs: labels of a fixed, seeded sample of reads and
+the count of every label byte over the whole output) as .npy files; the inputs are the same on every run with the same
+arguments, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -47,8 +55,15 @@ K = 40
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run everything else the bench measures or checks: the scan roofline, the accuracy "
+                         "against the generator's truth, the CPU baseline, the PCIe / host-feed / CLI / other-configuration extras "
+                         "(each still subject to --no-cpu / --no-extras / --only-pcie); off by default, a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64): the labels of a "
+                         "fixed, seeded sample of whole reads and the count of every label byte over the whole output")
     ap.add_argument("--genome", type=float, default=None,
                     help="synthetic diploid genome length; default 200e6 (configs[2]) for one GPU, 3e9 (configs[3]) for --gpus N > 1 or --shard")
     ap.add_argument("--shard", default=None, metavar="r/N",
@@ -90,7 +105,10 @@ def parse():
                     help="cap on the thread count of the reference's -T<all> leg: every thread does 240 000 mallocs of 60 KB (alloc_rel_arg for "
                          "MAX_READ_LEN, ~1 GB touched) and the threads serialise on the address-space lock: 0.3 s at -T1, 9.6 s at -T16, 85 s at -T64 (measured)")
     ap.add_argument("--no-extras", action="store_true", help="skip the MHC-like / PCIe / CLI extras (profiling runs)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def self_launch(a):
@@ -120,6 +138,48 @@ def tables_estimate():
     mb = int(os.environ.get("CLASSPRO_SKELLAM_TABLE_MB", "1024"))
     twin = os.environ.get("CLASSPRO_EXP_TABLE", "1") != "0"
     return mb * 2.0 ** 20 * (2 if twin else 1) + 80e6
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20      # --dump-outputs writes at most this much in all, over every rank
+DUMP_SAMPLE_BASES = 12_000_000     # labels of the sampled reads, 4 B each as float32, shared out over the ranks
+DUMP_SEED = 12345
+
+
+def dump_sample(seq_off_all, first, last, nsets=1):
+    """--dump-outputs: global indices of the reads of [first, last) whose labels are written, in read order -- the reads
+    taken in a seeded random order for as long as their bases stay within this rank's part of DUMP_SAMPLE_BASES, one of `nsets`
+    equal parts when every rank writes a set (the same sample on every run)."""
+    lens = np.diff(seq_off_all[first:last + 1])
+    order = np.random.default_rng(DUMP_SEED).permutation(last - first)
+    return np.sort(order[np.cumsum(lens[order]) <= DUMP_SAMPLE_BASES // nsets]) + first
+
+
+def collect_outputs(batches, sample, parts, counts):
+    """What the last step left in the sub-batches' label arrays: the labels of the sampled reads that lie in these
+    sub-batches (appended to `parts`) and the count of every label byte over all their bases (added to `counts`)."""
+    import torch
+    for rd, b in batches:
+        r0 = rd["first"]
+        sel = sample[(sample >= r0) & (sample < r0 + rd["nreads"])] - r0
+        so = rd["seq_off_h"]
+        if len(sel):
+            parts.append(torch.cat([b.labels[int(so[i]):int(so[i + 1])] for i in sel]).cpu().numpy())
+        for p0 in range(0, b.total_bases, 1 << 28):
+            counts += torch.bincount(b.labels[p0:min(b.total_bases, p0 + (1 << 28))], minlength=256).cpu().numpy()
+
+
+def write_outputs(d, suffix, seq_off_all, sample, parts, counts, nsets=1):
+    lab = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    off = np.concatenate([[0], np.cumsum(np.diff(seq_off_all)[sample])])
+    assert off[-1] == lab.size, "sampled labels do not add up to the sampled reads"
+    out = {"labels": lab.astype(np.float32),                  # label bytes ('E', 'H', 'D', 'R', ...) of the sampled reads, concatenated
+           "labels_read_index": sample.astype(np.float64),    # which reads they are (global index in the generated set)
+           "labels_read_offset": off.astype(np.float64),      # where each read's labels start in `labels` (+ the end)
+           "label_counts": counts.astype(np.float64)}         # count of every label byte value 0-255 over the whole output
+    assert sum(v.nbytes for v in out.values()) <= DUMP_MAX_BYTES // nsets, "dump larger than this rank's share of DUMP_MAX_BYTES"
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + suffix + ".npy"), v)
 
 
 def main():
@@ -303,12 +363,14 @@ def main():
         torch.cuda.synchronize()
 
     dt, t_gen, my_bases, my_kmers, nsub = 0.0, 0.0, 0, 0, 0
+    if a.dump_outputs:                                      # what the last step computes, gathered window by window
+        dump_reads, dump_parts, dump_counts = dump_sample(ds.seq_off_all, first, last, world), [], np.zeros(256, dtype=np.int64)
     batches = []
     for wi, (w_first, w_count) in enumerate(windows):
         del batches
         torch.cuda.empty_cache()                            # the previous window's 4 B per base go back before the next is generated
         tg = time.time()
-        batches = make_batches(w_first, w_count, truth=(rank == 0))
+        batches = make_batches(w_first, w_count, truth=(rank == 0 and a.full))   # (the truth serves --full's accuracy figure only)
         t_gen += time.time() - tg
         my_bases += sum(b.total_bases for _, b in batches)
         my_kmers += sum(b.total_kmers for _, b in batches)
@@ -327,7 +389,11 @@ def main():
         dt += time.perf_counter() - t0
         for w in wss:                                       # the error words are sticky: every launch since the last check is covered
             check(L.cp_workspace_check(w))
-    # (the last window stays resident: the roofline loop, the CPU legs and the extras below run on it)
+        if a.dump_outputs:
+            collect_outputs(batches, dump_reads, dump_parts, dump_counts)
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, "" if world == 1 else "_rank%d" % rank, ds.seq_off_all, dump_reads, dump_parts, dump_counts, world)
+    # (the last window stays resident: with --full, the roofline loop, the CPU legs and the extras below run on it)
     win_bases = sum(b.total_bases for _, b in batches)
     win_kmers = sum(b.total_kmers for _, b in batches)
     my_dt = dt
@@ -346,7 +412,7 @@ def main():
     #      host): `value` above is kernels on resident data and scales by construction; this is where 8 feeders contending
     #      for the host's cores and DRAM would show.  Reported per rank in extras.pcie_all_ranks, never as `value`. ----
     pcie_ranks = None
-    if world > 1 and not a.no_extras and not a.no_rank_pcie:
+    if a.full and world > 1 and not a.no_extras and not a.no_rank_pcie:
         import copy
         a2 = copy.copy(a)
         a2.pcie_gbases, a2.pcie_seconds = min(a.pcie_gbases, 1.0), min(a.pcie_seconds, 1.0)
@@ -365,53 +431,54 @@ def main():
 
     if rank == 0:
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        # ---- roofline of the profile-scan kernel: HIP events on the launch stream; every launch streams one
-        #      sub-batch's profile (1.6 GB at the default size), the whole resident set (16 GB >> the 256 MiB
-        #      Infinity Cache) in rotation ----------------------------------------------------------------------
-        # (the library scans a batch in kernel launches of at most 2^31 positions -- capi.hip: launch_scan -- and so does this
-        #  loop: one cp_scan_candidates call per such piece, i.e. per kernel launch)
-        chunk = 1 << 31
-        if os.environ.get("CLASSPRO_SCAN_CHUNK_KMERS"):
-            chunk = max(4096, int(os.environ["CLASSPRO_SCAN_CHUNK_KMERS"]) & ~4095)
-        pieces = []
-        for _, b in batches:
-            for p0 in range(0, max(b.total_kmers, 1), chunk):
-                n = min(chunk, b.total_kmers - p0)
-                pieces.append((b.prof.data_ptr() + 2 * p0, n, torch.zeros(n // 64 + 2, dtype=torch.int64, device=dev)))
-        reps = max(1, 200 // len(pieces))
+        roof, cpu = None, None
+        if a.full:
+            # ---- roofline of the profile-scan kernel: HIP events on the launch stream; every launch streams one
+            #      sub-batch's profile (1.6 GB at the default size), the whole resident set (16 GB >> the 256 MiB
+            #      Infinity Cache) in rotation ----------------------------------------------------------------------
+            # (the library scans a batch in kernel launches of at most 2^31 positions -- capi.hip: launch_scan -- and so does this
+            #  loop: one cp_scan_candidates call per such piece, i.e. per kernel launch)
+            chunk = 1 << 31
+            if os.environ.get("CLASSPRO_SCAN_CHUNK_KMERS"):
+                chunk = max(4096, int(os.environ["CLASSPRO_SCAN_CHUNK_KMERS"]) & ~4095)
+            pieces = []
+            for _, b in batches:
+                for p0 in range(0, max(b.total_kmers, 1), chunk):
+                    n = min(chunk, b.total_kmers - p0)
+                    pieces.append((b.prof.data_ptr() + 2 * p0, n, torch.zeros(n // 64 + 2, dtype=torch.int64, device=dev)))
+            reps = max(1, 200 // len(pieces))
 
-        def scan_all():
-            for ptr, n, bm in pieces:
-                check(L.cp_scan_candidates(clf.p, ptr, n, bm.data_ptr(), stream))
-        scan_all()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(dev))
-        for _ in range(reps):
+            def scan_all():
+                for ptr, n, bm in pieces:
+                    check(L.cp_scan_candidates(clf.p, ptr, n, bm.data_ptr(), stream))
             scan_all()
-        e1.record(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize()
-        nlaunch = reps * len(pieces)
-        scan_ms = e0.elapsed_time(e1) / nlaunch
-        alg_bytes = 2.0 * win_kmers / len(pieces)       # 2 B (uint16 count) per position; average launch
-        achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
-        del pieces
-        traffic, traffic_src = None, None
-        pmc = os.path.join(_ROOT, "profiles", "scan_pmc.json")
-        if os.path.exists(pmc):
-            try:
-                j = json.load(open(pmc))
-                # quoted only for the kernel and launch size it was measured on (rocprofv3 --pmc pass of this command)
-                if j.get("kernel_id") == scan_kernel_id() and abs(j["positions_per_launch"] - alg_bytes / 2) < 0.02 * alg_bytes / 2:
-                    traffic = j["hbm_bytes_per_position"] * alg_bytes / 2
-                    traffic_src = j.get("source")
-            except Exception:
-                traffic = None
-        roof = {"kernel": "k_scan_candidates", "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "ms_per_launch": round(scan_ms, 4), "algorithmic_bytes_per_launch": alg_bytes, "launches_timed": nlaunch,
-                "working_set_bytes": 2.0 * win_kmers}
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(torch.cuda.current_stream(dev))
+            for _ in range(reps):
+                scan_all()
+            e1.record(torch.cuda.current_stream(dev))
+            torch.cuda.synchronize()
+            nlaunch = reps * len(pieces)
+            scan_ms = e0.elapsed_time(e1) / nlaunch
+            alg_bytes = 2.0 * win_kmers / len(pieces)       # 2 B (uint16 count) per position; average launch
+            achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
+            del pieces
+            traffic, traffic_src = None, None
+            pmc = os.path.join(_ROOT, "profiles", "scan_pmc.json")
+            if os.path.exists(pmc):
+                try:
+                    j = json.load(open(pmc))
+                    # quoted only for the kernel and launch size it was measured on (rocprofv3 --pmc pass of this command)
+                    if j.get("kernel_id") == scan_kernel_id() and abs(j["positions_per_launch"] - alg_bytes / 2) < 0.02 * alg_bytes / 2:
+                        traffic = j["hbm_bytes_per_position"] * alg_bytes / 2
+                        traffic_src = j.get("source")
+                except Exception:
+                    traffic = None
+            roof = {"kernel": "k_scan_candidates", "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "ms_per_launch": round(scan_ms, 4), "algorithmic_bytes_per_launch": alg_bytes, "launches_timed": nlaunch,
+                    "working_set_bytes": 2.0 * win_kmers}
 
-        rd0, b0 = batches[0]
         extras = {"pcie_all_ranks": None if pcie_ranks is None else
                   {"what": "PCIe-inclusive pipeline (host packing + H2D + format kernels + classification + 2-bit labels D2H), all ranks at once, 1 Gbase staged per rank",
                    "sum_mbases_per_s": round(sum((x.get("mbases_per_s") or 0) for x in pcie_ranks), 1), "ranks": pcie_ranks},
@@ -425,25 +492,27 @@ def main():
                   "workspace_gb": round(sum(int(L.cp_workspace_bytes(w)) for w in wss) / 1e9, 2),
                   "synth_err_kmer_fraction": round(ds.n_err_kmers / max(1, ds.total_bases), 4)}
 
-        # ---- accuracy against the generator's ground truth (prof2class.c:210-229: multiplicity 0 E, 1 H, 2 D, >=3 R) ----
-        tmap = torch.full((256,), ord("R"), dtype=torch.uint8, device=dev)
-        tmap[0], tmap[1], tmap[2] = ord("E"), ord("H"), ord("D")
-        # (on the first reads of the sub-batch, up to a gigabase: torch's masked indexing counts in 32 bits)
-        na = int(np.searchsorted(rd0["seq_off_h"], min(b0.total_bases, 1_000_000_000), side="right") - 1)
-        nb_a, nk_a = int(rd0["seq_off_h"][na]), int(rd0["prof_off_h"][na])
-        kpos = torch.ones(nb_a, dtype=torch.bool, device=dev)
-        for k in range(K - 1):
-            kpos[b0.seq_off[:na] + k] = False
-        extras["accuracy_vs_synthetic_truth"] = round(float((b0.labels[:nb_a][kpos] == tmap[rd0["truth"][:nk_a].long()]).float().mean()), 5)
-        del kpos
+        if a.full:
+            # ---- accuracy against the generator's ground truth (prof2class.c:210-229: multiplicity 0 E, 1 H, 2 D, >=3 R) ----
+            rd0, b0 = batches[0]
+            tmap = torch.full((256,), ord("R"), dtype=torch.uint8, device=dev)
+            tmap[0], tmap[1], tmap[2] = ord("E"), ord("H"), ord("D")
+            # (on the first reads of the sub-batch, up to a gigabase: torch's masked indexing counts in 32 bits)
+            na = int(np.searchsorted(rd0["seq_off_h"], min(b0.total_bases, 1_000_000_000), side="right") - 1)
+            nb_a, nk_a = int(rd0["seq_off_h"][na]), int(rd0["prof_off_h"][na])
+            kpos = torch.ones(nb_a, dtype=torch.bool, device=dev)
+            for k in range(K - 1):
+                kpos[b0.seq_off[:na] + k] = False
+            extras["accuracy_vs_synthetic_truth"] = round(float((b0.labels[:nb_a][kpos] == tmap[rd0["truth"][:nk_a].long()]).float().mean()), 5)
+            del kpos
 
         # ---- CPU baseline: the oracle (a port, pthreads) on bounded samples of the same workload; every label
         #      of the samples is also compared with the HIP result --------------------------------------------
-        cpu = None
-        if not a.no_cpu and world == 1:                 # (the contract: on rank 0 at N = 1 only)
-            cpu = cpu_baseline(a, ds, batches, hcov, dcov)
-        if not a.no_extras and world == 1 and not a.shard and G <= 200_000_000:
-            extras.update(extra_rates(a, ds, clf, batches, hcov, dcov, dev, stream))
+        if a.full:
+            if not a.no_cpu and world == 1:                 # (the contract: on rank 0 at N = 1 only)
+                cpu = cpu_baseline(a, ds, batches, hcov, dcov)
+            if not a.no_extras and world == 1 and not a.shard and G <= 200_000_000:
+                extras.update(extra_rates(a, ds, clf, batches, hcov, dcov, dev, stream))
 
         out = {
             "metric": "Mbases/s classified (k=40, 40x HiFi) at 1/2/4/8 MI355X vs CPU -T16", "value": round(value, 2), "unit": "Mbases/s",
@@ -452,7 +521,7 @@ def main():
             "data": "synthetic",
             "timed_region": "classification kernels only (cp_classify_batch per sub-batch): bases, uint16 count profiles and labels are "
                             "resident in HBM; H2D, D2H, profile decode, file I/O and the host are OUTSIDE the timed region.  The other rates "
-                            "of the same run: extras.pcie.mbases_per_s (host packing + PCIe + format kernels + kernels + labels back), "
+                            "of a --full run: extras.pcie.mbases_per_s (host packing + PCIe + format kernels + kernels + labels back), "
                             "extras.cli_end_to_end_mbases_per_s (the ClassPro binary on files, process start to exit), extras.host_feed (the host side alone)",
             "config": {"workload": "synthetic %.0f Mbp diploid, %dx HiFi, r=%d, k=40 (%s): %d distinct reads, %.2f Gbases%s; a rank's share resident in HBM "
                                    "%s, sub-batches of at most %.0f Mbases; value = kernels on HBM-resident inputs (see timed_region)"
@@ -464,7 +533,7 @@ def main():
                        "reads_rank0": last - first, "bases_rank0": my_bases, "hcov": hcov, "dcov": dcov,
                        "shard": a.shard,
                        "parallelism": "contiguous read ranges balanced by bases x%d (%s), no collective" % (shard_n if a.shard else world, a.scaling)},
-            "roofline": roof, "cpu_baseline": cpu, "extras": extras,
+            "full": a.full, "roofline": roof, "cpu_baseline": cpu, "extras": extras,
         }
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -11,24 +11,24 @@ TAG=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
-python bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" > $OUT/progress.txt
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --steps 5 --warmup 2 --no-cpu --no-extras > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu --no-extras > $OUT/stats.log 2>&1
 python scripts/timeline.py $(ls $OUT/stats/*/*_kernel_trace.csv | tail -1) $OUT/timeline.txt --skip=4
 echo "stats done" >> $OUT/progress.txt
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python bench.py --steps 1 --warmup 1 --no-cpu --no-extras > $OUT/fetch.log 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python bench.py --steps 1 --warmup 1 --no-cpu --no-extras > $OUT/write.log 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras > $OUT/fetch.log 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras > $OUT/write.log 2>&1
 echo "hbm passes done" >> $OUT/progress.txt
 sq_pass() {
   name=$1; shift
   rm -rf $OUT/sq_tmp
-  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/sq_tmp -- python bench.py --steps 1 --warmup 1 --no-cpu --no-extras --streams 1 > $OUT/sq_$name.log 2>&1 || true
+  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/sq_tmp -- python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras --streams 1 > $OUT/sq_$name.log 2>&1 || true
   python - "$OUT" "$name" "$@" <<'PY'
 import csv, glob, collections, sys
 out, name = sys.argv[1], sys.argv[2]
 f = glob.glob(out + "/sq_tmp/**/*counter_collection.csv", recursive=True)
 w = open("%s/sq_%s.txt" % (out, name), "w")
-w.write("# rocprofv3 --kernel-trace --pmc %s -- python bench.py --steps 1 --warmup 1 --no-cpu --no-extras --streams 1\n" % " ".join(sys.argv[3:]))
+w.write("# rocprofv3 --kernel-trace --pmc %s -- python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras --streams 1\n" % " ".join(sys.argv[3:]))
 if not f:
     w.write("no counter output:\n" + open("%s/sq_%s.log" % (out, name)).read()[-1500:])
     raise SystemExit

@@ -2,7 +2,7 @@
 # round 4: the default bench with the new extras.pcie, the nccl path on one device, the pre-flight message, configs[3] whole at N=1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r4_bench; rm -rf $O; mkdir -p $O
-timeout -k 10 400 python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+timeout -k 10 400 python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
 python - <<'PY'
 import json
 j=json.loads(open("gpurun_out/r4_bench/bench.json").read().strip().splitlines()[-1])

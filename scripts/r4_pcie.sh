@@ -12,7 +12,7 @@ except Exception as e:
     print(sys.argv[2], "failed", e)
 PY
 }
-B="python bench.py --steps 2 --warmup 1 --no-cpu --only-pcie"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu --only-pcie"
 run base $B
 run base_again $B
 run slots4 $B --pcie-slots 4

@@ -11,11 +11,11 @@ except Exception as e:
     print(sys.argv[2], "failed", e, open(sys.argv[1].replace(".json",".err")).read()[-500:])
 PY
 }
-B="python bench.py --steps 2 --warmup 1 --no-cpu --only-pcie"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu --only-pcie"
 run base $B
 run base_again $B
 run full8 $B --pcie-gbases 8
-rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $O/trace -- python bench.py --steps 1 --warmup 1 --no-cpu --only-pcie --pcie-seconds 0.3 > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $O/trace -- python bench.py --full --steps 1 --warmup 1 --no-cpu --only-pcie --pcie-seconds 0.3 > $O/trace.log 2>&1
 echo "trace rc=$?"; ls $O/trace/*/ | head
 python - <<'PY'
 import csv,glob

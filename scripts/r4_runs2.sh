@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r4_runs2; rm -rf $O; mkdir -p $O
 for i in 1 2; do
-python bench.py --steps 2 --warmup 1 --no-cpu --only-pcie > $O/p$i.json 2> $O/p$i.err; python - $i <<'PY'
+python bench.py --full --steps 2 --warmup 1 --no-cpu --only-pcie > $O/p$i.json 2> $O/p$i.err; python - $i <<'PY'
 import json,sys
 try:
     j=json.loads(open("gpurun_out/r4_runs2/p%s.json"%sys.argv[1]).read().strip().splitlines()[-1]); p=j["extras"].get("pcie") or j["extras"]

@@ -45,7 +45,7 @@ for kind in ("fetch", "write"):
             k = k[5:]
         agg[(k.replace(" ", ""), r["Counter_Name"])].append(float(r["Counter_Value"]))
 with open(os.path.join(dst, name + "_pmc.txt"), "w") as f:
-    f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --steps 1 --warmup 1 --no-cpu --no-extras`\n")
+    f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras`\n")
     f.write("# values in KiB per dispatch as reported; gfx950 correction for streaming reads: bytes = 2*FETCH_SIZE*1024\n")
     f.write("%-36s %-11s %6s %14s %14s %14s\n" % ("kernel", "counter", "n", "avg_KiB", "min_KiB", "max_KiB"))
     tot = collections.Counter()
@@ -67,7 +67,7 @@ wsz = agg[("k_scan_candidates", "WRITE_SIZE")]
 fetch = 2.0 * 1024 * sum(fs) / len(fs)
 write = 1024.0 * sum(wsz) / len(wsz)
 json.dump({"kernel": "k_scan_candidates", "kernel_id": kernel_id, "positions_per_launch": kmers,
-           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --steps 1 --warmup 1 --no-cpu --no-extras (scripts/profile_round.sh)",
+           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --full --steps 1 --warmup 1 --no-cpu --no-extras (scripts/profile_round.sh)",
            "fetch_bytes_per_launch_corrected": fetch, "write_bytes_per_launch": write,
            "hbm_bytes_per_position": (fetch + write) / kmers,
            "source": "profiles/%s_pmc.txt (FETCH_SIZE x2 per MI355X_MICROARCH.md HBM section)" % name},

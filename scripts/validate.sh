@@ -8,14 +8,14 @@ python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1 || { tail -30 $O/pytest
 tail -2 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 j=json.loads(open("gpurun_out/validate/bench.json").read().strip().splitlines()[-1])
 print("default:", j["value"], j["ms_per_step"], j["roofline"]["frac"], j["cpu_baseline"]["value"], j["cpu_baseline"]["label_mismatches_vs_hip"])
 print({k:v for k,v in j["extras"].items() if k not in ("cli_end_to_end",)})
 PY
-python bench.py --gpus 2 --backend gloo --genome 4e8 --window-gbases 4 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err || { tail $O/n2.err; exit 1; }
+python bench.py --full --gpus 2 --backend gloo --genome 4e8 --window-gbases 4 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err || { tail $O/n2.err; exit 1; }
 python - <<'PY'
 import json
 j=json.loads(open("gpurun_out/validate/n2.json").read().strip().splitlines()[-1])
