@@ -17,9 +17,19 @@ SYMBOLS = [
     "cp_encode_profile", "cp_decode_profiles", "cp_params_create_model", "cp_params_create_pe", "cp_load_error_model", "cp_unpack_bases",
     "cp_find_seeds_batch", "cp_get_rep_masks", "cp_rep_masks_capacity", "cp_params_tables", "cp_pack_bases", "cp_pack_labels", "cp_unpack_labels", "cp_math_eval", "cp_pack_bases_batch",
     "cp_label_runs", "cp_label_runs_capacity", "cp_expand_label_runs",
+    "cp_kmer_table_create", "cp_kmer_table_destroy", "cp_kmer_table_add", "cp_kmer_table_stats",
+    "cp_kmer_table_consensus", "cp_kmer_table_export",
 ]
 
 _lib = None
+
+
+class KmerStats(C.Structure):
+    """cp_kmer_stats of include/classpro_amd.h."""
+    _fields_ = [("n_kmers", C.c_int64), ("n_skipped", C.c_int64), ("n_distinct", C.c_int64), ("n_unanimous", C.c_int64),
+                ("label_total", C.c_int64 * 4), ("cns_total", C.c_int64 * 4), ("s_fixed_hi", C.c_uint64),
+                ("s_fixed_lo", C.c_uint64), ("consistency", C.c_double), ("slots", C.c_int64), ("bytes", C.c_int64),
+                ("growths", C.c_int64)]
 
 
 class ClassProError(RuntimeError):
@@ -88,6 +98,14 @@ def lib():
     L.cp_get_rep_masks.argtypes = [vp, vp, vp, vp, i64]
     L.cp_rep_masks_capacity.argtypes = [vp]
     L.cp_rep_masks_capacity.restype = i64
+    L.cp_kmer_table_create.argtypes = [i32, i32, i64, C.POINTER(vp)]
+    L.cp_kmer_table_destroy.argtypes = [vp]
+    L.cp_kmer_table_destroy.restype = None
+    L.cp_kmer_table_add.argtypes = [vp, vp, vp, vp, i32, i64, vp]
+    L.cp_kmer_table_stats.argtypes = [vp, C.POINTER(KmerStats)]
+    L.cp_kmer_table_consensus.argtypes = [vp, vp, vp, i32, i64, vp, vp]
+    L.cp_kmer_table_export.argtypes = [vp, vp, vp, vp, i64]
+    L.cp_kmer_table_export.restype = i64
     _lib = L
     return L
 

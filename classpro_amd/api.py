@@ -320,3 +320,87 @@ class Classifier:
         lh, rh = l.cpu().numpy(), r.cpu().numpy()
         so = b.seq_off_h
         return [(lh[so[i]:so[i + 1]], rh[so[i]:so[i + 1]]) for i in range(b.nreads)]
+
+
+class KmerTable:
+    """Per-k-mer label table on the device (cp_kmer_table_*; semantics in include/classpro_amd.h): counts, for every
+    distinct k-mer, how often each label E/H/D/R was given to it across the reads added, then gives the consensus label
+    per k-mer, the statistics and the consistency figure of the reference's agg2cons.py.  canonical=True keys a k-mer and
+    its reverse complement together.  initial_slots only matters for tests that force growth."""
+
+    LABELS = "EHDR"
+
+    def __init__(self, K, canonical=False, device="cuda:0", initial_slots=0):
+        from ._lib import KmerStats
+        self.L = lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("classpro_amd runs on a HIP device only")
+        torch.cuda.set_device(self.device)
+        self.K, self.canonical = K, bool(canonical)
+        self._Stats = KmerStats
+        t = C.c_void_p()
+        check(self.L.cp_kmer_table_create(K, int(self.canonical), int(initial_slots), C.byref(t)))
+        self.t = t
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "t", None):
+            self.L.cp_kmer_table_destroy(self.t)
+            self.t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_tensors(self, seq, seq_off, labels):
+        """Adds a batch given as device tensors in the flat layout: seq uint8, seq_off int64 [n+1], labels uint8."""
+        n = seq_off.numel() - 1
+        total = int(seq_off[-1].item()) if n > 0 else 0
+        check(self.L.cp_kmer_table_add(self.t, seq.data_ptr(), seq_off.data_ptr(), labels.data_ptr(), n, total,
+                                       self._stream()))
+
+    def add(self, b):
+        """Adds a `Batch` labelled by Classifier.classify / run (its `labels` tensor)."""
+        check(self.L.cp_kmer_table_add(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.labels.data_ptr(), b.nreads,
+                                       b.total_bases, self._stream()))
+
+    def stats(self):
+        s = self._Stats()
+        check(self.L.cp_kmer_table_stats(self.t, C.byref(s)))
+        d = {f: getattr(s, f) for f, _ in s._fields_}
+        d["label_total"] = list(s.label_total)
+        d["cns_total"] = list(s.cns_total)
+        d["s_fixed"] = (s.s_fixed_hi << 64) | s.s_fixed_lo
+        return d
+
+    def consensus_tensors(self, seq, seq_off, labels):
+        """Consensus labels for a batch given as device tensors: a new uint8 tensor in the layout of `labels`."""
+        out = labels.clone()
+        n = seq_off.numel() - 1
+        total = int(seq_off[-1].item()) if n > 0 else 0
+        check(self.L.cp_kmer_table_consensus(self.t, seq.data_ptr(), seq_off.data_ptr(), n, total, out.data_ptr(),
+                                             self._stream()))
+        return out
+
+    def consensus(self, b):
+        """Consensus labels for the reads of a labelled `Batch`: a device uint8 tensor in the layout of b.labels (K-1 'N',
+        then the consensus label of each k-mer; a skipped k-mer keeps its own label)."""
+        out = b.labels.clone()
+        check(self.L.cp_kmer_table_consensus(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.nreads, b.total_bases,
+                                             out.data_ptr(), self._stream()))
+        return out
+
+    def entries(self):
+        """Occupied entries in key order: numpy (hi uint64, lo uint64, counts uint32[n, 4] in order E, H, D, R), key =
+        hi << 63 | lo."""
+        n = check(self.L.cp_kmer_table_export(self.t, None, None, None, 0))
+        hi, lo = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+        cnt = np.zeros((max(n, 1), 4), np.uint32)
+        m = check(self.L.cp_kmer_table_export(self.t, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, n))
+        assert m == n
+        return hi[:n], lo[:n], cnt[:n]

@@ -1162,3 +1162,6 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
   return CP_OK;
 }
 #endif
+
+// per-k-mer label table (class2cns): kmer_table.hip
+#include "kmer_table.hip"

@@ -1,0 +1,243 @@
+// class2cns.cpp -- per-k-mer label consensus and consistency of a .class file.
+//
+//   class2cns [-v] [-c] [-u] [-x] [-C<out.class>] <estimate>.class <fastk_root>[.prof]
+//
+// Without -u, -x or -C this is the reference's tool (src/class2cns.c:15-78): one line "KMER L" per k-mer position
+// (i in [K-1, rlen), K from the .prof stub), the input of scripts/naive_consensus.sh's `sort | uniq -c`.  That mode
+// runs on the host only and never touches the GPU.  The flags replace the rest of that pipeline with the device
+// table of include/classpro_amd.h (cp_kmer_table_*), on GPU 0:
+//   -u  the aggregated table, "%7ld KMER L" per (k-mer, label) with a count > 0, in key order then label order
+//       D < E < H < R: byte for byte `class2cns est.class root | LC_ALL=C sort | uniq -c` when every k-mer is made
+//       of upper-case A C G T (the table skips other k-mers).
+//   -x  "Overall consistency = <v>", the harmonic mean of agg2cons.py's most-common fraction, <v> printed as the
+//       shortest string that reads back as the same double (Python's repr).
+//   -C  a second pass writes <out.class>: the input's headers and sequences, the consensus labels (tie: R > D > H > E).
+//   -c  canonical k-mers (a k-mer and its reverse complement share one entry) for -u, -x and -C; under -u each line
+//       then carries the canonical k-mer's text.
+//   -v  a summary on stderr: distinct, unanimous and skipped k-mers, table size.
+#include <hip/hip_runtime.h>
+#include <charconv>
+#include <cmath>
+#include "host_io.h"
+#include "../../../include/classpro_amd.h"
+
+static const char *USAGE = "[-v] [-c] [-u] [-x] [-C<out.class>] <estimate>.class <fastk_root>[.prof]";
+
+static const int64_t BATCH_BASES = (int64_t)256 << 20;        // bases per device batch
+
+static void cp_die(int rc, const char *what)
+{ die("%s: %s: %s (%d)\n",PROG,what,cp_last_error(),rc); }
+
+static void hip_die(hipError_t e, const char *what)
+{ die("%s: %s: %s\n",PROG,what,hipGetErrorString(e)); }
+
+#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
+
+// host and device buffers of one batch of records (pinned host memory)
+struct Batch
+  { char *h_seq = nullptr, *h_lab = nullptr, *d_seq = nullptr, *d_lab = nullptr;
+    int64_t *h_off = nullptr, *d_off = nullptr;
+    int64_t cap_bases = 0, cap_reads = 0, nbases = 0;
+    int nreads = 0;
+
+    void reserve(int64_t bases, int64_t reads)
+    { if (bases > cap_bases)
+        { if (h_seq) { HCHK(hipHostFree(h_seq)); HCHK(hipHostFree(h_lab)); HCHK(hipFree(d_seq)); HCHK(hipFree(d_lab)); }
+          HCHK(hipHostMalloc((void **)&h_seq,bases,hipHostMallocDefault));
+          HCHK(hipHostMalloc((void **)&h_lab,bases,hipHostMallocDefault));
+          HCHK(hipMalloc((void **)&d_seq,bases));
+          HCHK(hipMalloc((void **)&d_lab,bases));
+          cap_bases = bases;
+        }
+      if (reads+1 > cap_reads)
+        { if (h_off) { HCHK(hipHostFree(h_off)); HCHK(hipFree(d_off)); }
+          HCHK(hipHostMalloc((void **)&h_off,(reads+1)*8,hipHostMallocDefault));
+          HCHK(hipMalloc((void **)&d_off,(reads+1)*8));
+          cap_reads = reads+1;
+        }
+    }
+    void upload(bool labels)
+    { HCHK(hipMemcpy(d_seq,h_seq,nbases,hipMemcpyHostToDevice));
+      if (labels) HCHK(hipMemcpy(d_lab,h_lab,nbases,hipMemcpyHostToDevice));
+      HCHK(hipMemcpy(d_off,h_off,(nreads+1)*8,hipMemcpyHostToDevice));
+    }
+  };
+
+// Reads the records of `path` in batches of about BATCH_BASES bases; calls f(batch, headers) for each.
+template <class F>
+static void for_batches(const char *path, Batch &B, bool keep_headers, F f)
+{ FastxReader in(path);
+  if (!in.f) die("%s: Cannot open %s [errno=%d]\n",PROG,path,errno);
+  std::vector<std::string> headers;
+  B.reserve(BATCH_BASES,1 << 16);
+  B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
+  auto flush = [&]()
+    { if (B.nreads) f(B,headers);
+      B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
+      headers.clear();
+    };
+  while (in.next() >= 0)
+    { const int64_t n = (int64_t)in.seq.size();
+      if (in.qual.size() != in.seq.size())
+        die("%s: record %s of %s carries no labels\n",PROG,in.name.c_str(),path);
+      if (B.nbases+n > B.cap_bases || B.nreads+1 >= B.cap_reads) flush();
+      if (n > B.cap_bases) B.reserve(n,B.cap_reads);
+      memcpy(B.h_seq+B.nbases,in.seq.data(),n);
+      memcpy(B.h_lab+B.nbases,in.qual.data(),n);
+      B.nbases += n;
+      B.h_off[++B.nreads] = B.nbases;
+      if (keep_headers)
+        headers.push_back("@"+in.name+(in.rec_comment ? " "+in.comment : std::string()));
+    }
+  flush();
+}
+
+static std::string kmer_text(uint64_t hi, uint64_t lo, int K)
+{ std::string s((size_t)K,'A');
+  for (int i = 0; i < K; i++)                                // base i from the start: key bits 2(K-1-i)+1 .. 2(K-1-i)
+    { const int b = 2*(K-1-i);
+      const unsigned v = b >= 63 ? (unsigned)(hi >> (b-63)) & 3 : b == 62 ? (unsigned)((lo >> 62) | (hi << 1)) & 3
+                                                                          : (unsigned)(lo >> b) & 3;
+      s[(size_t)i] = "ACGT"[v];
+    }
+  return s;
+}
+
+static std::string repr_double(double v)
+{ char buf[64];
+  if (std::isnan(v)) return "nan";
+  auto r = std::to_chars(buf,buf+sizeof(buf),v,std::chars_format::fixed);
+  std::string s(buf,r.ptr);
+  if (s.find('.') == std::string::npos) s += ".0";
+  return s;
+}
+
+int main(int argc, char **argv)
+{ PROG = "class2cns";
+  bool verbose = false, canon = false, table = false, cons = false;
+  const char *cns_out = nullptr;
+  std::vector<std::string> pos;
+  for (int i = 1; i < argc; i++)
+    { const char *a = argv[i];
+      if (a[0] != '-') { pos.push_back(a); continue; }
+      if (a[1] == 'C')
+        { if (a[2] == '\0') die("%s: -C needs an output path (-C<out.class>)\n",PROG);
+          cns_out = a+2;
+          continue;
+        }
+      for (int k = 1; a[k]; k++)                                 // ARG_FLAGS("vcux")
+        switch (a[k])
+          { case 'v': verbose = true; break;
+            case 'c': canon = true; break;
+            case 'u': table = true; break;
+            case 'x': cons = true; break;
+            default: die("%s: -%c is an illegal option\n",PROG,a[k]);
+          }
+    }
+  if (pos.size() != 2)
+    die("Usage: %s %s\n",PROG,USAGE);
+  const char *cls = pos[0].c_str();
+  { FastxReader probe(cls);                                      // class2cns.c:48-52, then 54-62
+    if (!probe.f) die("%s: Cannot open %s [errno=%d]\n",PROG,cls,errno);
+  }
+  Profiles P;
+  if (!P.open(pos[1]))
+    die("%s: Cannot open %s.prof\n",PROG,pos[1].c_str());
+  const int K = P.kmer, Km1 = K-1;
+
+  static char obuf[1 << 22];
+  setvbuf(stdout,obuf,_IOFBF,sizeof(obuf));
+  if (!table && !cons && !cns_out)                               // the reference's mode, class2cns.c:62-68
+    { FastxReader in(cls);
+      std::string line;
+      while (in.next() >= 0)
+        { const std::string &s = in.seq, &q = in.qual;
+          const int n = (int)s.size();
+          if (n > Km1 && q.size() < s.size())
+            die("%s: record %s of %s carries no labels\n",PROG,in.name.c_str(),cls);
+          for (int i = Km1; i < n; i++)
+            { line.assign(s,(size_t)(i-Km1),(size_t)K);
+              line.push_back(' ');
+              line.push_back(q[(size_t)i]);
+              line.push_back('\n');
+              fwrite(line.data(),1,line.size(),stdout);
+            }
+        }
+      fflush(stdout);
+      return 0;
+    }
+
+  HCHK(hipSetDevice(0));
+  cp_kmer_table *T = nullptr;
+  int rc = cp_kmer_table_create(K,canon ? 1 : 0,0,&T);
+  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_create");
+  Batch B;
+  for_batches(cls,B,false,[&](Batch &b, std::vector<std::string> &)
+    { b.upload(true);
+      int r = cp_kmer_table_add(T,b.d_seq,b.d_off,b.d_lab,b.nreads,b.nbases,nullptr);
+      if (r != CP_OK) cp_die(r,"cp_kmer_table_add");
+      HCHK(hipStreamSynchronize(nullptr));                        // the host buffers are refilled next
+    });
+  cp_kmer_stats st;
+  rc = cp_kmer_table_stats(T,&st);
+  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_stats");
+  if (verbose)
+    fprintf(stderr,"%s: K = %d%s: %lld k-mer positions, %lld distinct k-mers, %lld unanimous, %lld skipped "
+                   "(a base other than A C G T); table %lld slots, %.3f GB, %lld growth steps\n",
+            PROG,K,canon ? " canonical" : "",(long long)st.n_kmers,(long long)st.n_distinct,(long long)st.n_unanimous,
+            (long long)st.n_skipped,(long long)st.slots,st.bytes/1e9,(long long)st.growths);
+
+  if (table)
+    { const int64_t n = cp_kmer_table_export(T,nullptr,nullptr,nullptr,0);
+      if (n < 0) cp_die((int)n,"cp_kmer_table_export");
+      std::vector<uint64_t> hi((size_t)std::max<int64_t>(n,1)), lo(hi.size());
+      std::vector<uint32_t> cnt(4*hi.size());
+      const int64_t m = cp_kmer_table_export(T,hi.data(),lo.data(),cnt.data(),n);
+      if (m != n) cp_die((int)m,"cp_kmer_table_export");
+      static const int ORDER[4] = { 2, 0, 1, 3 };                   // D < E < H < R (counts are stored E, H, D, R)
+      char buf[48];
+      for (int64_t i = 0; i < n; i++)
+        { const std::string km = kmer_text(hi[(size_t)i],lo[(size_t)i],K);
+          for (int o = 0; o < 4; o++)
+            { const uint32_t c = cnt[(size_t)(4*i+ORDER[o])];
+              if (!c) continue;
+              snprintf(buf,sizeof(buf),"%7ld ",(long)c);
+              fputs(buf,stdout);
+              fwrite(km.data(),1,km.size(),stdout);
+              fputc(' ',stdout);
+              fputc("EHDR"[ORDER[o]],stdout);
+              fputc('\n',stdout);
+            }
+        }
+    }
+  if (cons)
+    fprintf(stdout,"Overall consistency = %s\n",repr_double(st.consistency).c_str());
+  fflush(stdout);
+
+  if (cns_out)
+    { FILE *out = fopen(cns_out,"w");
+      if (!out) die("%s: Cannot open %s for 'w'\n",PROG,cns_out);
+      std::vector<char> wbuf(1 << 22);
+      setvbuf(out,wbuf.data(),_IOFBF,wbuf.size());
+      for_batches(cls,B,true,[&](Batch &b, std::vector<std::string> &headers)
+        { b.upload(true);
+          int r = cp_kmer_table_consensus(T,b.d_seq,b.d_off,b.nreads,b.nbases,b.d_lab,nullptr);
+          if (r != CP_OK) cp_die(r,"cp_kmer_table_consensus");
+          HCHK(hipMemcpy(b.h_lab,b.d_lab,b.nbases,hipMemcpyDeviceToHost));
+          for (int i = 0; i < b.nreads; i++)
+            { const int64_t s = b.h_off[i], n = b.h_off[i+1]-s;
+              fputs(headers[(size_t)i].c_str(),out);
+              fputc('\n',out);
+              fwrite(b.h_seq+s,1,(size_t)n,out);
+              fputs("\n+\n",out);
+              fwrite(b.h_lab+s,1,(size_t)n,out);
+              fputc('\n',out);
+            }
+        });
+      rc = cp_kmer_table_stats(T,&st);                              // a k-mer missing from the table would show here
+      if (rc != CP_OK) cp_die(rc,"cp_kmer_table_consensus");
+      if (fclose(out) != 0) die("%s: Cannot write %s\n",PROG,cns_out);
+    }
+  cp_kmer_table_destroy(T);
+  return 0;
+}

@@ -61,6 +61,7 @@ struct FastxReader
     int last;                      // last header char seen ('>' or '@'), 0 = none
     std::string name, comment, seq, qual;
     bool have_comment;
+    bool rec_comment = false;      // the record just read had a comment of its own (class2cns -C rewrites headers)
     bool bad_qual = false;         // FASTQ record whose quality string is not as long as its sequence (kseq: -2)
 
     explicit FastxReader(const char *path) : f(gzopen(path,"r")), buf(1 << 20), beg(0), end(0), eof(false), last(0), have_comment(false)
@@ -119,6 +120,7 @@ struct FastxReader
         }
       else if (c == '\r')
         rest_of_line(nullptr,false);
+      rec_comment = got_comment;
       if (got_comment) { comment = cm; have_comment = true; }    // kseq leaves the old comment buffer otherwise
       while ((c = getc()) != -1 && c != '>' && c != '+' && c != '@')
         { if (c == '\n') continue;

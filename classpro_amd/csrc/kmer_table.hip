@@ -1,0 +1,561 @@
+// kmer_table.hip -- per-k-mer label table on the device (class2cns): how often each distinct k-mer of a labelled batch
+// got each of the labels E/H/D/R, the consensus label per k-mer and the consistency figure of the reference's
+// scripts/agg2cons.py.  Semantics: include/classpro_amd.h, "Per-k-mer label table".  Included by capi.hip (set_err,
+// HIPCHK and the library's error contract are shared).
+//
+// The table is open addressing with linear probing, one 32-byte slot per key: hi = key bits 125..63, lo = key bits
+// 62..0, four u32 counts.  A key has at most 126 bits, so the all-ones word never is a half of a key and marks an
+// EMPTY half.  An insert never waits on another lane: it CASes hi from EMPTY (or finds it equal), then lo from EMPTY
+// (or finds it equal), and adds one count; a slot's (hi, lo) once set never changes, so every insert of one key stops
+// at the same slot (the first one of its probe sequence whose final key is that key).  Probing is bounded
+// (KT_PROBE); an insert that runs past the bound sets its position's bit in a failure bitmap and adds nothing.  The
+// host then grows the table (rehash into at least twice the slots) and replays exactly the failed positions.
+#include <algorithm>
+
+typedef unsigned __int128 kt_u128;
+
+#define KT_EMPTY  0xFFFFFFFFFFFFFFFFull
+#define KT_M63    0x7FFFFFFFFFFFFFFFull
+#define KT_PROBE  64                       // slots looked at per insert / lookup before an insert counts as failed
+#define KT_CHUNK  64                       // consecutive k-mer positions one lane rolls its key over
+#define KT_BLOCK  256
+#define KT_ERR_LABEL    1u                 // a counted position held a label other than E/H/D/R
+#define KT_ERR_OVERFLOW 2u                 // a count passed 2^32-1
+
+struct kt_slot { unsigned long long hi, lo; unsigned int cnt[4]; };          // cnt in label order E, H, D, R
+static_assert(sizeof(kt_slot) == 32, "one 32-byte slot per key");
+
+struct kt_ctl                                                                 // device-side counters of one table
+  { unsigned long long n_fail;            // failed inserts of the last add / replay launch
+    unsigned long long n_occ;             // occupied slots = distinct keys
+    unsigned long long n_skip;            // k-mer positions skipped (a base other than upper-case A C G T)
+    unsigned long long n_rfail;           // failed inserts of the last rehash
+    unsigned long long n_out;             // export: entries written
+    unsigned int err, pad;
+  };
+
+struct kt_part                                                                // one block's share of the statistics
+  { unsigned long long n_distinct, n_unanimous, label_total[4], cns_total[4], s_hi, s_lo; };
+
+__host__ __device__ static inline unsigned long long kt_mix(unsigned long long x)
+{ x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return x;
+}
+
+__device__ static inline unsigned long long kt_home(unsigned long long hi, unsigned long long lo)
+{ return kt_mix(lo ^ kt_mix(hi ^ 0x9e3779b97f4a7c15ull)); }
+
+__device__ static inline int kt_base(unsigned char c)                        // A C G T -> 0..3, anything else -1
+{ return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+
+__device__ static inline int kt_label(unsigned char c)                       // E H D R -> 0..3, anything else -1
+{ return c == 'E' ? 0 : c == 'H' ? 1 : c == 'D' ? 2 : c == 'R' ? 3 : -1; }
+
+// consensus label: the largest count; a tie goes to the larger copy number, R > D > H > E
+__host__ __device__ static inline int kt_consensus(const unsigned int *c)
+{ int best = 0;
+  for (int l = 1; l < 4; l++)
+    if (c[l] >= c[best]) best = l;
+  return best;
+}
+
+__device__ static inline unsigned long long kt_load(const unsigned long long *p)
+{ return __hip_atomic_load(p,__ATOMIC_RELAXED,__HIP_MEMORY_SCOPE_AGENT); }
+
+// Finds or claims the slot of (hi, lo); returns it, or NULL after KT_PROBE slots.  *claimed: this lane set lo.
+__device__ static inline kt_slot *kt_find_or_claim(kt_slot *tab, unsigned long long mask, unsigned long long hi,
+                                                   unsigned long long lo, bool *claimed)
+{ unsigned long long s = kt_home(hi,lo) & mask;
+  for (int p = 0; p < KT_PROBE; p++, s = (s+1) & mask)
+    { kt_slot *e = tab+s;
+      unsigned long long h = kt_load(&e->hi);
+      if (h == KT_EMPTY)
+        { const unsigned long long o = atomicCAS(&e->hi,KT_EMPTY,hi);
+          h = (o == KT_EMPTY) ? hi : o;
+        }
+      if (h != hi) continue;
+      unsigned long long w = kt_load(&e->lo);
+      if (w == KT_EMPTY)
+        { const unsigned long long o = atomicCAS(&e->lo,KT_EMPTY,lo);
+          if (o == KT_EMPTY) { w = lo; *claimed = true; }
+          else w = o;
+        }
+      if (w == lo) return e;
+    }
+  return nullptr;
+}
+
+// Read-only lookup (the table is not written while it runs).
+__device__ static inline const kt_slot *kt_lookup(const kt_slot *tab, unsigned long long mask, unsigned long long hi,
+                                                  unsigned long long lo)
+{ unsigned long long s = kt_home(hi,lo) & mask;
+  for (int p = 0; p < KT_PROBE; p++, s = (s+1) & mask)
+    { const kt_slot *e = tab+s;
+      const unsigned long long h = e->hi;
+      if (h == KT_EMPTY) return nullptr;
+      if (h == hi && e->lo == lo) return e;
+    }
+  return nullptr;
+}
+
+// Walks the k-mer positions [p0, p0+KT_CHUNK) of the flat batch (global base index j, k-mer = seq[j-K+1..j] of j's
+// read, j >= read start + K-1), rolling the forward key and its reverse complement one base at a time.  Calls
+// f(j, hi, lo) for every k-mer of upper-case A C G T only; returns the number of the others.
+template <bool CANON, class F>
+__device__ static inline unsigned long long kt_walk(const char *seq, const int64_t *seq_off, int nreads, int64_t total,
+                                                    int K, int64_t p0, F f)
+{ const int64_t p1 = min(p0+(int64_t)KT_CHUNK,total);
+  int lo_r = 0, hi_r = nreads;                          // the read holding p0: seq_off[r] <= p0 < seq_off[r+1]
+  while (hi_r-lo_r > 1)
+    { const int mid = (lo_r+hi_r) >> 1;
+      if (seq_off[mid] <= p0) lo_r = mid; else hi_r = mid;
+    }
+  const kt_u128 kmask = (((kt_u128)1) << (2*K))-1;
+  const int rshift = 2*K-2;
+  unsigned long long nskip = 0;
+  int r = lo_r;
+  for (int64_t p = p0; p < p1 && r < nreads; r++)
+    { const int64_t rs = seq_off[r], re = seq_off[r+1];
+      if (re <= p) continue;                            // empty reads
+      const int64_t q1 = min(p1,re);
+      const int64_t first = max(p,rs+K-1);
+      if (first < q1)
+        { kt_u128 fw = 0, rc = 0;
+          int valid = 0;
+          for (int64_t j = first-K+1; j < q1; j++)
+            { const int b = kt_base((unsigned char)seq[j]);
+              if (b < 0) { valid = 0; fw = 0; rc = 0; }
+              else
+                { fw = ((fw << 2) | (kt_u128)b) & kmask;
+                  rc = (rc >> 2) | (((kt_u128)(3-b)) << rshift);
+                  valid++;
+                }
+              if (j < first) continue;
+              if (valid < K) { nskip++; continue; }
+              const kt_u128 key = (CANON && rc < fw) ? rc : fw;
+              f(j,(unsigned long long)(key >> 63),(unsigned long long)key & KT_M63);
+            }
+        }
+      p = q1;
+    }
+  return nskip;
+}
+
+// One add pass (REPLAY = false) or a replay of the positions whose bit is set in fail_in (REPLAY = true).
+template <bool CANON, bool REPLAY>
+__global__ void __launch_bounds__(KT_BLOCK) kt_add_kernel(kt_slot *tab, unsigned long long mask, const char *seq,
+                                                          const int64_t *seq_off, const char *labels, int nreads,
+                                                          int64_t total, int K, const unsigned int *fail_in,
+                                                          unsigned int *fail_out, kt_ctl *ctl)
+{ const int64_t p0 = ((int64_t)blockIdx.x*blockDim.x+threadIdx.x)*KT_CHUNK;
+  if (p0 >= total) return;
+  unsigned long long nfail = 0, nocc = 0;
+  unsigned int err = 0;
+  const unsigned long long nskip = kt_walk<CANON>(seq,seq_off,nreads,total,K,p0,
+    [&](int64_t j, unsigned long long hi, unsigned long long lo)
+    { if (REPLAY && !((fail_in[j >> 5] >> (j & 31)) & 1u)) return;
+      const int l = kt_label((unsigned char)labels[j]);
+      if (l < 0) { err |= KT_ERR_LABEL; return; }
+      bool claimed = false;
+      kt_slot *e = kt_find_or_claim(tab,mask,hi,lo,&claimed);
+      nocc += claimed;
+      if (!e)
+        { atomicOr(&fail_out[j >> 5],1u << (j & 31));
+          nfail++;
+          return;
+        }
+      if (atomicAdd(&e->cnt[l],1u) == 0xFFFFFFFFu) err |= KT_ERR_OVERFLOW;
+    });
+  if (nfail) atomicAdd(&ctl->n_fail,nfail);
+  if (nocc) atomicAdd(&ctl->n_occ,nocc);
+  if (!REPLAY && nskip) atomicAdd(&ctl->n_skip,nskip);
+  if (err) atomicOr(&ctl->err,err);
+}
+
+__global__ void __launch_bounds__(KT_BLOCK) kt_fill_kernel(kt_slot *tab, unsigned long long n)
+{ for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { kt_slot e;
+      e.hi = e.lo = KT_EMPTY;
+      e.cnt[0] = e.cnt[1] = e.cnt[2] = e.cnt[3] = 0;
+      tab[s] = e;
+    }
+}
+
+// every occupied slot of `old` into `tab` (distinct keys: each lane claims a slot of its own, then stores its counts)
+__global__ void __launch_bounds__(KT_BLOCK) kt_rehash_kernel(const kt_slot *old, unsigned long long n_old, kt_slot *tab,
+                                                             unsigned long long mask, kt_ctl *ctl)
+{ unsigned long long nfail = 0;
+  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n_old;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kt_slot o = old[s];
+      if (o.lo == KT_EMPTY) continue;
+      bool claimed = false;
+      kt_slot *e = kt_find_or_claim(tab,mask,o.hi,o.lo,&claimed);
+      if (!e || !claimed) { nfail++; continue; }
+      e->cnt[0] = o.cnt[0]; e->cnt[1] = o.cnt[1]; e->cnt[2] = o.cnt[2]; e->cnt[3] = o.cnt[3];
+    }
+  if (nfail) atomicAdd(&ctl->n_rfail,nfail);
+}
+
+// per-block partial statistics over the occupied slots (integer sums only: the result does not depend on the order)
+__global__ void __launch_bounds__(KT_BLOCK) kt_stats_kernel(const kt_slot *tab, unsigned long long n, kt_part *parts)
+{ kt_part a = {};
+  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kt_slot e = tab[s];
+      if (e.lo == KT_EMPTY) continue;
+      unsigned long long tot = 0, mx = 0;
+      for (int l = 0; l < 4; l++)
+        { tot += e.cnt[l];
+          mx = max(mx,(unsigned long long)e.cnt[l]);
+          a.label_total[l] += e.cnt[l];
+        }
+      a.n_distinct++;
+      a.n_unanimous += (tot == mx);
+      a.cns_total[kt_consensus(e.cnt)] += tot;
+      // floor(tot * 2^64 / mx) = q * 2^64 + floor(r * 2^64 / mx), the fraction by two 32-bit long-division steps
+      // (mx < 2^32, r < mx)
+      const unsigned long long q = tot/mx, r = tot%mx;
+      const unsigned long long a1 = r << 32, q1 = a1/mx, r1 = a1%mx, q2 = (r1 << 32)/mx;
+      const unsigned long long frac = (q1 << 32) | q2;
+      a.s_lo += frac;
+      a.s_hi += q+(a.s_lo < frac);
+    }
+  __shared__ kt_part sh[KT_BLOCK];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int w = KT_BLOCK/2; w > 0; w >>= 1)
+    { if ((int)threadIdx.x < w)
+        { kt_part &x = sh[threadIdx.x];
+          const kt_part &y = sh[threadIdx.x+w];
+          x.n_distinct += y.n_distinct;
+          x.n_unanimous += y.n_unanimous;
+          for (int l = 0; l < 4; l++) { x.label_total[l] += y.label_total[l]; x.cns_total[l] += y.cns_total[l]; }
+          x.s_lo += y.s_lo;
+          x.s_hi += y.s_hi+(x.s_lo < y.s_lo);
+        }
+      __syncthreads();
+    }
+  if (threadIdx.x == 0) parts[blockIdx.x] = sh[0];
+}
+
+// consensus labels: out[j] = the consensus label of the k-mer ending at j; skipped k-mers keep what out holds
+template <bool CANON>
+__global__ void __launch_bounds__(KT_BLOCK) kt_consensus_kernel(const kt_slot *tab, unsigned long long mask,
+                                                                const char *seq, const int64_t *seq_off, int nreads,
+                                                                int64_t total, int K, char *out, kt_ctl *ctl)
+{ const int64_t p0 = ((int64_t)blockIdx.x*blockDim.x+threadIdx.x)*KT_CHUNK;
+  if (p0 >= total) return;
+  unsigned int err = 0;
+  kt_walk<CANON>(seq,seq_off,nreads,total,K,p0,
+    [&](int64_t j, unsigned long long hi, unsigned long long lo)
+    { const kt_slot *e = kt_lookup(tab,mask,hi,lo);
+      if (!e) { err |= KT_ERR_LABEL; return; }           // a k-mer that was never added: the caller's error
+      out[j] = "EHDR"[kt_consensus(e->cnt)];
+    });
+  if (err) atomicOr(&ctl->err,err);
+}
+
+__global__ void __launch_bounds__(KT_BLOCK) kt_export_kernel(const kt_slot *tab, unsigned long long n, kt_slot *out,
+                                                             unsigned long long cap, kt_ctl *ctl)
+{ for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kt_slot e = tab[s];
+      if (e.lo == KT_EMPTY) continue;
+      const unsigned long long i = atomicAdd(&ctl->n_out,1ull);
+      if (i < cap) out[i] = e;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+
+struct cp_kmer_table
+  { int K, canonical, device;
+    kt_slot *tab;
+    unsigned long long slots;
+    kt_ctl *ctl;                         // device
+    kt_ctl *h_ctl;                       // pinned host copy
+    unsigned int *fail[2];               // failure bitmaps, 1 bit per base position of a batch
+    size_t fail_words;
+    int64_t growths;
+    bool overflowed;                     // sticky: a count passed 2^32-1
+    hipStream_t stream;                  // stream of the last call that queued work
+  };
+
+static int kt_grid(unsigned long long n)
+{ return (int)std::min<unsigned long long>((n+KT_BLOCK-1)/KT_BLOCK,8192); }
+
+static int kt_alloc_table(kt_slot **out, unsigned long long slots, hipStream_t st)
+{ void *p = nullptr;
+  hipError_t e = hipMalloc(&p,(size_t)slots*sizeof(kt_slot));
+  if (e != hipSuccess)
+    { (void)hipGetLastError();
+      char m[160];
+      snprintf(m,sizeof(m),"cp_kmer_table: hipMalloc(%llu slots, %llu bytes): %s",slots,
+               (unsigned long long)(slots*sizeof(kt_slot)),hipGetErrorString(e));
+      return set_err(CP_ENOMEM,m);
+    }
+  kt_fill_kernel<<<kt_grid(slots),KT_BLOCK,0,st>>>((kt_slot *)p,slots);
+  *out = (kt_slot *)p;
+  return CP_OK;
+}
+
+static int kt_sync_ctl(cp_kmer_table *t, hipStream_t st)
+{ HIPCHK(hipMemcpyAsync(t->h_ctl,t->ctl,sizeof(kt_ctl),hipMemcpyDeviceToHost,st));
+  HIPCHK(hipStreamSynchronize(st));
+  return CP_OK;
+}
+
+// rehash into a table of at least `want` slots (a power of two, > slots); the old table stays intact on failure
+static int kt_grow(cp_kmer_table *t, unsigned long long want, hipStream_t st)
+{ for (int attempt = 0; attempt < 4; attempt++, want <<= 1)
+    { kt_slot *nt = nullptr;
+      int rc = kt_alloc_table(&nt,want,st);
+      if (rc != CP_OK) return rc;
+      HIPCHK(hipMemsetAsync(&t->ctl->n_rfail,0,sizeof(unsigned long long),st));
+      kt_rehash_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,nt,want-1,t->ctl);
+      HIPCHK(hipGetLastError());
+      rc = kt_sync_ctl(t,st);
+      if (rc != CP_OK) { (void)hipFree(nt); return rc; }
+      if (t->h_ctl->n_rfail == 0)
+        { HIPCHK(hipFree(t->tab));
+          t->tab = nt;
+          t->slots = want;
+          t->growths++;
+          return CP_OK;
+        }
+      HIPCHK(hipFree(nt));                                 // a probe run too long in the new table: larger still
+    }
+  return set_err(CP_ENOMEM,"cp_kmer_table: rehash kept failing its probe bound");
+}
+
+static unsigned long long kt_pow2_at_least(unsigned long long n)
+{ unsigned long long s = 64;
+  while (s < n) s <<= 1;
+  return s;
+}
+
+extern "C" int cp_kmer_table_create(int K, int canonical, int64_t initial_slots, cp_kmer_table **out)
+{ if (!out) return set_err(CP_EINVAL,"cp_kmer_table_create: null out");
+  *out = nullptr;
+  if (K < 2 || K > 63)
+    return set_err(CP_EINVAL,"cp_kmer_table_create: K must lie in [2, 63] (a key holds 2K <= 126 bits)");
+  if (initial_slots < 0 || initial_slots > ((int64_t)1 << 40))
+    return set_err(CP_EINVAL,"cp_kmer_table_create: bad initial_slots");
+  cp_kmer_table *t = new (std::nothrow) cp_kmer_table();
+  if (!t) return set_err(CP_ENOMEM,"cp_kmer_table_create: out of memory");
+  t->K = K; t->canonical = canonical ? 1 : 0;
+  t->slots = kt_pow2_at_least(initial_slots > 0 ? (unsigned long long)initial_slots : (1ull << 20));
+  hipError_t e = hipGetDevice(&t->device);
+  if (e == hipSuccess) e = hipMalloc(&t->ctl,sizeof(kt_ctl));
+  if (e == hipSuccess) e = hipHostMalloc(&t->h_ctl,sizeof(kt_ctl),hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemset(t->ctl,0,sizeof(kt_ctl));
+  int rc = CP_OK;
+  if (e == hipSuccess)
+    { rc = kt_alloc_table(&t->tab,t->slots,nullptr);
+      if (rc == CP_OK) e = hipStreamSynchronize(nullptr);
+    }
+  if (e != hipSuccess || rc != CP_OK)
+    { if (e != hipSuccess) rc = set_err(CP_EHIP,std::string("cp_kmer_table_create: ")+hipGetErrorString(e));
+      cp_kmer_table_destroy(t);
+      return rc;
+    }
+  *out = t;
+  return CP_OK;
+}
+
+extern "C" void cp_kmer_table_destroy(cp_kmer_table *t)
+{ if (!t) return;
+  (void)hipDeviceSynchronize();
+  if (t->tab) (void)hipFree(t->tab);
+  if (t->ctl) (void)hipFree(t->ctl);
+  if (t->h_ctl) (void)hipHostFree(t->h_ctl);
+  for (int i = 0; i < 2; i++)
+    if (t->fail[i]) (void)hipFree(t->fail[i]);
+  delete t;
+}
+
+extern "C" int cp_kmer_table_add(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, const char *d_labels,
+                                 int nreads, int64_t total_bases, void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_table_add: bad argument");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off || !d_labels) return set_err(CP_EINVAL,"cp_kmer_table_add: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  t->stream = st;
+  const size_t words = (size_t)((total_bases+31)/32);
+  if (words > t->fail_words)
+    { HIPCHK(hipStreamSynchronize(st));
+      for (int i = 0; i < 2; i++)
+        { if (t->fail[i]) { (void)hipFree(t->fail[i]); t->fail[i] = nullptr; }
+          if (hipMalloc(&t->fail[i],words*4) != hipSuccess)
+            { (void)hipGetLastError();
+              t->fail_words = 0;
+              return set_err(CP_ENOMEM,"cp_kmer_table_add: cannot allocate the failure bitmap");
+            }
+        }
+      t->fail_words = words;
+    }
+  const int grid = (int)((total_bases+(int64_t)KT_BLOCK*KT_CHUNK-1)/((int64_t)KT_BLOCK*KT_CHUNK));
+  HIPCHK(hipMemsetAsync(t->fail[0],0,words*4,st));
+  HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
+  if (t->canonical)
+    kt_add_kernel<true,false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,t->K,
+                                                      nullptr,t->fail[0],t->ctl);
+  else
+    kt_add_kernel<false,false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,t->K,
+                                                       nullptr,t->fail[0],t->ctl);
+  HIPCHK(hipGetLastError());
+  // the one read-back: failed inserts and occupancy.  Failures: grow, replay only them; then keep the load <= 1/2.
+  for (int round = 0; ; round++)
+    { int rc = kt_sync_ctl(t,st);
+      if (rc != CP_OK) return rc;
+      const unsigned long long nfail = t->h_ctl->n_fail, nocc = t->h_ctl->n_occ;
+      if (nfail == 0 && 2*nocc <= t->slots) return CP_OK;
+      if (round >= 16) return set_err(CP_ENOMEM,"cp_kmer_table_add: the table did not settle after 16 growth steps");
+      rc = kt_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+nfail))),st);
+      if (rc != CP_OK) return rc;
+      if (nfail == 0) continue;
+      HIPCHK(hipMemsetAsync(t->fail[1],0,words*4,st));
+      HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
+      if (t->canonical)
+        kt_add_kernel<true,true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,
+                                                         t->K,t->fail[0],t->fail[1],t->ctl);
+      else
+        kt_add_kernel<false,true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,
+                                                          t->K,t->fail[0],t->fail[1],t->ctl);
+      HIPCHK(hipGetLastError());
+      std::swap(t->fail[0],t->fail[1]);
+    }
+}
+
+// n_distinct * 2^64 / S, correctly rounded (S >= n_distinct * 2^64 > 0): 64 significant quotient bits by restoring
+// division, then round half to even on the dropped bits and the remainder
+static double kt_ratio(unsigned long long n, unsigned long long s_hi, unsigned long long s_lo)
+{ const kt_u128 S = ((kt_u128)s_hi << 64) | s_lo;
+  kt_u128 r = (kt_u128)n << 64;
+  unsigned long long m = 0;
+  int e = 0, nbits = 0;
+  // the quotient lies in [1/4, 1]: its leading bit is at 2^0, 2^-1 or 2^-2
+  if (r >= S) { m = 1; r -= S; nbits = 1; }
+  while (nbits < 64)
+    { r <<= 1;
+      e--;
+      const unsigned long long bit = r >= S;
+      if (bit) r -= S;
+      if (nbits > 0 || bit) { m = (m << 1) | bit; nbits++; }
+    }
+  // value = m * 2^e, m has 64 significant bits; keep 53
+  const unsigned long long drop = m & 0x7ff;
+  m >>= 11;
+  e += 11;
+  if (drop > 0x400 || (drop == 0x400 && (r != 0 || (m & 1)))) m++;
+  if (m == (1ull << 53)) { m >>= 1; e++; }
+  return ldexp((double)m,e);
+}
+
+extern "C" int cp_kmer_table_stats(cp_kmer_table *t, cp_kmer_stats *out)
+{ if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_table_stats: bad argument");
+  hipStream_t st = t->stream;
+  const int grid = kt_grid(t->slots);
+  std::vector<kt_part> parts((size_t)grid);
+  kt_part *d_parts = nullptr;
+  HIPCHK(hipMalloc(&d_parts,sizeof(kt_part)*grid));
+  kt_stats_kernel<<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots,d_parts);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(parts.data(),d_parts,sizeof(kt_part)*grid,hipMemcpyDeviceToHost,st);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->h_ctl,t->ctl,sizeof(kt_ctl),hipMemcpyDeviceToHost,st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_parts);
+  if (e != hipSuccess) return set_err(CP_EHIP,std::string("cp_kmer_table_stats: ")+hipGetErrorString(e));
+  const unsigned int err = t->h_ctl->err;
+  if (err)                                                  // deferred device errors: reported once, then cleared
+    { HIPCHK(hipMemsetAsync(&t->ctl->err,0,sizeof(unsigned int),st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+  if (err & KT_ERR_OVERFLOW) t->overflowed = true;
+  if (t->overflowed)
+    return set_err(CP_EOVERFLOW,"cp_kmer_table: a k-mer's count of one label passed 2^32-1; the table is no longer exact");
+  if (err & KT_ERR_LABEL)
+    return set_err(CP_EINVAL,"cp_kmer_table: a counted k-mer position held a label other than E/H/D/R, or a consensus "
+                             "pass met a k-mer that was never added");
+  kt_part a = {};
+  for (const kt_part &p : parts)
+    { a.n_distinct += p.n_distinct;
+      a.n_unanimous += p.n_unanimous;
+      for (int l = 0; l < 4; l++) { a.label_total[l] += p.label_total[l]; a.cns_total[l] += p.cns_total[l]; }
+      a.s_lo += p.s_lo;
+      a.s_hi += p.s_hi+(a.s_lo < p.s_lo);
+    }
+  memset(out,0,sizeof(*out));
+  out->n_skipped = (int64_t)t->h_ctl->n_skip;
+  out->n_distinct = (int64_t)a.n_distinct;
+  out->n_unanimous = (int64_t)a.n_unanimous;
+  for (int l = 0; l < 4; l++)
+    { out->label_total[l] = (int64_t)a.label_total[l];
+      out->cns_total[l] = (int64_t)a.cns_total[l];
+      out->n_kmers += out->label_total[l];
+    }
+  out->s_fixed_hi = a.s_hi;
+  out->s_fixed_lo = a.s_lo;
+  out->consistency = a.n_distinct ? kt_ratio(a.n_distinct,a.s_hi,a.s_lo) : NAN;
+  out->slots = (int64_t)t->slots;
+  out->bytes = (int64_t)(t->slots*sizeof(kt_slot)+2*t->fail_words*4);
+  out->growths = t->growths;
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_table_consensus(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                                       int64_t total_bases, char *d_labels, void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_table_consensus: bad argument");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off || !d_labels) return set_err(CP_EINVAL,"cp_kmer_table_consensus: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  t->stream = st;
+  const int grid = (int)((total_bases+(int64_t)KT_BLOCK*KT_CHUNK-1)/((int64_t)KT_BLOCK*KT_CHUNK));
+  if (t->canonical)
+    kt_consensus_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,
+                                                      d_labels,t->ctl);
+  else
+    kt_consensus_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,
+                                                       d_labels,t->ctl);
+  HIPCHK(hipGetLastError());
+  return CP_OK;
+}
+
+extern "C" int64_t cp_kmer_table_export(cp_kmer_table *t, uint64_t *hi, uint64_t *lo, uint32_t *counts4,
+                                        int64_t capacity)
+{ if (!t || capacity < 0) return set_err(CP_EINVAL,"cp_kmer_table_export: bad argument");
+  hipStream_t st = t->stream;
+  int rc = kt_sync_ctl(t,st);
+  if (rc != CP_OK) return rc;
+  const unsigned long long n = t->h_ctl->n_occ;
+  if ((unsigned long long)capacity < n || !hi || !lo || !counts4) return (int64_t)n;
+  if (n == 0) return 0;
+  kt_slot *d_out = nullptr;
+  if (hipMalloc(&d_out,(size_t)n*sizeof(kt_slot)) != hipSuccess)
+    { (void)hipGetLastError();
+      return set_err(CP_ENOMEM,"cp_kmer_table_export: cannot allocate the export buffer");
+    }
+  std::vector<kt_slot> h((size_t)n);
+  hipError_t e = hipMemsetAsync(&t->ctl->n_out,0,sizeof(unsigned long long),st);
+  if (e == hipSuccess)
+    { kt_export_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,d_out,n,t->ctl);
+      e = hipGetLastError();
+    }
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(),d_out,(size_t)n*sizeof(kt_slot),hipMemcpyDeviceToHost,st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_out);
+  if (e != hipSuccess) return set_err(CP_EHIP,std::string("cp_kmer_table_export: ")+hipGetErrorString(e));
+  std::sort(h.begin(),h.end(),[](const kt_slot &a, const kt_slot &b)
+            { return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo; });
+  for (size_t i = 0; i < (size_t)n; i++)
+    { hi[i] = h[i].hi;
+      lo[i] = h[i].lo;
+      for (int l = 0; l < 4; l++) counts4[4*i+l] = h[i].cnt[l];
+    }
+  return (int64_t)n;
+}

@@ -251,6 +251,69 @@ int cp_seq_context(const char *d_seq, const int64_t *d_seq_off, int nreads, int6
 int cp_scan_candidates(const cp_params *p, const uint16_t *d_prof, int64_t total_kmers,
                        uint64_t *d_bitmap, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-k-mer label table (class2cns): how often each distinct k-mer got each label across all the reads that hold
+ * it.  Replaces the reference's text pipeline scripts/naive_consensus.sh (src/class2cns.c:62-68, then
+ * `sort | uniq -c`, then scripts/agg2cons.py) with a hashed count on the device.
+ *
+ *   Input        reads and labels in the flat layout above, as cp_classify_batch leaves them: K-1 'N', then one of
+ *                E/H/D/R per k-mer.  Reads shorter than K contribute nothing.
+ *   Occurrences  the k-mer ending at read position i, for i in [K-1, rlen) (class2cns.c:63).
+ *   Skipped      a k-mer holding a base other than upper-case A C G T is not counted, only tallied in n_skipped.
+ *                (Difference from the reference: its text pipeline keeps such a k-mer as a string of its own.)
+ *   Bad label    a label other than E/H/D/R at a counted position is an error, CP_EINVAL, reported by the next
+ *                cp_kmer_table_stats (deferred, as cp_workspace_check does for the classifier).
+ *   Key          2 bits per base, A=0 C=1 G=2 T=3, first base most significant, so numeric key order is LC_ALL=C
+ *                text order.  2 <= K <= 63 (a key holds 2K <= 126 bits); any other K is CP_EINVAL.  Exported as
+ *                hi = key bits 125..63, lo = key bits 62..0.
+ *   Forward      (canonical = 0) the key is the k-mer as read: the reference pipeline's semantics.
+ *   Canonical    (canonical = 1) the key is min(forward, reverse complement): a k-mer and its reverse complement
+ *                share one entry (as FASTK counts k-mers).
+ *   Counts       four exact u32 per distinct key, in label order E, H, D, R.  A count that would pass 2^32-1 makes
+ *                every later cp_kmer_table_stats return CP_EOVERFLOW: a wrapped count is never reported.
+ *   Consensus    the label with the largest count; a tie goes to the label of larger copy number, R > D > H > E
+ *                (a project choice: the reference defines none).
+ *   Consistency  n_distinct / S with S = sum over distinct keys of total/max (each term in [1, 4]): the harmonic
+ *                mean of agg2cons.py's most-common fraction mcf = max/total.  Each term is accumulated as
+ *                floor(total * 2^64 / max) in 128-bit fixed point (s_fixed_hi:s_fixed_lo) and `consistency` is the
+ *                correctly rounded double of n_distinct * 2^64 / S_fixed, so it is the same bit for bit whatever the
+ *                batching, read order or thread schedule (NaN when the table is empty).
+ *
+ * The table sizes itself: inserts that run past the probe bound are replayed after the table grows (rehash into at
+ * least twice the slots), and it also grows when more than half of its slots are occupied.  Nothing is dropped.
+ * initial_slots (0 = default) exists so that tests can force growth.  A growth step that cannot allocate returns
+ * CP_ENOMEM and leaves the table as it was.  One GPU per table.
+ */
+typedef struct cp_kmer_table cp_kmer_table;
+typedef struct
+  { int64_t  n_kmers;              /* counted occurrences (= sum of label_total) */
+    int64_t  n_skipped;            /* occurrences skipped: a base other than upper-case A C G T */
+    int64_t  n_distinct;           /* distinct keys */
+    int64_t  n_unanimous;          /* distinct keys whose occurrences all carry one label (mcf == 1) */
+    int64_t  label_total[4];       /* occurrences per input label, order E, H, D, R */
+    int64_t  cns_total[4];         /* occurrences per consensus label of their key, order E, H, D, R */
+    uint64_t s_fixed_hi, s_fixed_lo;   /* S in 64.64 fixed point (see Consistency) */
+    double   consistency;
+    int64_t  slots, bytes;         /* table slots now; device bytes held (slots of 32 bytes + failure bitmaps) */
+    int64_t  growths;              /* growth steps so far */
+  } cp_kmer_stats;
+int  cp_kmer_table_create(int K, int canonical, int64_t initial_slots, cp_kmer_table **out);
+void cp_kmer_table_destroy(cp_kmer_table *t);
+/* Counts every k-mer occurrence of a labelled batch.  Asynchronous on `stream` except for one read-back of the
+ * failed-insert and occupancy counters (and, when the table grows, the growth itself). */
+int  cp_kmer_table_add(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, const char *d_labels,
+                       int nreads, int64_t total_bases, void *stream);
+/* Synchronises; reports deferred device errors (CP_EINVAL, CP_EOVERFLOW) first. */
+int  cp_kmer_table_stats(cp_kmer_table *t, cp_kmer_stats *out);
+/* Consensus labels in place: d_labels[i] becomes the consensus label of the k-mer ending at i for every counted
+ * position; the K-1 leading positions and skipped k-mers keep what d_labels holds.  A k-mer that is not in the
+ * table is reported as CP_EINVAL by the next cp_kmer_table_stats.  Asynchronous on `stream`. */
+int  cp_kmer_table_consensus(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                             int64_t total_bases, char *d_labels, void *stream);
+/* Occupied entries in key order into host arrays (counts4 holds 4 per entry, order E, H, D, R).  Returns the number of
+ * entries; when capacity is smaller than that (or an array is NULL) nothing is written. */
+int64_t cp_kmer_table_export(cp_kmer_table *t, uint64_t *hi, uint64_t *lo, uint32_t *counts4, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif
