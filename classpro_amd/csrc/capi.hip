@@ -10,6 +10,7 @@
 #include <vector>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <time.h>
 #include "cp_host_setup.h"
 #include "kernels.hip"
@@ -22,6 +23,8 @@ static int set_err(int code, const std::string &msg) { g_err = msg; return code;
        if (e_ != hipSuccess)                                                               \
          return set_err(CP_EHIP,std::string(#call)+": "+hipGetErrorString(e_));            \
      } while (0)
+// the status of the kernel launches issued since the last check
+static int launch_status() { HIPCHK(hipGetLastError()); return CP_OK; }
 
 extern "C" const char *cp_last_error(void) { return g_err.c_str(); }
 extern "C" const char *cp_version(void) { return "classpro_amd 0.1 (gfx950)"; }
@@ -253,8 +256,7 @@ extern "C" int cp_math_eval(int fn, const double *d_x, const double *d_x2, doubl
   if (n == 0) return CP_OK;
   const int64_t blocks = (n+255)/256;
   hipLaunchKernelGGL(k_math_eval,dim3((unsigned)(blocks < 4096 ? blocks : 4096)),dim3(256),0,(hipStream_t)stream,fn,d_x,d_x2,d_y,n);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 extern "C" int cp_params_export(const cp_params *p, int *cov4, double *dr_ratio, int *cmax, double *hc_erate,
@@ -280,11 +282,16 @@ extern "C" int cp_decode_profile(const uint8_t *code, int64_t len, uint16_t *pro
 //  Workspace: device scratch grown on demand (never shrunk), reused across batches.
 // ---------------------------------------------------------------------------------------------
 struct dbuf { void *p; size_t cap; };
+// the one place where a buffer's bytes get a type: the kernel's signature checks the T a launch names
+template <class T> static T *as(const dbuf &b) { return (T *)b.p; }
 
 struct cp_workspace
-  { dbuf bitmap, ncand, nintvl, nrel, ioff, eoff, hoff, wall, wall_s, hkeys, hvals, eintvl, ointvl, intvl, rintvl,
-         rrec, pcls, ivA, ivB, ivC, relmap, parent, eff, rpos, asgn, ord, err, perm, wlist, err2, tres, fwc, dtot,
-         s_cap, s_rcap, s_dummy, s_key, s_seg, s_aux, s_mi, s_rep, s_repcnt, scan_state, order_tmp;
+  { // every device buffer, and nothing but: cp_workspace_destroy and cp_workspace_bytes walk `b` as an array of dbufs
+    struct bufs
+      { dbuf bitmap, ncand, nintvl, nrel, ioff, eoff, hoff, wall, wall_s, hkeys, hvals, eintvl, ointvl, intvl, rintvl,
+             rrec, pcls, ivA, ivB, ivC, relmap, parent, eff, rpos, asgn, ord, err, perm, wlist, err2, tres, fwc, dtot,
+             s_cap, s_rcap, s_dummy, s_key, s_seg, s_aux, s_mi, s_rep, s_repcnt, scan_state, order_tmp;
+      } b;
     int      scan_epoch;      // tag of the next k_prefix_caps_mb launch (its state array is never cleared)
     int64_t *h_totals;        // pinned: [totalI, totalE, totalH]
     unsigned long long *h_tot64, *d_tot64;   // pinned, and its device address: the totals as {value << 24 | launch tag}, written by the kernel itself
@@ -301,6 +308,9 @@ struct cp_workspace
     hipStream_t aux;          // size classes of one stage run side by side: the rare long reads are latency-bound
     hipEvent_t  ev_fork, ev_join;
   };
+static_assert(std::is_trivially_copyable<dbuf>::value && sizeof(cp_workspace::bufs) % sizeof(dbuf) == 0,
+              "cp_workspace::bufs is walked as an array of dbufs");
+static const size_t NBUFS = sizeof(cp_workspace::bufs)/sizeof(dbuf);
 
 // Grow-only.  A buffer that is outgrown may still be read by kernels of the previous call on the workspace's stream (the
 // entry points are asynchronous), and hipFree synchronises the whole device: the old buffer is parked on the
@@ -328,7 +338,16 @@ static int ensure(cp_workspace *ws, dbuf &b, size_t need)
   b.p = np; b.cap = want;
   return CP_OK;
 }
-#define ENSURE(b,n) do { int rc_ = ensure(ws,b,(size_t)(n)); if (rc_ != CP_OK) return rc_; } while (0)
+#define CHK(call)   do { int rc_ = (call); if (rc_ != CP_OK) return rc_; } while (0)
+#define ENSURE(b,n) CHK(ensure(ws,b,(size_t)(n)))
+
+// ensure(), and a buffer that was replaced is zeroed, all of it, on `st`
+static int ensure_zeroed(cp_workspace *ws, dbuf &b, size_t need, hipStream_t st)
+{ const size_t c0 = b.cap;
+  ENSURE(b,need);
+  if (b.cap != c0) HIPCHK(hipMemsetAsync(b.p,0,b.cap,st));
+  return CP_OK;
+}
 
 extern "C" int cp_workspace_create(cp_workspace **out)
 { if (!out) return set_err(CP_EINVAL,"cp_workspace_create: null out");
@@ -342,13 +361,13 @@ extern "C" int cp_workspace_create(cp_workspace **out)
   // the error words (device): [0] find_wall / classification, [1] find_seeds, [2] profile decode.  Sticky: kernels OR
   // into them, only cp_workspace_check reads and clears them, so a flag raised by any call since the last check is seen
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ws->aux,hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&ws->err.p,16);
-  if (e == hipSuccess) { ws->err.cap = 16; e = hipMemsetAsync(ws->err.p,0,16,ws->aux); }
+  if (e == hipSuccess) e = hipMalloc(&ws->b.err.p,16);
+  if (e == hipSuccess) { ws->b.err.cap = 16; e = hipMemsetAsync(ws->b.err.p,0,16,ws->aux); }
   if (e == hipSuccess) e = hipStreamSynchronize(ws->aux);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ws->ev_fork,hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ws->ev_join,hipEventDisableTiming);
   if (e != hipSuccess)
-    { if (ws->err.p) (void)hipFree(ws->err.p);
+    { if (ws->b.err.p) (void)hipFree(ws->b.err.p);
       delete ws->retired;
       free(ws);
       return set_err(CP_EHIP,std::string("cp_workspace_create: ")+hipGetErrorString(e));
@@ -359,11 +378,8 @@ extern "C" int cp_workspace_create(cp_workspace **out)
 
 extern "C" void cp_workspace_destroy(cp_workspace *ws)
 { if (!ws) return;
-  dbuf *all[] = { &ws->bitmap,&ws->ncand,&ws->nintvl,&ws->nrel,&ws->ioff,&ws->eoff,&ws->hoff,&ws->wall,&ws->wall_s,&ws->hkeys,&ws->hvals,
-                  &ws->eintvl,&ws->ointvl,&ws->intvl,&ws->rintvl,&ws->rrec,&ws->pcls,&ws->ivA,&ws->ivB,&ws->ivC,&ws->relmap,&ws->parent,&ws->eff,&ws->rpos,
-                  &ws->asgn,&ws->ord,&ws->err,&ws->perm,&ws->wlist,&ws->err2,&ws->tres,&ws->fwc,&ws->dtot,
-                  &ws->s_cap,&ws->s_rcap,&ws->s_dummy,&ws->s_key,&ws->s_seg,&ws->s_aux,&ws->s_mi,&ws->s_rep,&ws->s_repcnt,&ws->scan_state,&ws->order_tmp };
-  for (dbuf *b : all) if (b->p) (void)hipFree(b->p);
+  dbuf *all = reinterpret_cast<dbuf *>(&ws->b);
+  for (size_t i = 0; i < NBUFS; i++) if (all[i].p) (void)hipFree(all[i].p);
   for (void *q : *ws->retired) (void)hipFree(q);
   delete ws->retired;
   if (ws->aux) (void)hipStreamDestroy(ws->aux);
@@ -377,16 +393,34 @@ extern "C" void cp_workspace_destroy(cp_workspace *ws)
 
 extern "C" size_t cp_workspace_bytes(const cp_workspace *ws)
 { if (!ws) return 0;
-  const dbuf *all[] = { &ws->bitmap,&ws->ncand,&ws->nintvl,&ws->nrel,&ws->ioff,&ws->eoff,&ws->hoff,&ws->wall,&ws->wall_s,&ws->hkeys,&ws->hvals,
-                        &ws->eintvl,&ws->ointvl,&ws->intvl,&ws->rintvl,&ws->rrec,&ws->pcls,&ws->ivA,&ws->ivB,&ws->ivC,&ws->relmap,&ws->parent,&ws->eff,&ws->rpos,
-                        &ws->asgn,&ws->ord,&ws->err,&ws->perm,&ws->wlist,&ws->err2,&ws->tres,&ws->fwc,&ws->dtot,
-                  &ws->s_cap,&ws->s_rcap,&ws->s_dummy,&ws->s_key,&ws->s_seg,&ws->s_aux,&ws->s_mi,&ws->s_rep,&ws->s_repcnt,&ws->scan_state,&ws->order_tmp };
+  const dbuf *all = reinterpret_cast<const dbuf *>(&ws->b);
   size_t s = 0;
-  for (const dbuf *b : all) s += b->cap;
+  for (size_t i = 0; i < NBUFS; i++) s += all[i].cap;
   return s;
 }
 
-// ---------------------------------------------------------------------------------------------
+// The run-time knobs (what each is for: at its use).  Read once per cp_run_stages / cp_scan_candidates call, NOT cached in
+// the workspace or the params as ADVICE.md suggests: the parity tests change them between calls on one live workspace
+// and between classifiers of one process, to run both forms of a stage side by side.
+struct run_knobs
+  { int64_t scan_chunk;    // CLASSPRO_SCAN_CHUNK_KMERS: positions per scan launch, >= 4096 and a multiple of it (default 2^31)
+    bool    fuse_rel;      // CLASSPRO_FUSE_REL: off if 0
+    int     compact;       // CLASSPRO_COMPACT_REL: 0 or 1 as given, anything else or unset 2
+    bool    full_sweep2;   // CLASSPRO_UNREL_SWEEP2: on if "full"
+  };
+
+static run_knobs read_knobs()
+{ run_knobs k;
+  const char *e;
+  const int64_t chunk = (e = getenv("CLASSPRO_SCAN_CHUNK_KMERS")) ? atoll(e) : 0;
+  k.scan_chunk = chunk >= 4096 ? chunk & ~(int64_t)4095 : (int64_t)1 << 31;
+  k.fuse_rel = !(e = getenv("CLASSPRO_FUSE_REL")) || atol(e) != 0;
+  const long crel = (e = getenv("CLASSPRO_COMPACT_REL")) ? atol(e) : 2;
+  k.compact = (crel == 0 || crel == 1) ? (int)crel : 2;
+  k.full_sweep2 = (e = getenv("CLASSPRO_UNREL_SWEEP2")) && !strcmp(e,"full");
+  return k;
+}
+
 static int scan_grid(int64_t total)
 { int64_t groups = total >> 3;
   int64_t blocks = (groups+256*SCAN_UNROLL-1)/(256*SCAN_UNROLL);
@@ -395,14 +429,12 @@ static int scan_grid(int64_t total)
   return (int)blocks;
 }
 
+// A batch is scanned in launches of at most `chunk` positions, by default 2^31 (4 GB of counts): 8-GB launches run 3-5 %
+// slower per byte (1581-1630 us against 2 x 768-770 us, A/B in one call, round 5).
 static int launch_scan(const cp_dev_params *hostP, const uint16_t *d_prof, int64_t total, uint64_t *d_bitmap,
-                       int64_t nwords, hipStream_t st)
+                       int64_t nwords, int64_t chunk, hipStream_t st)
 { if (((uintptr_t)d_prof) & 15)
     return set_err(CP_EINVAL,"profile buffer must be 16-byte aligned");
-  // A batch is scanned in launches of at most 2^31 positions (4 GB of counts): 8-GB launches run 3-5 % slower per byte
-  // (1581-1630 us against 2 x 768-770 us, A/B in one call, round 5).  CLASSPRO_SCAN_CHUNK_KMERS: another size (tests).
-  int64_t chunk = (int64_t)1 << 31;
-  if (const char *e = getenv("CLASSPRO_SCAN_CHUNK_KMERS")) { const int64_t v = atoll(e); if (v >= 4096) chunk = v & ~(int64_t)4095; }
   uint8_t *bm = (uint8_t *)d_bitmap;
   for (int64_t p0 = 0; p0 < total || p0 == 0; p0 += chunk)
     { const bool last = p0+chunk >= total;
@@ -411,50 +443,250 @@ static int launch_scan(const cp_dev_params *hostP, const uint16_t *d_prof, int64
                          d_prof+p0,n,hostP->cov[CP_REPEAT],bm+(p0 >> 3),last ? nwords*8-(p0 >> 3) : (n >> 3),p0 > 0 ? 1 : 0);
       if (last) break;
     }
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 extern "C" int cp_scan_candidates(const cp_params *p, const uint16_t *d_prof, int64_t total_kmers,
                                   uint64_t *d_bitmap, void *stream)
 { if (!p || !d_prof || !d_bitmap || total_kmers < 0)
     return set_err(CP_EINVAL,"cp_scan_candidates: bad argument");
-  return launch_scan(&p->host,d_prof,total_kmers,d_bitmap,total_kmers/64+1,(hipStream_t)stream);
+  return launch_scan(&p->host,d_prof,total_kmers,d_bitmap,total_kmers/64+1,read_knobs().scan_chunk,(hipStream_t)stream);
 }
 
 // exclusive prefix sums of the three capacity arrays (+ totals), one block per 1024 reads
 static int launch_prefix_caps(cp_workspace *ws, int64_t *a, int64_t *b, int64_t *c, int n, int64_t *totals, hipStream_t st,
                               bool to_host = false)
 { const int tiles = (n+SCAN_TILE-1)/SCAN_TILE;
-  const size_t c0 = ws->scan_state.cap;
-  ENSURE(ws->scan_state,(size_t)tiles*sizeof(cp_scan_state));
   // The launch tag only ever grows (1 .. 2^24-1): a freshly zeroed array (tag 0) is valid for any launch, so growing it
   // does NOT start the count over -- the pinned words the host polls still hold the tags of earlier launches, and a
   // second "launch 1" would match them at once and hand the previous batch's totals to this one.
-  if (ws->scan_state.cap != c0)
-    HIPCHK(hipMemsetAsync(ws->scan_state.p,0,ws->scan_state.cap,st));
+  CHK(ensure_zeroed(ws,ws->b.scan_state,(size_t)tiles*sizeof(cp_scan_state),st));
   if (++ws->scan_epoch > (int)SCAN_TAG_MASK)              // the tags start over: from a cleared array, and with the polled
-    { HIPCHK(hipMemsetAsync(ws->scan_state.p,0,ws->scan_state.cap,st)); ws->scan_epoch = 1; }   // words invalidated below
+    { HIPCHK(hipMemsetAsync(ws->b.scan_state.p,0,ws->b.scan_state.cap,st)); ws->scan_epoch = 1; }   // words invalidated below
   if (to_host)                                            // no earlier launch's totals can pass for this one's
     for (int q = 0; q < 3; q++) __atomic_store_n(&ws->h_tot64[q],0ull,__ATOMIC_RELEASE);
-  hipLaunchKernelGGL(k_prefix_caps_mb,dim3(tiles),dim3(WAVE),0,st,a,b,c,n,totals,(cp_scan_state *)ws->scan_state.p,ws->scan_epoch,
+  hipLaunchKernelGGL(k_prefix_caps_mb,dim3(tiles),dim3(WAVE),0,st,a,b,c,n,totals,as<cp_scan_state>(ws->b.scan_state),ws->scan_epoch,
                      to_host ? ws->d_tot64 : (unsigned long long *)NULL);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 // perm[] = read ids by decreasing key >> shift (kernels.hip: k_order_hist / k_order_scatter)
 static int launch_order_by_work(cp_workspace *ws, const int32_t *key, int n, int shift, int32_t *perm, hipStream_t st,
                                 const int64_t *long_off = nullptr)
-{ const size_t c0 = ws->order_tmp.cap;
-  ENSURE(ws->order_tmp,(size_t)(2*ORDER_BINS+1)*4);
-  if (ws->order_tmp.cap != c0) HIPCHK(hipMemsetAsync(ws->order_tmp.p,0,ws->order_tmp.cap,st));   // zero once: the scatter kernel's last block leaves it zero
+{ CHK(ensure_zeroed(ws,ws->b.order_tmp,(size_t)(2*ORDER_BINS+1)*4,st));   // zero once: the scatter kernel's last block leaves it zero
   const int blocks = (n+ORDER_TILE-1)/ORDER_TILE;
-  int32_t *ghist = (int32_t *)ws->order_tmp.p, *gcur = ghist+ORDER_BINS;
+  int32_t *ghist = as<int32_t>(ws->b.order_tmp), *gcur = ghist+ORDER_BINS;
   hipLaunchKernelGGL(k_order_hist,dim3(blocks),dim3(WAVE),0,st,key,n,shift,ghist,long_off);
   hipLaunchKernelGGL(k_order_scatter,dim3(blocks),dim3(WAVE),0,st,key,n,shift,ghist,gcur,perm,long_off);
-  HIPCHK(hipGetLastError());
+  return launch_status();
+}
+
+// cp_run_stages: one launcher per stage, in the order of the pipeline.  What they share travels in a run_ctx on the
+// caller's stack; every as<T>() sits at its launch, behind the ENSURE of its buffer (which may replace the pointer).
+struct run_ctx
+  { const cp_params *p;
+    const char *d_seq; const int64_t *d_seq_off; const uint16_t *d_prof; const int64_t *d_prof_off; char *d_labels;
+    int nreads; int64_t total_kmers; int last_stage; hipStream_t st;
+    run_knobs knobs;
+    // find_rel_intvl inside k_find_wall (CLASSPRO_FUSE_REL=0: as a kernel of its own, always so when the call stops at
+    // the wall stage: the stage API shows find_wall's records as the reference's find_wall leaves them)
+    bool fuse_rel;
+    // whole-path calls: the reliable intervals go to classify_rel as 24-byte records (kernels.hip: cp_rrec) instead of
+    // 48-byte copies + an index, and only intvl[].asgn comes back (CLASSPRO_COMPACT_REL=0: the copies, as the stage API has them)
+    // ... and the interval records as three arrays (cp_soa; CLASSPRO_COMPACT_REL=1: the 24-byte and 4-byte records only)
+    int compact;                          // 0: off, 1: compact records, 2: and the three arrays (ws->last_compact)
+    int64_t totalI, totalE, totalH;       // wait_totals
+    cp_soa soa; uint32_t *pcls;           // stage_wall: the three arrays if compact == 2, the (end, class) words if compact, or null
+  };
+
+// ---- stage 1: candidate scan + capacities ------------------------------------------------
+static int stage_scan_caps(cp_workspace *ws, run_ctx &c)
+{ const int nreads = c.nreads;
+  ENSURE(ws->b.bitmap,ws->nwords*8);
+  ENSURE(ws->b.ncand,(size_t)nreads*4); ENSURE(ws->b.nintvl,(size_t)nreads*4); ENSURE(ws->b.nrel,(size_t)nreads*4);
+  ENSURE(ws->b.ioff,((size_t)nreads+1)*8); ENSURE(ws->b.eoff,((size_t)nreads+1)*8); ENSURE(ws->b.hoff,((size_t)nreads+1)*8);
+  // The head of a call: scan, candidate counts, prefix sums, then the one host round trip (scratch sizes depend on the
+  // data).  (Tried: the head on a high-priority stream of its own, forked from the caller's -- 143.9 against 146.9
+  // Gbases/s without, 187 against 192 with the kernels of the end of round 3: the other stream's wide kernels are what fills the machine, and pre-empting them costs more than
+  // the head's latency gains.)
+  if (c.last_stage < CP_STAGE_LABELS)                    // (the whole path writes both counts for every read: the zeros are for the
+    { HIPCHK(hipMemsetAsync(ws->b.nintvl.p,0,(size_t)nreads*4,c.st));  //  stage API's read-back after an early stop)
+      HIPCHK(hipMemsetAsync(ws->b.nrel.p,0,(size_t)nreads*4,c.st));
+    }
+  CHK(launch_scan(&c.p->host,c.d_prof,c.total_kmers,as<uint64_t>(ws->b.bitmap),ws->nwords,c.knobs.scan_chunk,c.st));
+  hipLaunchKernelGGL(k_count_caps,dim3(nreads),dim3(WAVE),0,c.st,as<uint64_t>(ws->b.bitmap),c.d_prof_off,nreads,
+                     as<int32_t>(ws->b.ncand),as<int64_t>(ws->b.ioff),as<int64_t>(ws->b.eoff),as<int64_t>(ws->b.hoff));
+  ENSURE(ws->b.dtot,32);
+  return launch_prefix_caps(ws,as<int64_t>(ws->b.ioff),as<int64_t>(ws->b.eoff),as<int64_t>(ws->b.hoff),nreads,as<int64_t>(ws->b.dtot),c.st,true);
+}
+
+// the only host round trip of the pipeline: the last tile of the prefix sums stores the three totals, tagged with the
+// launch's number, into pinned host memory and the host polls for them (every so often it asks the stream whether
+// it died instead)
+static int wait_totals(cp_workspace *ws, run_ctx &c)
+{ const unsigned tag = (unsigned)ws->scan_epoch;           // 1 .. 2^24-1 (launch_prefix_caps)
+  volatile unsigned long long *ht = ws->h_tot64;
+  // Polling costs a host core while it lasts (about the head's 1 ms per call and caller: INTEGRATION.md).  Each turn
+  // is a cpu-relax; the clock is read every 64 turns; the stream is asked whether it died every 100 us; and a wait
+  // that has lasted 2 ms -- the head queued behind other streams' work -- goes on in 20-us sleeps instead of spinning.
+  const auto t0 = std::chrono::steady_clock::now();
+  auto next_query = t0+std::chrono::microseconds(100);
+  bool sleepy = false;
+  for (unsigned spins = 1; ; spins++)
+    { const unsigned long long g0 = __atomic_load_n(&ht[0],__ATOMIC_ACQUIRE), g1 = __atomic_load_n(&ht[1],__ATOMIC_ACQUIRE),
+                               g2 = __atomic_load_n(&ht[2],__ATOMIC_ACQUIRE);
+      if ((g0 & 0xffffffu) == tag && (g1 & 0xffffffu) == tag && (g2 & 0xffffffu) == tag)
+        { ws->h_totals[0] = (int64_t)(g0 >> 24); ws->h_totals[1] = (int64_t)(g1 >> 24); ws->h_totals[2] = (int64_t)(g2 >> 24);
+          break;
+        }
+      if (sleepy) { struct timespec ts = { 0, 20000 }; nanosleep(&ts,NULL); }
+      else __builtin_ia32_pause();
+      if (sleepy || (spins & 63) == 0)
+        { const auto now = std::chrono::steady_clock::now();
+          if (now-t0 > std::chrono::milliseconds(2)) sleepy = true;
+          if (now < next_query) continue;
+          next_query = now+std::chrono::microseconds(sleepy ? 1000 : 100);
+          const hipError_t q = hipStreamQuery(c.st);
+          if (q != hipErrorNotReady)                     // the stream is idle (or failed) and the totals never came
+            { if (q != hipSuccess) return set_err(CP_EHIP,std::string("cp_run_stages: ")+hipGetErrorString(q));
+              HIPCHK(hipMemcpy(&ws->h_totals[0],ws->b.dtot.p,24,hipMemcpyDeviceToHost));
+              break;
+            }
+          (void)hipGetLastError();
+        }
+    }
+  c.totalI = ws->totalI = ws->h_totals[0]; c.totalE = ws->totalE = ws->h_totals[1]; c.totalH = ws->totalH = ws->h_totals[2];
   return CP_OK;
+}
+
+// ---- stage 2: find_wall ----------------------------------------------------------------------
+static int stage_wall(cp_workspace *ws, run_ctx &c)
+{ const int nreads = c.nreads;
+  const int64_t totalI = c.totalI, ncell = c.total_kmers+nreads;
+  // The two flag arrays are all zero between batches: k_find_wall clears, before it ends, the few cells a read's walk
+  // touched (its candidates and the ends of its E-/O-intervals), so only a newly allocated array is filled here --
+  // not 2 x (one byte per k-mer) per batch.
+  CHK(ensure_zeroed(ws,ws->b.wall,(size_t)ncell,c.st));
+  CHK(ensure_zeroed(ws,ws->b.wall_s,(size_t)ncell,c.st));
+  ENSURE(ws->b.hkeys,(size_t)c.totalH*4);
+  ENSURE(ws->b.hvals,(size_t)c.totalH*4*8);
+  ENSURE(ws->b.eintvl,(size_t)c.totalE*sizeof(cp_eintvl)); ENSURE(ws->b.ointvl,(size_t)c.totalE*sizeof(cp_eintvl));
+  ENSURE(ws->b.intvl,(size_t)totalI*sizeof(cp_intvl));
+  ENSURE(ws->b.perm,(size_t)nreads*4);
+  ENSURE(ws->b.wlist,(size_t)totalI*4*4);
+  // longest reads first: key = wall candidates / 4 (bins of 4 up to 4096 candidates)
+  CHK(launch_order_by_work(ws,as<int32_t>(ws->b.ncand),nreads,2,as<int32_t>(ws->b.perm),c.st));
+  ENSURE(ws->b.tres,(size_t)totalI*sizeof(task_res));
+  ENSURE(ws->b.fwc,(size_t)nreads*16);
+  // the walk's read-only part (candidate list, filters, the pure part of every live (candidate, error type) pair), then
+  // the replay and the list phases: two kernels because the first wants registers and the second waves (kernels.hip)
+  hipLaunchKernelGGL(k_wall_tasks,dim3(nreads),dim3(WAVE),0,c.st,
+                     c.p->dev,c.d_seq,c.d_seq_off,c.d_prof,c.d_prof_off,nreads,as<uint64_t>(ws->b.bitmap),as<uint8_t>(ws->b.wall),
+                     as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.perm),as<int32_t>(ws->b.wlist),as<task_res>(ws->b.tres),as<int32_t>(ws->b.fwc));
+  ENSURE(ws->b.rintvl,(size_t)totalI*sizeof(cp_intvl));
+  ENSURE(ws->b.relmap,(size_t)totalI*4);
+  if (c.compact)                                          // (c.pcls and c.soa are null otherwise)
+    { ENSURE(ws->b.rrec,(size_t)totalI*sizeof(cp_rrec)); ENSURE(ws->b.pcls,(size_t)totalI*4);
+      c.pcls = as<uint32_t>(ws->b.pcls);
+    }
+  if (c.compact == 2)
+    { ENSURE(ws->b.ivA,(size_t)totalI*sizeof(cp_ivA)); ENSURE(ws->b.ivB,(size_t)totalI*sizeof(cp_ivB)); ENSURE(ws->b.ivC,(size_t)totalI*sizeof(cp_ivC));
+      c.soa = cp_soa{ as<cp_ivA>(ws->b.ivA), as<cp_ivB>(ws->b.ivB), as<cp_ivC>(ws->b.ivC) };
+    }
+  ws->last_compact = c.compact;
+  hipLaunchKernelGGL(k_find_wall,dim3(nreads),dim3(WAVE),0,c.st,
+                     c.p->dev,c.d_seq,c.d_seq_off,c.d_prof,c.d_prof_off,nreads,
+                     as<uint8_t>(ws->b.wall),as<uint8_t>(ws->b.wall_s),as<int32_t>(ws->b.hkeys),as<double>(ws->b.hvals),as<int64_t>(ws->b.hoff),
+                     as<cp_eintvl>(ws->b.eintvl),as<cp_eintvl>(ws->b.ointvl),as<int64_t>(ws->b.eoff),as<cp_intvl>(ws->b.intvl),as<int64_t>(ws->b.ioff),
+                     as<int32_t>(ws->b.nintvl),as<int32_t>(ws->b.err),as<int32_t>(ws->b.perm),as<int32_t>(ws->b.wlist),as<task_res>(ws->b.tres),as<int32_t>(ws->b.fwc),
+                     as<cp_intvl>(ws->b.rintvl),as<int32_t>(ws->b.relmap),as<int32_t>(ws->b.nrel),c.compact ? 2 : c.fuse_rel ? 1 : 0,
+                     as<cp_rrec>(ws->b.rrec),c.soa);
+  return launch_status();
+}
+
+// ---- stage 3: find_rel_intvl (on the whole-path call: done by k_find_wall on the records it emits) ----------
+static int stage_rel(cp_workspace *ws, run_ctx &c)
+{ if (c.fuse_rel) return CP_OK;
+  hipLaunchKernelGGL(k_find_rel,dim3(c.nreads),dim3(WAVE),0,c.st,
+                     c.p->dev,c.d_seq,c.d_seq_off,c.d_prof,c.d_prof_off,c.nreads,as<cp_intvl>(ws->b.intvl),as<cp_intvl>(ws->b.rintvl),
+                     as<int32_t>(ws->b.relmap),as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.nintvl),as<int32_t>(ws->b.nrel));
+  return launch_status();
+}
+
+// The size classes of one classify stage touch disjoint reads and run side by side: the rare ones on ws->aux, between
+// fork_aux() and join_aux(), the main class on the caller's stream.
+static int fork_aux(cp_workspace *ws, hipStream_t st)
+{ HIPCHK(hipEventRecord(ws->ev_fork,st)); HIPCHK(hipStreamWaitEvent(ws->aux,ws->ev_fork,0)); return CP_OK; }
+static int join_aux(cp_workspace *ws, hipStream_t st)
+{ HIPCHK(hipEventRecord(ws->ev_join,ws->aux)); HIPCHK(hipStreamWaitEvent(st,ws->ev_join,0)); return CP_OK; }
+
+// ---- stage 4: classify_rel -------------------------------------------------------------------
+static int stage_classify_rel(cp_workspace *ws, run_ctx &c)
+{ const int nreads = c.nreads; const int64_t totalI = c.totalI;
+  ENSURE(ws->b.parent,(size_t)totalI*2*4); ENSURE(ws->b.eff,(size_t)totalI*2*4);
+  ENSURE(ws->b.rpos,(size_t)totalI*2); ENSURE(ws->b.asgn,(size_t)totalI*2);
+  // (the fw / bw assignments are only read back through the stage API: the whole-path call leaves the array as it is --
+  //  a 37-MB fill that sat 0.7 ms in the serial path of every 1-Gbase sub-batch)
+  if (c.last_stage < CP_STAGE_LABELS) HIPCHK(hipMemsetAsync(ws->b.asgn.p,0xff,(size_t)totalI*2,c.st));
+  // size classes (kernels.hip: REL_SMALL_*): M <= 128 four reads per wave, up to 1024 one read per wave, larger (or a
+  // read beyond 65535 k-mers): the sequential kernel
+  CHK(launch_order_by_work(ws,as<int32_t>(ws->b.nrel),nreads,0,as<int32_t>(ws->b.perm),c.st,c.d_prof_off));
+  // (the classes touch disjoint reads; the rare classes are a handful of latency-bound waves -- on most batches none at
+  //  all, and the sequential kernel's 1024 scratch-using waves still cost 0.9 ms to start -- so they run beside the main
+  //  class on the auxiliary stream)
+  CHK(fork_aux(ws,c.st));
+  hipLaunchKernelGGL(k_classify_rel,dim3(nreads < 1024 ? nreads : 1024),dim3(WAVE),0,ws->aux,
+                     c.p->dev,c.d_prof_off,nreads,as<cp_intvl>(ws->b.intvl),as<cp_intvl>(ws->b.rintvl),as<int32_t>(ws->b.relmap),
+                     as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.nrel),as<int8_t>(ws->b.parent),as<int32_t>(ws->b.eff),
+                     as<uint8_t>(ws->b.rpos),as<int8_t>(ws->b.asgn),totalI,as<int32_t>(ws->b.perm),c.soa);
+  // one argument list for the group kernel's instantiations: the middle class on ws->aux, the main class on the caller's
+  // stream with (COMPACT = 1) or without the compact records
+  auto grp = [&](auto kernel, dim3 grid, dim3 block, hipStream_t s, const cp_rrec *rrec)
+    { hipLaunchKernelGGL(kernel,grid,block,0,s,
+                         c.p->dev,c.d_prof_off,nreads,as<cp_intvl>(ws->b.intvl),as<cp_intvl>(ws->b.rintvl),as<int32_t>(ws->b.relmap),
+                         as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.nrel),as<int8_t>(ws->b.asgn),totalI,as<int32_t>(ws->b.perm),rrec,c.soa);
+    };
+  grp(k_classify_rel_grp<REL_SMALL_MAXM,1024,1,1,0>,dim3(nreads < 2048 ? nreads : 2048),dim3(WAVE),ws->aux,nullptr);
+  const dim3 grid((nreads+REL_SMALL_G*REL_SMALL_WPB-1)/(REL_SMALL_G*REL_SMALL_WPB)), block(WAVE*REL_SMALL_WPB);
+  if (c.compact) grp(k_classify_rel_grp<0,REL_SMALL_MAXM,REL_SMALL_G,REL_SMALL_WPB,1>,grid,block,c.st,as<cp_rrec>(ws->b.rrec));
+  else           grp(k_classify_rel_grp<0,REL_SMALL_MAXM,REL_SMALL_G,REL_SMALL_WPB,0>,grid,block,c.st,nullptr);
+  CHK(join_aux(ws,c.st));
+  return launch_status();
+}
+
+// ---- stage 5: classify_unrel -------------------------------------------------------------------
+static int stage_classify_unrel(cp_workspace *ws, run_ctx &c)
+{ const int nreads = c.nreads;
+  ENSURE(ws->b.ord,(size_t)c.totalI*4);
+  // size classes (kernels.hip: UNREL_SMALL_*): N <= 256 and up to 1024, two reads per wave each (four speculative update
+  // slots per read), larger: the sequential kernel; the rare classes on the auxiliary stream again
+  CHK(launch_order_by_work(ws,as<int32_t>(ws->b.nintvl),nreads,0,as<int32_t>(ws->b.perm),c.st,c.d_prof_off));
+  CHK(fork_aux(ws,c.st));
+  hipLaunchKernelGGL(k_classify_unrel,dim3(nreads < 1024 ? nreads : 1024),dim3(WAVE),0,ws->aux,
+                     c.p->dev,nreads,as<cp_intvl>(ws->b.intvl),as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.nintvl),
+                     as<int32_t>(ws->b.ord),as<int32_t>(ws->b.perm),c.d_prof_off,c.pcls,c.soa);
+  // One argument list for the group kernel's instantiations.  c.pcls is the (end, class) words on every compact call
+  // and null otherwise: the COMPACT = 1 form (compact == 2) always gets the words, as it did when it named them itself.
+  // The second sweep re-evaluates only the intervals whose inputs changed since the first (kernels.hip);
+  // CLASSPRO_UNREL_SWEEP2=full: every one of them, as the reference does (same classes: tests, A/B)
+  auto grp = [&](auto kernel, dim3 grid, hipStream_t s)
+    { hipLaunchKernelGGL(kernel,grid,dim3(WAVE),0,s,
+                         c.p->dev,nreads,as<cp_intvl>(ws->b.intvl),as<int64_t>(ws->b.ioff),as<int32_t>(ws->b.nintvl),
+                         as<int32_t>(ws->b.perm),c.d_prof_off,c.pcls,c.soa,c.knobs.full_sweep2 ? 1 : 0);
+    };
+  grp(k_classify_unrel_grp<UNREL_SMALL_MAXN,1024,UNREL_BIG_G,0>,dim3((nreads+UNREL_BIG_G-1)/UNREL_BIG_G < 2048 ? (nreads+UNREL_BIG_G-1)/UNREL_BIG_G : 2048),ws->aux);
+  if (c.compact == 2) grp(k_classify_unrel_grp<0,UNREL_SMALL_MAXN,UNREL_SMALL_G,1>,dim3((nreads+UNREL_SMALL_G-1)/UNREL_SMALL_G),c.st);
+  else                grp(k_classify_unrel_grp<0,UNREL_SMALL_MAXN,UNREL_SMALL_G,0>,dim3((nreads+UNREL_SMALL_G-1)/UNREL_SMALL_G),c.st);
+  CHK(join_aux(ws,c.st));
+  return launch_status();
+}
+
+// ---- stage 6: labels ---------------------------------------------------------------------------
+static int stage_labels(cp_workspace *ws, run_ctx &c)
+{ hipLaunchKernelGGL(k_paint_labels,dim3(c.nreads),dim3(WAVE),0,c.st,
+                     c.p->dev,c.d_seq_off,c.nreads,as<cp_intvl>(ws->b.intvl),as<int64_t>(ws->b.ioff),
+                     as<int32_t>(ws->b.nintvl),c.d_labels,c.pcls);
+  return launch_status();
 }
 
 extern "C" int cp_run_stages(const cp_params *p, cp_workspace *ws,
@@ -478,224 +710,17 @@ extern "C" int cp_run_stages(const cp_params *p, cp_workspace *ws,
   ws->nreads = nreads; ws->total_kmers = total_kmers; ws->total_bases = total_bases;
   ws->totalI = ws->totalE = 0; ws->last_stage = last_stage; ws->stream = st; ws->last_compact = 0;
   ws->nwords = total_kmers/64+2;
-  if (nreads == 0)
-    return CP_OK;
-
-  // ---- stage 1: candidate scan + capacities ------------------------------------------------
-  ENSURE(ws->bitmap,ws->nwords*8);
-  ENSURE(ws->ncand,(size_t)nreads*4);
-  ENSURE(ws->nintvl,(size_t)nreads*4);
-  ENSURE(ws->nrel,(size_t)nreads*4);
-  ENSURE(ws->ioff,((size_t)nreads+1)*8);
-  ENSURE(ws->eoff,((size_t)nreads+1)*8);
-  ENSURE(ws->hoff,((size_t)nreads+1)*8);
-  // The head of a call: scan, candidate counts, prefix sums, then the one host round trip (scratch sizes depend on the
-  // data).  (Tried: the head on a high-priority stream of its own, forked from the caller's -- 143.9 against 146.9
-  // Gbases/s without, 187 against 192 with the kernels of the end of round 3: the other stream's wide kernels are what fills the machine, and pre-empting them costs more than
-  // the head's latency gains.)
-  hipStream_t hs = st;
-  if (last_stage < CP_STAGE_LABELS)                      // (the whole path writes both counts for every read: the zeros are for the
-    { HIPCHK(hipMemsetAsync(ws->nintvl.p,0,(size_t)nreads*4,hs));      //  stage API's read-back after an early stop)
-      HIPCHK(hipMemsetAsync(ws->nrel.p,0,(size_t)nreads*4,hs));
-    }
-  int rc = launch_scan(&p->host,d_prof,total_kmers,(uint64_t *)ws->bitmap.p,ws->nwords,hs);
-  if (rc != CP_OK) return rc;
-  hipLaunchKernelGGL(k_count_caps,dim3(nreads),dim3(WAVE),0,hs,
-                     (const uint64_t *)ws->bitmap.p,d_prof_off,nreads,
-                     (int32_t *)ws->ncand.p,(int64_t *)ws->ioff.p,(int64_t *)ws->eoff.p,(int64_t *)ws->hoff.p);
-  ENSURE(ws->dtot,32);
-  rc = launch_prefix_caps(ws,(int64_t *)ws->ioff.p,(int64_t *)ws->eoff.p,(int64_t *)ws->hoff.p,nreads,(int64_t *)ws->dtot.p,hs,true);
-  if (rc != CP_OK) return rc;
-  if (last_stage == CP_STAGE_SCAN)
-    return CP_OK;
-
-  // the only host round trip of the pipeline: the last tile of the prefix sums stores the three totals, tagged with the
-  // launch's number, into pinned host memory and the host polls for them (every so often it asks the stream whether
-  // it died instead)
-  { const unsigned tag = (unsigned)ws->scan_epoch;         // 1 .. 2^24-1 (launch_prefix_caps)
-    volatile unsigned long long *ht = ws->h_tot64;
-    // Polling costs a host core while it lasts (about the head's 1 ms per call and caller: INTEGRATION.md).  Each turn
-    // is a cpu-relax; the clock is read every 64 turns; the stream is asked whether it died every 100 us; and a wait
-    // that has lasted 2 ms -- the head queued behind other streams' work -- goes on in 20-us sleeps instead of spinning.
-    const auto t0 = std::chrono::steady_clock::now();
-    auto next_query = t0+std::chrono::microseconds(100);
-    bool sleepy = false;
-    for (unsigned spins = 1; ; spins++)
-      { const unsigned long long g0 = __atomic_load_n(&ht[0],__ATOMIC_ACQUIRE), g1 = __atomic_load_n(&ht[1],__ATOMIC_ACQUIRE),
-                                 g2 = __atomic_load_n(&ht[2],__ATOMIC_ACQUIRE);
-        if ((g0 & 0xffffffu) == tag && (g1 & 0xffffffu) == tag && (g2 & 0xffffffu) == tag)
-          { ws->h_totals[0] = (int64_t)(g0 >> 24); ws->h_totals[1] = (int64_t)(g1 >> 24); ws->h_totals[2] = (int64_t)(g2 >> 24);
-            break;
-          }
-        if (sleepy) { struct timespec ts = { 0, 20000 }; nanosleep(&ts,NULL); }
-        else __builtin_ia32_pause();
-        if (sleepy || (spins & 63) == 0)
-          { const auto now = std::chrono::steady_clock::now();
-            if (now-t0 > std::chrono::milliseconds(2)) sleepy = true;
-            if (now < next_query) continue;
-            next_query = now+std::chrono::microseconds(sleepy ? 1000 : 100);
-            const hipError_t q = hipStreamQuery(hs);
-            if (q != hipErrorNotReady)                   // the stream is idle (or failed) and the totals never came
-              { if (q != hipSuccess) return set_err(CP_EHIP,std::string("cp_run_stages: ")+hipGetErrorString(q));
-                HIPCHK(hipMemcpy(&ws->h_totals[0],ws->dtot.p,24,hipMemcpyDeviceToHost));
-                break;
-              }
-            (void)hipGetLastError();
-          }
-      }
-  }
-  const int64_t totalI = ws->h_totals[0], totalE = ws->h_totals[1], totalH = ws->h_totals[2];
-  ws->totalI = totalI; ws->totalE = totalE; ws->totalH = totalH;
-
-  // ---- stage 2: find_wall ----------------------------------------------------------------------
-  const int64_t ncell = total_kmers+nreads;
-  // The two flag arrays are all zero between batches: k_find_wall clears, before it ends, the few cells a read's walk
-  // touched (its candidates and the ends of its E-/O-intervals), so only a newly allocated array is filled here --
-  // not 2 x (one byte per k-mer) per batch.
-  { const size_t c0 = ws->wall.cap, c1 = ws->wall_s.cap;
-    ENSURE(ws->wall,ncell);
-    ENSURE(ws->wall_s,ncell);
-    if (ws->wall.cap != c0)   HIPCHK(hipMemsetAsync(ws->wall.p,0,ws->wall.cap,st));
-    if (ws->wall_s.cap != c1) HIPCHK(hipMemsetAsync(ws->wall_s.p,0,ws->wall_s.cap,st));
-  }
-  ENSURE(ws->hkeys,(size_t)totalH*4);
-  ENSURE(ws->hvals,(size_t)totalH*4*8);
-  ENSURE(ws->eintvl,(size_t)totalE*sizeof(cp_eintvl));
-  ENSURE(ws->ointvl,(size_t)totalE*sizeof(cp_eintvl));
-  ENSURE(ws->intvl,(size_t)totalI*sizeof(cp_intvl));
-  ENSURE(ws->perm,(size_t)nreads*4);
-  ENSURE(ws->wlist,(size_t)totalI*4*4);
-  // longest reads first: key = wall candidates / 4 (bins of 4 up to 4096 candidates)
-  rc = launch_order_by_work(ws,(const int32_t *)ws->ncand.p,nreads,2,(int32_t *)ws->perm.p,st);
-  if (rc != CP_OK) return rc;
-  ENSURE(ws->tres,(size_t)totalI*sizeof(task_res));
-  ENSURE(ws->fwc,(size_t)nreads*16);
-  // the walk's read-only part (candidate list, filters, the pure part of every live (candidate, error type) pair), then
-  // the replay and the list phases: two kernels because the first wants registers and the second waves (kernels.hip)
-  hipLaunchKernelGGL(k_wall_tasks,dim3(nreads),dim3(WAVE),0,st,
-                     p->dev,d_seq,d_seq_off,d_prof,d_prof_off,nreads,(const uint64_t *)ws->bitmap.p,(uint8_t *)ws->wall.p,
-                     (const int64_t *)ws->ioff.p,(const int32_t *)ws->perm.p,(int32_t *)ws->wlist.p,(task_res *)ws->tres.p,
-                     (int32_t *)ws->fwc.p);
-  // find_rel_intvl inside k_find_wall (CLASSPRO_FUSE_REL=0: as a kernel of its own, always so when the call stops at
-  // the wall stage: the stage API shows find_wall's records as the reference's find_wall leaves them)
-  const char *fuse_e = getenv("CLASSPRO_FUSE_REL");       // (read per call: the parity test runs both forms in one process)
-  const bool fuse_rel = (!fuse_e || atol(fuse_e) != 0) && last_stage >= CP_STAGE_REL;
-  ENSURE(ws->rintvl,(size_t)totalI*sizeof(cp_intvl));
-  ENSURE(ws->relmap,(size_t)totalI*4);
-  // whole-path calls: the reliable intervals go to classify_rel as 24-byte records (kernels.hip: cp_rrec) instead of
-  // 48-byte copies + an index, and only intvl[].asgn comes back (CLASSPRO_COMPACT_REL=0: the copies, as the stage API has them)
-  const char *crel_e = getenv("CLASSPRO_COMPACT_REL");
-  const bool compact_rel = fuse_rel && last_stage == CP_STAGE_LABELS && (!crel_e || atol(crel_e) != 0);
-  // ... and the interval records as three arrays (cp_soa; CLASSPRO_COMPACT_REL=1: the 24-byte and 4-byte records only)
-  const bool soa_on = compact_rel && (!crel_e || atol(crel_e) != 1);
-  if (compact_rel) { ENSURE(ws->rrec,(size_t)totalI*sizeof(cp_rrec)); ENSURE(ws->pcls,(size_t)totalI*4); }
-  if (soa_on) { ENSURE(ws->ivA,(size_t)totalI*sizeof(cp_ivA)); ENSURE(ws->ivB,(size_t)totalI*sizeof(cp_ivB)); ENSURE(ws->ivC,(size_t)totalI*sizeof(cp_ivC)); }
-  cp_soa soa; soa.a = soa_on ? (cp_ivA *)ws->ivA.p : nullptr; soa.b = soa_on ? (cp_ivB *)ws->ivB.p : nullptr; soa.c = soa_on ? (cp_ivC *)ws->ivC.p : nullptr;
-  ws->last_compact = compact_rel ? (soa_on ? 2 : 1) : 0;
-  hipLaunchKernelGGL(k_find_wall,dim3(nreads),dim3(WAVE),0,st,
-                     p->dev,d_seq,d_seq_off,d_prof,d_prof_off,nreads,
-                     (uint8_t *)ws->wall.p,(uint8_t *)ws->wall_s.p,(int32_t *)ws->hkeys.p,(double *)ws->hvals.p,(const int64_t *)ws->hoff.p,
-                     (cp_eintvl *)ws->eintvl.p,(cp_eintvl *)ws->ointvl.p,
-                     (const int64_t *)ws->eoff.p,(cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,
-                     (int32_t *)ws->nintvl.p,(int32_t *)ws->err.p,(const int32_t *)ws->perm.p,(int32_t *)ws->wlist.p,
-                     (const task_res *)ws->tres.p,(const int32_t *)ws->fwc.p,
-                     (cp_intvl *)ws->rintvl.p,(int32_t *)ws->relmap.p,(int32_t *)ws->nrel.p,compact_rel ? 2 : fuse_rel ? 1 : 0,
-                     (cp_rrec *)ws->rrec.p,soa);
-  HIPCHK(hipGetLastError());
-  if (last_stage == CP_STAGE_WALL)
-    return CP_OK;
-
-  // ---- stage 3: find_rel_intvl (on the whole-path call: done by k_find_wall on the records it emits) ----------
-  if (!fuse_rel)
-    { hipLaunchKernelGGL(k_find_rel,dim3(nreads),dim3(WAVE),0,st,
-                         p->dev,d_seq,d_seq_off,d_prof,d_prof_off,nreads,(cp_intvl *)ws->intvl.p,(cp_intvl *)ws->rintvl.p,
-                         (int32_t *)ws->relmap.p,(const int64_t *)ws->ioff.p,(const int32_t *)ws->nintvl.p,(int32_t *)ws->nrel.p);
-      HIPCHK(hipGetLastError());
-    }
-  if (last_stage == CP_STAGE_REL)
-    return CP_OK;
-
-  // ---- stage 4: classify_rel -------------------------------------------------------------------
-  ENSURE(ws->parent,(size_t)totalI*2*4);
-  ENSURE(ws->eff,(size_t)totalI*2*4);
-  ENSURE(ws->rpos,(size_t)totalI*2);
-  ENSURE(ws->asgn,(size_t)totalI*2);
-  // (the fw / bw assignments are only read back through the stage API: the whole-path call leaves the array as it is --
-  //  a 37-MB fill that sat 0.7 ms in the serial path of every 1-Gbase sub-batch)
-  if (last_stage < CP_STAGE_LABELS) HIPCHK(hipMemsetAsync(ws->asgn.p,0xff,(size_t)totalI*2,st));
-  // size classes (kernels.hip: REL_SMALL_*): M <= 128 four reads per wave, up to 1024 one read per wave, larger (or a
-  // read beyond 65535 k-mers): the sequential kernel
-  rc = launch_order_by_work(ws,(const int32_t *)ws->nrel.p,nreads,0,(int32_t *)ws->perm.p,st,d_prof_off);
-  if (rc != CP_OK) return rc;
-  // (the classes touch disjoint reads; the rare classes are a handful of latency-bound waves -- on most batches none at
-  //  all, and the sequential kernel's 1024 scratch-using waves still cost 0.9 ms to start -- so they run beside the main
-  //  class on the auxiliary stream)
-  HIPCHK(hipEventRecord(ws->ev_fork,st));
-  HIPCHK(hipStreamWaitEvent(ws->aux,ws->ev_fork,0));
-  hipLaunchKernelGGL(k_classify_rel,dim3(nreads < 1024 ? nreads : 1024),dim3(WAVE),0,ws->aux,
-                     p->dev,d_prof_off,nreads,(cp_intvl *)ws->intvl.p,(cp_intvl *)ws->rintvl.p,(const int32_t *)ws->relmap.p,
-                     (const int64_t *)ws->ioff.p,(const int32_t *)ws->nrel.p,(int8_t *)ws->parent.p,(int32_t *)ws->eff.p,
-                     (uint8_t *)ws->rpos.p,(int8_t *)ws->asgn.p,totalI,(const int32_t *)ws->perm.p,soa);
-  hipLaunchKernelGGL((k_classify_rel_grp<REL_SMALL_MAXM,1024,1,1,0>),dim3(nreads < 2048 ? nreads : 2048),dim3(WAVE),0,ws->aux,
-                     p->dev,d_prof_off,nreads,(cp_intvl *)ws->intvl.p,(cp_intvl *)ws->rintvl.p,(const int32_t *)ws->relmap.p,
-                     (const int64_t *)ws->ioff.p,(const int32_t *)ws->nrel.p,(int8_t *)ws->asgn.p,totalI,(const int32_t *)ws->perm.p,
-                     (const cp_rrec *)nullptr,soa);
-  HIPCHK(hipEventRecord(ws->ev_join,ws->aux));
-  if (compact_rel)
-    hipLaunchKernelGGL((k_classify_rel_grp<0,REL_SMALL_MAXM,REL_SMALL_G,REL_SMALL_WPB,1>),
-                       dim3((nreads+REL_SMALL_G*REL_SMALL_WPB-1)/(REL_SMALL_G*REL_SMALL_WPB)),dim3(WAVE*REL_SMALL_WPB),0,st,
-                       p->dev,d_prof_off,nreads,(cp_intvl *)ws->intvl.p,(cp_intvl *)ws->rintvl.p,(const int32_t *)ws->relmap.p,
-                       (const int64_t *)ws->ioff.p,(const int32_t *)ws->nrel.p,(int8_t *)ws->asgn.p,totalI,(const int32_t *)ws->perm.p,
-                       (const cp_rrec *)ws->rrec.p,soa);
-  else
-    hipLaunchKernelGGL((k_classify_rel_grp<0,REL_SMALL_MAXM,REL_SMALL_G,REL_SMALL_WPB,0>),
-                       dim3((nreads+REL_SMALL_G*REL_SMALL_WPB-1)/(REL_SMALL_G*REL_SMALL_WPB)),dim3(WAVE*REL_SMALL_WPB),0,st,
-                       p->dev,d_prof_off,nreads,(cp_intvl *)ws->intvl.p,(cp_intvl *)ws->rintvl.p,(const int32_t *)ws->relmap.p,
-                       (const int64_t *)ws->ioff.p,(const int32_t *)ws->nrel.p,(int8_t *)ws->asgn.p,totalI,(const int32_t *)ws->perm.p,
-                       (const cp_rrec *)nullptr,soa);
-  HIPCHK(hipStreamWaitEvent(st,ws->ev_join,0));
-  HIPCHK(hipGetLastError());
-  if (last_stage == CP_STAGE_CLASS_REL)
-    return CP_OK;
-
-  // ---- stage 5: classify_unrel -------------------------------------------------------------------
-  ENSURE(ws->ord,(size_t)totalI*4);
-  // size classes (kernels.hip: UNREL_SMALL_*): N <= 256 and up to 1024, two reads per wave each (four speculative update
-  // slots per read), larger: the sequential kernel; the rare classes on the auxiliary stream again
-  rc = launch_order_by_work(ws,(const int32_t *)ws->nintvl.p,nreads,0,(int32_t *)ws->perm.p,st,d_prof_off);
-  if (rc != CP_OK) return rc;
-  // the second sweep re-evaluates only the intervals whose inputs changed since the first (kernels.hip);
-  // CLASSPRO_UNREL_SWEEP2=full: every one of them, as the reference does (same classes: tests, A/B)
-  const char *sw2_e = getenv("CLASSPRO_UNREL_SWEEP2");
-  const int full_sweep2 = (sw2_e && !strcmp(sw2_e,"full")) ? 1 : 0;
-  HIPCHK(hipEventRecord(ws->ev_fork,st));
-  HIPCHK(hipStreamWaitEvent(ws->aux,ws->ev_fork,0));
-  hipLaunchKernelGGL(k_classify_unrel,dim3(nreads < 1024 ? nreads : 1024),dim3(WAVE),0,ws->aux,
-                     p->dev,nreads,(cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,(const int32_t *)ws->nintvl.p,
-                     (int32_t *)ws->ord.p,(const int32_t *)ws->perm.p,d_prof_off,compact_rel ? (uint32_t *)ws->pcls.p : (uint32_t *)nullptr,soa);
-  hipLaunchKernelGGL((k_classify_unrel_grp<UNREL_SMALL_MAXN,1024,UNREL_BIG_G,0>),dim3((nreads+UNREL_BIG_G-1)/UNREL_BIG_G < 2048 ? (nreads+UNREL_BIG_G-1)/UNREL_BIG_G : 2048),dim3(WAVE),0,ws->aux,
-                     p->dev,nreads,(cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,(const int32_t *)ws->nintvl.p,
-                     (const int32_t *)ws->perm.p,d_prof_off,compact_rel ? (uint32_t *)ws->pcls.p : (uint32_t *)nullptr,soa,full_sweep2);
-  HIPCHK(hipEventRecord(ws->ev_join,ws->aux));
-  if (soa_on)
-    hipLaunchKernelGGL((k_classify_unrel_grp<0,UNREL_SMALL_MAXN,UNREL_SMALL_G,1>),dim3((nreads+UNREL_SMALL_G-1)/UNREL_SMALL_G),dim3(WAVE),0,st,
-                       p->dev,nreads,(cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,(const int32_t *)ws->nintvl.p,
-                       (const int32_t *)ws->perm.p,d_prof_off,(uint32_t *)ws->pcls.p,soa,full_sweep2);
-  else
-    hipLaunchKernelGGL((k_classify_unrel_grp<0,UNREL_SMALL_MAXN,UNREL_SMALL_G,0>),dim3((nreads+UNREL_SMALL_G-1)/UNREL_SMALL_G),dim3(WAVE),0,st,
-                       p->dev,nreads,(cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,(const int32_t *)ws->nintvl.p,
-                       (const int32_t *)ws->perm.p,d_prof_off,compact_rel ? (uint32_t *)ws->pcls.p : (uint32_t *)nullptr,soa,full_sweep2);
-  HIPCHK(hipStreamWaitEvent(st,ws->ev_join,0));
-  HIPCHK(hipGetLastError());
-  if (last_stage == CP_STAGE_CLASS_ALL)
-    return CP_OK;
-
-  // ---- stage 6: labels ---------------------------------------------------------------------------
-  hipLaunchKernelGGL(k_paint_labels,dim3(nreads),dim3(WAVE),0,st,
-                     p->dev,d_seq_off,nreads,(const cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,
-                     (const int32_t *)ws->nintvl.p,d_labels,compact_rel ? (const uint32_t *)ws->pcls.p : (const uint32_t *)nullptr);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  if (nreads == 0) return CP_OK;
+  run_ctx c = { p, d_seq, d_seq_off, d_prof, d_prof_off, d_labels, nreads, total_kmers, last_stage, st, read_knobs() };
+  c.fuse_rel = c.knobs.fuse_rel && last_stage >= CP_STAGE_REL;
+  c.compact = (c.fuse_rel && last_stage == CP_STAGE_LABELS) ? c.knobs.compact : 0;
+  CHK(stage_scan_caps(ws,c));       if (last_stage == CP_STAGE_SCAN) return CP_OK;
+  CHK(wait_totals(ws,c));
+  CHK(stage_wall(ws,c));            if (last_stage == CP_STAGE_WALL) return CP_OK;
+  CHK(stage_rel(ws,c));             if (last_stage == CP_STAGE_REL) return CP_OK;
+  CHK(stage_classify_rel(ws,c));    if (last_stage == CP_STAGE_CLASS_REL) return CP_OK;
+  CHK(stage_classify_unrel(ws,c));  if (last_stage == CP_STAGE_CLASS_ALL) return CP_OK;
+  return stage_labels(ws,c);
 }
 
 extern "C" int cp_classify_batch(const cp_params *p, cp_workspace *ws,
@@ -713,8 +738,8 @@ extern "C" int cp_workspace_check(cp_workspace *ws)
 { if (!ws) return set_err(CP_EINVAL,"cp_workspace_check: null workspace");
   // one read-back of the three sticky error words, then they are cleared: every flag raised by a call on this
   // workspace since the previous check is reported once
-  HIPCHK(hipMemcpyAsync(ws->h_err,ws->err.p,16,hipMemcpyDeviceToHost,ws->stream));
-  HIPCHK(hipMemsetAsync(ws->err.p,0,16,ws->stream));
+  HIPCHK(hipMemcpyAsync(ws->h_err,ws->b.err.p,16,hipMemcpyDeviceToHost,ws->stream));
+  HIPCHK(hipMemsetAsync(ws->b.err.p,0,16,ws->stream));
   HIPCHK(hipStreamSynchronize(ws->stream));
   for (void *q : *ws->retired) (void)hipFree(q);          // nothing on the stream uses an outgrown buffer any more
   ws->retired->clear();
@@ -738,61 +763,56 @@ extern "C" int cp_workspace_check(cp_workspace *ws)
 
 extern "C" int cp_get_counts(cp_workspace *ws, int32_t *n_cand, int32_t *n_intvl, int32_t *n_rel, int64_t *cap_off)
 { if (!ws) return set_err(CP_EINVAL,"cp_get_counts: null workspace");
-  int rc = cp_workspace_check(ws);
-  if (rc != CP_OK) return rc;
+  CHK(cp_workspace_check(ws));
   size_t n = (size_t)ws->nreads;
   if (n == 0) return CP_OK;
-  if (n_cand)  HIPCHK(hipMemcpy(n_cand,ws->ncand.p,n*4,hipMemcpyDeviceToHost));
-  if (n_intvl) HIPCHK(hipMemcpy(n_intvl,ws->nintvl.p,n*4,hipMemcpyDeviceToHost));
-  if (n_rel)   HIPCHK(hipMemcpy(n_rel,ws->nrel.p,n*4,hipMemcpyDeviceToHost));
-  if (cap_off) HIPCHK(hipMemcpy(cap_off,ws->ioff.p,(n+1)*8,hipMemcpyDeviceToHost));
+  if (n_cand)  HIPCHK(hipMemcpy(n_cand,ws->b.ncand.p,n*4,hipMemcpyDeviceToHost));
+  if (n_intvl) HIPCHK(hipMemcpy(n_intvl,ws->b.nintvl.p,n*4,hipMemcpyDeviceToHost));
+  if (n_rel)   HIPCHK(hipMemcpy(n_rel,ws->b.nrel.p,n*4,hipMemcpyDeviceToHost));
+  if (cap_off) HIPCHK(hipMemcpy(cap_off,ws->b.ioff.p,(n+1)*8,hipMemcpyDeviceToHost));
   return CP_OK;
 }
+
+template <class T> static int fetch(std::vector<T> &v, const dbuf &b, size_t n)      // the first n elements of a device buffer
+{ v.resize(n); HIPCHK(hipMemcpy(v.data(),b.p,n*sizeof(T),hipMemcpyDeviceToHost)); return CP_OK; }
+
+// cp_get_intervals after a whole-path call (cp_classify_batch): the final classes live in the (end, class) words the
+// label paint reads, not in the records: they are put into the records here.
+static int compact_intervals_to_host(cp_workspace *ws, cp_intvl *intvl)
+try
+{ const size_t nI = (size_t)ws->totalI, nr = (size_t)ws->nreads;
+  std::vector<uint32_t> pc; std::vector<int64_t> off; std::vector<int32_t> ni;
+  CHK(fetch(pc,ws->b.pcls,nI)); CHK(fetch(off,ws->b.ioff,nr+1)); CHK(fetch(ni,ws->b.nintvl,nr));
+  std::vector<cp_ivA> A; std::vector<cp_ivB> B; std::vector<cp_ivC> Cc;
+  if (ws->last_compact == 2)                              // the records went to the device as three arrays: put them together
+    { CHK(fetch(A,ws->b.ivA,nI)); CHK(fetch(B,ws->b.ivB,nI)); CHK(fetch(Cc,ws->b.ivC,nI)); }
+  for (size_t r = 0; r < nr; r++)
+    for (int k = 0; k < ni[r]; k++)
+      { const size_t at = (size_t)(off[r]+k);
+        cp_intvl &I = intvl[at];
+        if (ws->last_compact == 2)
+          { memset(&I,0,sizeof(I));
+            I.b = A[at].b; I.e = A[at].e; I.cb = A[at].cb; I.ce = A[at].ce; I.ccb = A[at].ccb; I.cce = A[at].cce;
+            I.is_rel = Cc[at].is_rel; I.pe = B[at].pe; I.peo_b = B[at].peo_b; I.peo_e = B[at].peo_e;
+          }
+        I.asgn = (int8_t)CP_PCLS_CLS(pc[at]);
+      }
+  return CP_OK;
+}
+catch (const std::bad_alloc &) { return set_err(CP_ENOMEM,"cp_get_intervals: out of host memory"); }   // (never through the C ABI)
 
 extern "C" int cp_get_intervals(cp_workspace *ws, cp_intvl *intvl, cp_intvl *rintvl, int64_t capacity)
 { if (!ws) return set_err(CP_EINVAL,"cp_get_intervals: null workspace");
   if (capacity < ws->totalI) return set_err(CP_EINVAL,"cp_get_intervals: capacity too small");
-  int rc = cp_workspace_check(ws);
-  if (rc != CP_OK) return rc;
+  CHK(cp_workspace_check(ws));
   size_t bytes = (size_t)ws->totalI*sizeof(cp_intvl);
   if (bytes == 0) return CP_OK;
-  if (intvl && ws->last_stage >= CP_STAGE_WALL) HIPCHK(hipMemcpy(intvl,ws->intvl.p,bytes,hipMemcpyDeviceToHost));
-  if (ws->last_compact)
-    { // after a whole-path call (cp_classify_batch) the final classes live in the (end, class) words the label paint reads,
-      // not in the records, and the reliable-interval copies were never made: the classes are put into the records here,
-      // `rintvl` comes back zeroed (run the stages up to CP_STAGE_CLASS_ALL for it)
-      if (rintvl) memset(rintvl,0,bytes);
-      if (intvl)
-        try
-        { std::vector<uint32_t> pc((size_t)ws->totalI);
-          std::vector<int64_t> off((size_t)ws->nreads+1);
-          std::vector<int32_t> ni((size_t)ws->nreads);
-          HIPCHK(hipMemcpy(pc.data(),ws->pcls.p,(size_t)ws->totalI*4,hipMemcpyDeviceToHost));
-          HIPCHK(hipMemcpy(off.data(),ws->ioff.p,((size_t)ws->nreads+1)*8,hipMemcpyDeviceToHost));
-          HIPCHK(hipMemcpy(ni.data(),ws->nintvl.p,(size_t)ws->nreads*4,hipMemcpyDeviceToHost));
-          std::vector<cp_ivA> A; std::vector<cp_ivB> B; std::vector<cp_ivC> Cc;
-          if (ws->last_compact == 2)                      // the records went to the device as three arrays: put them together
-            { A.resize((size_t)ws->totalI); B.resize((size_t)ws->totalI); Cc.resize((size_t)ws->totalI);
-              HIPCHK(hipMemcpy(A.data(),ws->ivA.p,(size_t)ws->totalI*sizeof(cp_ivA),hipMemcpyDeviceToHost));
-              HIPCHK(hipMemcpy(B.data(),ws->ivB.p,(size_t)ws->totalI*sizeof(cp_ivB),hipMemcpyDeviceToHost));
-              HIPCHK(hipMemcpy(Cc.data(),ws->ivC.p,(size_t)ws->totalI*sizeof(cp_ivC),hipMemcpyDeviceToHost));
-            }
-          for (int r = 0; r < ws->nreads; r++)
-            for (int k = 0; k < ni[(size_t)r]; k++)
-              { const size_t at = (size_t)(off[(size_t)r]+k);
-                cp_intvl &I = intvl[at];
-                if (ws->last_compact == 2)
-                  { memset(&I,0,sizeof(I));
-                    I.b = A[at].b; I.e = A[at].e; I.cb = A[at].cb; I.ce = A[at].ce; I.ccb = A[at].ccb; I.cce = A[at].cce;
-                    I.is_rel = Cc[at].is_rel; I.pe = B[at].pe; I.peo_b = B[at].peo_b; I.peo_e = B[at].peo_e;
-                  }
-                I.asgn = (int8_t)CP_PCLS_CLS(pc[at]);
-              }
-        }
-        catch (const std::bad_alloc &) { return set_err(CP_ENOMEM,"cp_get_intervals: out of host memory"); }   // (never through the C ABI)
-      return CP_OK;
+  if (intvl && ws->last_stage >= CP_STAGE_WALL) HIPCHK(hipMemcpy(intvl,ws->b.intvl.p,bytes,hipMemcpyDeviceToHost));
+  if (ws->last_compact)                                   // the reliable-interval copies were never made: `rintvl` comes
+    { if (rintvl) memset(rintvl,0,bytes);                 // back zeroed (run the stages up to CP_STAGE_CLASS_ALL for it)
+      return intvl ? compact_intervals_to_host(ws,intvl) : CP_OK;
     }
-  if (rintvl && ws->last_stage >= CP_STAGE_REL) HIPCHK(hipMemcpy(rintvl,ws->rintvl.p,bytes,hipMemcpyDeviceToHost));
+  if (rintvl && ws->last_stage >= CP_STAGE_REL) HIPCHK(hipMemcpy(rintvl,ws->b.rintvl.p,bytes,hipMemcpyDeviceToHost));
   return CP_OK;
 }
 
@@ -801,12 +821,11 @@ extern "C" int cp_get_rel_asgn(cp_workspace *ws, int8_t *fw, int8_t *bw, int64_t
   if (capacity < ws->totalI) return set_err(CP_EINVAL,"cp_get_rel_asgn: capacity too small");
   if (ws->last_stage < CP_STAGE_CLASS_REL) return set_err(CP_EINVAL,"cp_get_rel_asgn: stage not run");
   if (ws->last_stage == CP_STAGE_LABELS) return set_err(CP_EINVAL,"cp_get_rel_asgn: run cp_run_stages up to CP_STAGE_CLASS_REL or CP_STAGE_CLASS_ALL (the whole-path call does not keep the two assignments of reads without reliable intervals defined)");
-  int rc = cp_workspace_check(ws);
-  if (rc != CP_OK) return rc;
+  CHK(cp_workspace_check(ws));
   size_t n = (size_t)ws->totalI;
   if (n == 0) return CP_OK;
-  if (fw) HIPCHK(hipMemcpy(fw,ws->asgn.p,n,hipMemcpyDeviceToHost));
-  if (bw) HIPCHK(hipMemcpy(bw,(int8_t *)ws->asgn.p+n,n,hipMemcpyDeviceToHost));
+  if (fw) HIPCHK(hipMemcpy(fw,ws->b.asgn.p,n,hipMemcpyDeviceToHost));
+  if (bw) HIPCHK(hipMemcpy(bw,as<int8_t>(ws->b.asgn)+n,n,hipMemcpyDeviceToHost));
   return CP_OK;
 }
 
@@ -814,7 +833,7 @@ extern "C" int cp_get_bitmap(cp_workspace *ws, uint64_t *words, int64_t nwords)
 { if (!ws || !words) return set_err(CP_EINVAL,"cp_get_bitmap: null argument");
   if (nwords > ws->nwords) nwords = ws->nwords;
   HIPCHK(hipStreamSynchronize(ws->stream));
-  if (nwords > 0) HIPCHK(hipMemcpy(words,ws->bitmap.p,(size_t)nwords*8,hipMemcpyDeviceToHost));
+  if (nwords > 0) HIPCHK(hipMemcpy(words,ws->b.bitmap.p,(size_t)nwords*8,hipMemcpyDeviceToHost));
   return CP_OK;
 }
 
@@ -830,8 +849,7 @@ extern "C" int cp_decode_profiles(cp_workspace *ws, const uint8_t *d_codes, cons
     return set_err(CP_EINVAL,"cp_decode_profiles: bad argument");
   if (nreads == 0) return CP_OK;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_decode_profiles,dim3(nreads),dim3(WAVE),0,st,
-                     d_codes,d_code_off,d_prof_off,nreads,d_prof,(int32_t *)ws->err.p+2);
+  hipLaunchKernelGGL(k_decode_profiles,dim3(nreads),dim3(WAVE),0,st,d_codes,d_code_off,d_prof_off,nreads,d_prof,as<int32_t>(ws->b.err)+2);
   HIPCHK(hipGetLastError());
   ws->decode_pending = 1;
   ws->stream = st;
@@ -852,51 +870,40 @@ extern "C" int cp_find_seeds_batch(const cp_params *p, cp_workspace *ws, const c
   ws->stream = st; ws->seed_nreads = nreads; ws->seed_totalR = 0;
   if (nreads == 0) return CP_OK;
   const int K = p->host.K;
-  ENSURE(ws->s_cap,((size_t)nreads+1)*8);
-  ENSURE(ws->s_rcap,((size_t)nreads+1)*8);
-  ENSURE(ws->s_dummy,((size_t)nreads+1)*8);
-  ENSURE(ws->s_key,(size_t)nreads*4);
-  ENSURE(ws->perm,(size_t)nreads*4);
-  ENSURE(ws->s_repcnt,(size_t)nreads*4);
-  HIPCHK(hipMemsetAsync(ws->s_dummy.p,0,((size_t)nreads+1)*8,st));
+  ENSURE(ws->b.s_cap,((size_t)nreads+1)*8); ENSURE(ws->b.s_rcap,((size_t)nreads+1)*8); ENSURE(ws->b.s_dummy,((size_t)nreads+1)*8);
+  ENSURE(ws->b.s_key,(size_t)nreads*4); ENSURE(ws->b.perm,(size_t)nreads*4); ENSURE(ws->b.s_repcnt,(size_t)nreads*4);
+  HIPCHK(hipMemsetAsync(ws->b.s_dummy.p,0,((size_t)nreads+1)*8,st));
   hipLaunchKernelGGL(k_seed_caps,dim3(nreads),dim3(WAVE),0,st,d_prof,d_prof_off,d_labels,d_seq_off,K,nreads,
-                     (int64_t *)ws->s_cap.p,(int64_t *)ws->s_rcap.p,(int32_t *)ws->s_key.p);
-  ENSURE(ws->dtot,32);
-  { int rc = launch_prefix_caps(ws,(int64_t *)ws->s_cap.p,(int64_t *)ws->s_rcap.p,(int64_t *)ws->s_dummy.p,nreads,(int64_t *)ws->dtot.p,st);
-    if (rc != CP_OK) return rc;
-  }
-  HIPCHK(hipMemcpyAsync(&ws->h_totals[0],ws->dtot.p,16,hipMemcpyDeviceToHost,st));
+                     as<int64_t>(ws->b.s_cap),as<int64_t>(ws->b.s_rcap),as<int32_t>(ws->b.s_key));
+  ENSURE(ws->b.dtot,32);
+  CHK(launch_prefix_caps(ws,as<int64_t>(ws->b.s_cap),as<int64_t>(ws->b.s_rcap),as<int64_t>(ws->b.s_dummy),nreads,as<int64_t>(ws->b.dtot),st));
+  HIPCHK(hipMemcpyAsync(&ws->h_totals[0],ws->b.dtot.p,16,hipMemcpyDeviceToHost,st));
   HIPCHK(hipStreamSynchronize(st));
   const int64_t totalS = ws->h_totals[0], totalR = ws->h_totals[1];
   ws->seed_totalR = totalR;
-  ENSURE(ws->s_seg,(size_t)totalS*2*16);
-  ENSURE(ws->s_aux,(size_t)totalS*4);
-  ENSURE(ws->s_mi,((size_t)totalS+3*(size_t)nreads)*2*4);
-  ENSURE(ws->s_rep,(size_t)totalR*2*4+16);
+  ENSURE(ws->b.s_seg,(size_t)totalS*2*16);
+  ENSURE(ws->b.s_aux,(size_t)totalS*4);
+  ENSURE(ws->b.s_mi,((size_t)totalS+3*(size_t)nreads)*2*4);
+  ENSURE(ws->b.s_rep,(size_t)totalR*2*4+16);
   HIPCHK(hipMemsetAsync(d_seeds,'E',(size_t)total_bases,st));
   hipLaunchKernelGGL(k_seed_prefix,dim3(nreads),dim3(WAVE),0,st,d_seq_off,K,nreads,d_seeds);
   // longest reads first: key = plen / 64
-  { int rc = launch_order_by_work(ws,(const int32_t *)ws->s_key.p,nreads,6,(int32_t *)ws->perm.p,st);
-    if (rc != CP_OK) return rc;
-  }
+  CHK(launch_order_by_work(ws,as<int32_t>(ws->b.s_key),nreads,6,as<int32_t>(ws->b.perm),st));
   hipLaunchKernelGGL(k_find_seeds,dim3(nreads),dim3(WAVE),0,st,d_seq,d_seq_off,d_prof,d_prof_off,d_labels,K,nreads,
-                     (const int64_t *)ws->s_cap.p,(const int64_t *)ws->s_rcap.p,(const int32_t *)ws->perm.p,
-                     (int32_t *)ws->s_seg.p,(int32_t *)ws->s_aux.p,(int32_t *)ws->s_mi.p,
-                     (int32_t *)ws->s_rep.p,(int32_t *)ws->s_repcnt.p,d_seeds,(int32_t *)ws->err.p+1,totalS);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+                     as<int64_t>(ws->b.s_cap),as<int64_t>(ws->b.s_rcap),as<int32_t>(ws->b.perm),as<int32_t>(ws->b.s_seg),as<int32_t>(ws->b.s_aux),
+                     as<int32_t>(ws->b.s_mi),as<int32_t>(ws->b.s_rep),as<int32_t>(ws->b.s_repcnt),d_seeds,as<int32_t>(ws->b.err)+1,totalS);
+  return launch_status();
 }
 
 extern "C" int cp_get_rep_masks(cp_workspace *ws, int32_t *count, int64_t *cap_off, int32_t *pairs, int64_t capacity)
 { if (!ws) return set_err(CP_EINVAL,"cp_get_rep_masks: null workspace");
   if (capacity < ws->seed_totalR) return set_err(CP_EINVAL,"cp_get_rep_masks: capacity too small");
-  int rc = cp_workspace_check(ws);
-  if (rc != CP_OK) return rc;
+  CHK(cp_workspace_check(ws));
   const size_t n = (size_t)ws->seed_nreads;
   if (n == 0) return CP_OK;
-  if (count)   HIPCHK(hipMemcpy(count,ws->s_repcnt.p,n*4,hipMemcpyDeviceToHost));
-  if (cap_off) HIPCHK(hipMemcpy(cap_off,ws->s_rcap.p,(n+1)*8,hipMemcpyDeviceToHost));
-  if (pairs && ws->seed_totalR > 0) HIPCHK(hipMemcpy(pairs,ws->s_rep.p,(size_t)ws->seed_totalR*8,hipMemcpyDeviceToHost));
+  if (count)   HIPCHK(hipMemcpy(count,ws->b.s_repcnt.p,n*4,hipMemcpyDeviceToHost));
+  if (cap_off) HIPCHK(hipMemcpy(cap_off,ws->b.s_rcap.p,(n+1)*8,hipMemcpyDeviceToHost));
+  if (pairs && ws->seed_totalR > 0) HIPCHK(hipMemcpy(pairs,ws->b.s_rep.p,(size_t)ws->seed_totalR*8,hipMemcpyDeviceToHost));
   return CP_OK;
 }
 extern "C" int64_t cp_rep_masks_capacity(const cp_workspace *ws) { return ws ? ws->seed_totalR : 0; }
@@ -907,8 +914,7 @@ extern "C" int cp_unpack_bases(const uint8_t *d_packed, const int64_t *d_pack_of
     return set_err(CP_EINVAL,"cp_unpack_bases: bad argument");
   if (nreads == 0) return CP_OK;
   hipLaunchKernelGGL(k_unpack_bases,dim3(nreads),dim3(256),0,(hipStream_t)stream,d_packed,d_pack_off,d_seq_off,nreads,d_seq);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 extern "C" int cp_pack_labels(const char *d_labels, const int64_t *d_seq_off, const int64_t *d_pack_off, int nreads,
@@ -917,8 +923,7 @@ extern "C" int cp_pack_labels(const char *d_labels, const int64_t *d_seq_off, co
     return set_err(CP_EINVAL,"cp_pack_labels: bad argument");
   if (nreads == 0) return CP_OK;
   hipLaunchKernelGGL(k_pack_labels,dim3(nreads),dim3(256),0,(hipStream_t)stream,d_labels,d_seq_off,d_pack_off,nreads,d_packed);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 // host: the inverse of cp_pack_labels for one read (stoc of const.c:19 on the codes; the first K-1 labels are 'N')
@@ -1062,10 +1067,10 @@ extern "C" int cp_label_runs(const cp_params *p, cp_workspace *ws, int32_t *d_en
   if (ws->last_stage < CP_STAGE_CLASS_ALL)
     return set_err(CP_EINVAL,"cp_label_runs: the batch on this workspace was not classified (run at least CP_STAGE_CLASS_ALL)");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_label_runs,dim3(ws->nreads),dim3(WAVE),0,st,p->dev,ws->nreads,(const cp_intvl *)ws->intvl.p,(const int64_t *)ws->ioff.p,
-                     (const int32_t *)ws->nintvl.p,d_ends,d_cls,d_nruns,ws->last_compact ? (const uint32_t *)ws->pcls.p : (const uint32_t *)nullptr);
+  hipLaunchKernelGGL(k_label_runs,dim3(ws->nreads),dim3(WAVE),0,st,p->dev,ws->nreads,as<cp_intvl>(ws->b.intvl),as<int64_t>(ws->b.ioff),
+                     as<int32_t>(ws->b.nintvl),d_ends,d_cls,d_nruns,ws->last_compact ? as<uint32_t>(ws->b.pcls) : nullptr);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(d_cap_off,ws->ioff.p,((size_t)ws->nreads+1)*8,hipMemcpyDeviceToDevice,st));
+  HIPCHK(hipMemcpyAsync(d_cap_off,ws->b.ioff.p,((size_t)ws->nreads+1)*8,hipMemcpyDeviceToDevice,st));
   return CP_OK;
 }
 
@@ -1092,8 +1097,7 @@ extern "C" int cp_seq_context(const char *d_seq, const int64_t *d_seq_off, int n
   (void)total_bases;
   if (nreads == 0) return CP_OK;
   hipLaunchKernelGGL(k_seq_context,dim3(nreads),dim3(256),0,(hipStream_t)stream,d_seq,d_seq_off,nreads,d_lctx,d_rctx);
-  HIPCHK(hipGetLastError());
-  return CP_OK;
+  return launch_status();
 }
 
 #ifdef CP_BOUNDS
@@ -1118,48 +1122,38 @@ extern "C" int cp_debug_seed_get(int *out4, int *recs)
   return CP_OK;
 }
 #endif
-#ifdef CP_SEED_PROF
-// diagnostic builds only: wall-clock ticks (100 MHz) of lane 0 of every wave of k_find_seeds_fast per phase, then reset
-extern "C" int cp_debug_seed_prof(unsigned long long *out8)
-{ HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out8,HIP_SYMBOL(g_seed_prof),8*sizeof(unsigned long long)));
-  unsigned long long z[8] = {0};
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_seed_prof),z,sizeof(z)));
+#if defined(CP_SEED_PROF) || defined(CP_PROF_WALK)
+// diagnostic builds only: n <= 12 words of a device profile array to the host, then (reset) zeroed on the device
+static int prof_read(unsigned long long *out, const void *sym, size_t n, bool reset = true)
+{ static const unsigned long long z[12] = {0};
+  HIPCHK(hipMemcpyFromSymbol(out,sym,n*sizeof(unsigned long long)));
+  if (reset) HIPCHK(hipMemcpyToSymbol(sym,z,n*sizeof(unsigned long long)));
   return CP_OK;
 }
+#endif
+#ifdef CP_SEED_PROF
+// wall-clock ticks (100 MHz) of lane 0 of every wave of k_find_seeds_fast per phase, then reset
+extern "C" int cp_debug_seed_prof(unsigned long long *out8)
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_seed_prof),8); }
 #endif
 #ifdef CP_PROF_WALK
 // diagnostic builds only: per read (candidates, tasks, SELF tasks, overflow) as k_wall_tasks left them (scripts/count_dist.py)
 extern "C" int cp_debug_task_counts(cp_workspace *ws, int32_t *out, int64_t nreads)
 { if (!ws || nreads > ws->nreads) return set_err(CP_EINVAL,"cp_debug_task_counts: bad arguments");
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out,ws->fwc.p,(size_t)nreads*4*sizeof(int32_t),hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out,ws->b.fwc.p,(size_t)nreads*4*sizeof(int32_t),hipMemcpyDeviceToHost));
   return CP_OK;
 }
-// diagnostic builds only: per-phase wave times of k_find_wall (max / sum / arg-max over reads), then reset
+// per-phase wave times of k_find_wall (max / sum / arg-max over reads), then reset
 extern "C" int cp_debug_live_prof(unsigned long long *out8)
-{ HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out8,HIP_SYMBOL(g_live_prof),8*sizeof(unsigned long long)));
-  unsigned long long z[8] = {0};
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_live_prof),z,sizeof(z)));
-  return CP_OK;
-}
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_live_prof),8); }
 extern "C" int cp_debug_emit_prof(unsigned long long *out8)
-{ HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out8,HIP_SYMBOL(g_emit_prof),8*sizeof(unsigned long long)));
-  unsigned long long z[8] = {0};
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_emit_prof),z,sizeof(z)));
-  return CP_OK;
-}
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_emit_prof),8); }
 extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 { HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out36,HIP_SYMBOL(g_phase_max),12*sizeof(unsigned long long)));
-  HIPCHK(hipMemcpyFromSymbol(out36+12,HIP_SYMBOL(g_phase_sum),12*sizeof(unsigned long long)));
-  HIPCHK(hipMemcpyFromSymbol(out36+24,HIP_SYMBOL(g_phase_arg),12*sizeof(unsigned long long)));
-  unsigned long long z[12] = {0};
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_max),z,sizeof(z)));
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_sum),z,sizeof(z)));
-  return CP_OK;
+  CHK(prof_read(out36,HIP_SYMBOL(g_phase_max),12));
+  CHK(prof_read(out36+12,HIP_SYMBOL(g_phase_sum),12));
+  return prof_read(out36+24,HIP_SYMBOL(g_phase_arg),12,false);      // (each new maximum stores its own)
 }
 #endif
 
