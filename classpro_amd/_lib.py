@@ -19,6 +19,7 @@ SYMBOLS = [
     "cp_label_runs", "cp_label_runs_capacity", "cp_expand_label_runs",
     "cp_kmer_table_create", "cp_kmer_table_destroy", "cp_kmer_table_add", "cp_kmer_table_stats",
     "cp_kmer_table_consensus", "cp_kmer_table_export",
+    "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
 _lib = None
@@ -30,6 +31,14 @@ class KmerStats(C.Structure):
                 ("label_total", C.c_int64 * 4), ("cns_total", C.c_int64 * 4), ("s_fixed_hi", C.c_uint64),
                 ("s_fixed_lo", C.c_uint64), ("consistency", C.c_double), ("slots", C.c_int64), ("bytes", C.c_int64),
                 ("growths", C.c_int64)]
+
+
+class AccStats(C.Structure):
+    """cp_acc_stats of include/classpro_amd.h."""
+    _fields_ = [("cfm", (C.c_int64 * 4) * 4), ("ntot", C.c_int64), ("ncor", C.c_int64), ("nfne", C.c_int64),
+                ("ntot_normal", C.c_int64), ("ncor_normal", C.c_int64), ("nfne_normal", C.c_int64),
+                ("ntot_repeat", C.c_int64), ("ncor_repeat", C.c_int64), ("nfne_repeat", C.c_int64),
+                ("n_reads", C.c_int64), ("n_reads_filtered", C.c_int64), ("n_invalid", C.c_int64)]
 
 
 class ClassProError(RuntimeError):
@@ -106,6 +115,12 @@ def lib():
     L.cp_kmer_table_consensus.argtypes = [vp, vp, vp, i32, i64, vp, vp]
     L.cp_kmer_table_export.argtypes = [vp, vp, vp, vp, i64]
     L.cp_kmer_table_export.restype = i64
+    L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
+    L.cp_acc_destroy.argtypes = [vp]
+    L.cp_acc_destroy.restype = None
+    L.cp_acc_add.argtypes = [vp, vp, vp, vp, i32, i64, vp]
+    L.cp_acc_read.argtypes = [vp, C.POINTER(AccStats)]
     _lib = L
     return L
 

@@ -404,3 +404,97 @@ class KmerTable:
         m = check(self.L.cp_kmer_table_export(self.t, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, n))
         assert m == n
         return hi[:n], lo[:n], cnt[:n]
+
+
+def _stream_of(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def threshold_labels(batch, thresholds, K, packed=False, counts=None):
+    """cp_threshold_labels (the per-read loop of ClassGS.c:228-248): a count c is E if c < thresholds[0], else H if
+    c < thresholds[1], else D if c < thresholds[2], else R; every read gets min(K-1, rlen) 'N' first.  `batch` is a
+    `Batch` or a tuple of device tensors (prof int16/uint16 payload, prof_off int64 [n+1], seq_off int64 [n+1]); reads
+    shorter than K are allowed.  Returns (labels, counts): labels a uint8 device tensor of seq_off[n] characters -- or,
+    with packed=True, the 2-bit bytes of cp_pack_labels and their int64 offsets as (packed, pack_off) -- and counts an
+    int64 device tensor [4], order E, H, D, R.  Pass a previous `counts` tensor to go on adding to it.  Nothing is
+    copied to the host."""
+    if isinstance(batch, Batch):
+        prof, prof_off, seq_off = batch.prof, batch.prof_off, batch.seq_off
+    else:
+        prof, prof_off, seq_off = batch
+    dev = seq_off.device
+    if dev.type != "cuda":
+        raise ValueError("classpro_amd runs on a HIP device only")
+    n = seq_off.numel() - 1
+    total = int(seq_off[-1].item()) if n > 0 else 0
+    t = (C.c_int32 * 3)(*[int(x) for x in thresholds])
+    if counts is None:
+        counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        if packed:
+            clen = (seq_off[1:] - seq_off[:-1] + 3) >> 2
+            pack_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(clen, 0, out=pack_off[1:])
+            out = torch.empty(max(int(pack_off[-1].item()) if n > 0 else 0, 1), dtype=torch.uint8, device=dev)
+            check(lib().cp_threshold_labels(K, t, prof.data_ptr(), prof_off.data_ptr(), seq_off.data_ptr(), n, total, None,
+                                            out.data_ptr(), pack_off.data_ptr(), counts.data_ptr(), _stream_of(dev)))
+            return (out, pack_off), counts
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        check(lib().cp_threshold_labels(K, t, prof.data_ptr(), prof_off.data_ptr(), seq_off.data_ptr(), n, total,
+                                        out.data_ptr(), None, None, counts.data_ptr(), _stream_of(dev)))
+    return out, counts
+
+
+class LabelAccuracy:
+    """class2acc's counting (class2acc.c:141-316, default report) for label strings in HBM (cp_acc_*; semantics in
+    include/classpro_amd.h): an accumulator over batches.  max_e_pct / rep_pct are class2acc's -f / -r."""
+
+    STATES = "ERHD"                                        # order of the confusion matrix's rows and columns
+
+    def __init__(self, K, max_e_pct=100, rep_pct=0, device="cuda:0"):
+        from ._lib import AccStats
+        self.L = lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("classpro_amd runs on a HIP device only")
+        torch.cuda.set_device(self.device)
+        self.K = K
+        self._Stats = AccStats
+        a = C.c_void_p()
+        check(self.L.cp_acc_create(K, float(max_e_pct), float(rep_pct), C.byref(a)))
+        self.a = a
+
+    def close(self):
+        if getattr(self, "a", None):
+            self.L.cp_acc_destroy(self.a)
+            self.a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, est, truth, seq_off=None):
+        """Adds a batch: `est` / `truth` uint8 device tensors in the label layout and `seq_off` int64 [n+1]; or
+        add(batch, truth) for a `Batch` labelled by Classifier.classify / run (its `labels` tensor is the estimate)."""
+        if isinstance(est, Batch):
+            est, seq_off = est.labels, est.seq_off
+        n = seq_off.numel() - 1
+        total = int(seq_off[-1].item()) if n > 0 else 0
+        if est.numel() < total or truth.numel() < total:
+            raise ValueError("LabelAccuracy.add: a label tensor is shorter than seq_off[-1]")
+        check(self.L.cp_acc_add(self.a, est.data_ptr(), truth.data_ptr(), seq_off.data_ptr(), n, total,
+                                _stream_of(self.device)))
+
+    def stats(self):
+        """dict: cfm (4x4 list, truth row, estimate column, order E R H D), ntot/ncor/nfne (all, _normal, _repeat),
+        n_reads, n_reads_filtered, n_invalid, accuracy and fn_error in percent (nan without counted k-mers).
+        Raises ClassProError (CP_EINVAL) when a label position held a character other than E/H/D/R."""
+        s = self._Stats()
+        check(self.L.cp_acc_read(self.a, C.byref(s)))
+        d = {f: getattr(s, f) for f, _ in s._fields_ if f != "cfm"}
+        d["cfm"] = [list(row) for row in s.cfm]
+        d["accuracy"] = 100.0 * s.ncor / s.ntot if s.ntot else float("nan")
+        d["fn_error"] = 100.0 * s.nfne / s.ntot if s.ntot else float("nan")
+        return d

@@ -12,6 +12,7 @@ OUT = os.path.join(_HERE, "libclasspro_amd.so")
 SYNTH = os.path.join(_HERE, "libcp_synth.so")  # device-side synthetic read sets: test / bench infrastructure (csrc/synth/)
 CLI = os.path.join(_HERE, "ClassPro")          # drop-in command line (csrc/host/classpro_main.cpp)
 CNS = os.path.join(_HERE, "class2cns")         # per-k-mer label consensus (csrc/host/class2cns.cpp; its flags use the GPU)
+GS = os.path.join(_HERE, "ClassGS")             # global-threshold labels and their accuracy (csrc/host/classgs.cpp; uses the GPU)
 TOOLS = {"prof2class": "prof2class.cpp", "class2acc": "class2acc.cpp"}   # host-only evaluation tools
 # -ffp-contract=off: the decision path compares doubles against thresholds and truncates them to
 # ints (class_rel.c:449,483); fused multiply-adds would change those values.
@@ -52,7 +53,7 @@ def _run(cmd, verbose):
 
 def build(force=False, verbose=False):
     # the HIP objects: library, command line, synthetic-set generator
-    outs, side, key = [OUT, CLI, CNS, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
+    outs, side, key = [OUT, CLI, CNS, GS, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
     if not _fresh(outs, side, key, force):
         if os.path.exists(side):
             os.remove(side)
@@ -61,6 +62,8 @@ def build(force=False, verbose=False):
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "classpro_main.cpp"), "-o", CLI,
               "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "class2cns.cpp"), "-o", CNS,
+              "-L" + _HERE, "-lclasspro_amd", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "classgs.cpp"), "-o", GS,
               "-L" + _HERE, "-lclasspro_amd", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
               os.path.join(CSRC, "synth", "synth_gen.hip"), "-o", SYNTH], verbose)

@@ -1159,3 +1159,6 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 
 // per-k-mer label table (class2cns): kmer_table.hip
 #include "kmer_table.hip"
+
+// global-threshold labels and label accuracy (ClassGS): label_tools.hip
+#include "label_tools.hip"

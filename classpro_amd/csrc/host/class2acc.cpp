@@ -7,6 +7,7 @@
 // estimate columns, order E R H D) and the overall / [Normal] / [Repeat] accuracy lines.  The
 // classified k-mers of a read are the positions after the leading 'N's of the estimate.
 #include "host_io.h"
+#include "acc_report.h"
 #include "../cp_host_setup.h"
 
 static const char *USAGE =
@@ -70,10 +71,11 @@ int main(int argc, char **argv)
   std::vector<uint16_t> profile(20000);
 
   int id = 1;
-  long long ntot = 0, ncor = 0, nfne = 0;
-  long long ntot_normal = 0, ncor_normal = 0, nfne_normal = 0;
-  long long ntot_repeat = 0, ncor_repeat = 0, nfne_repeat = 0;
-  long long cfm[4][4] = {};
+  AccTotals T;                                                             // class2acc.c:126-133
+  long long &ntot = T.ntot, &ncor = T.ncor, &nfne = T.nfne;
+  long long &ntot_normal = T.ntot_normal, &ncor_normal = T.ncor_normal, &nfne_normal = T.nfne_normal;
+  long long &ntot_repeat = T.ntot_repeat, &ncor_repeat = T.ncor_repeat, &nfne_repeat = T.nfne_repeat;
+  long long (&cfm)[4][4] = T.cfm;
   double cov[2] = { -1, -1 };
   while (est.next() >= 0)
     { if (tru.next() < 0)
@@ -164,20 +166,6 @@ int main(int argc, char **argv)
   if (tru.next() >= 0)
     die("# seqs in %s < # seqs in %s\n",pos[0].c_str(),pos[1].c_str());
 
-  static const char stoc[4] = { 'E', 'R', 'H', 'D' };
-  fprintf(stdout,"\nConfusion Matrix (Truth\\Est):\n  ");
-  for (int i = 0; i < 4; i++) fprintf(stdout,"%15c",stoc[i]);
-  fprintf(stdout,"\n");
-  for (int i = 0; i < 4; i++)
-    { fprintf(stdout,"%c:",stoc[i]);
-      for (int j = 0; j < 4; j++) fprintf(stdout,"%15lld",cfm[i][j]);
-      fprintf(stdout,"\n");
-    }
-  fprintf(stdout,"\nAccuracy = %4.2lf %% (= %lld / %lld), FN Error = %4.2lf %%\n",
-          (double)ncor/ntot*100,ncor,ntot,(double)nfne/ntot*100);
-  fprintf(stdout,"[Normal] Accuracy = %4.2lf %% (= %lld / %lld), FN Error = %4.2lf %%\n",
-          (double)ncor_normal/ntot_normal*100,ncor_normal,ntot_normal,(double)nfne_normal/ntot_normal*100);
-  fprintf(stdout,"[Repeat] Accuracy = %4.2lf %% (= %lld / %lld), FN Error = %4.2lf %%\n",
-          (double)ncor_repeat/ntot_repeat*100,ncor_repeat,ntot_repeat,(double)nfne_repeat/ntot_repeat*100);
+  print_acc_report(stdout,T);
   return 0;
 }

@@ -314,6 +314,56 @@ int  cp_kmer_table_consensus(cp_kmer_table *t, const char *d_seq, const int64_t 
  * entries; when capacity is smaller than that (or an array is NULL) nothing is written. */
 int64_t cp_kmer_table_export(cp_kmer_table *t, uint64_t *hi, uint64_t *lo, uint32_t *counts4, int64_t capacity);
 
+/* ------------------------------------------------------------------------------------------
+ * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
+ * baseline the reference compares ClassPro against, for a batch in the flat layout above.
+ *
+ *   Label     of a count c: E if c < thres[0], else H if c < thres[1], else D if c < thres[2], else R.  This is the
+ *             reference's chain, so unsorted thresholds have a defined result (with 30 10 50 no k-mer is H).  Any
+ *             int32_t value is legal (the host clamps to [0, 65536]); counts are the full uint16_t range.
+ *   Read r    gets 'N' on its first min(K-1, rlen_r) positions, then one label per count.  Unlike cp_classify_batch,
+ *             reads shorter than K are allowed: they have no counts (prof_off[r+1] = prof_off[r]) and get only 'N'.
+ *   Outputs   each optional (NULL = not wanted, at least one required):
+ *             d_labels  [total_bases]  the characters;
+ *             d_packed  + d_pack_off [nreads+1]: the 2-bit layout of cp_pack_labels, written directly;
+ *             d_counts  int64 [4] on the device, order E, H, D, R, ADDED TO, so several batches accumulate.
+ * Offsets are 64-bit throughout: a batch may hold more than 2^31 bases.  Asynchronous on `stream`.
+ */
+int cp_threshold_labels(int K, const int32_t *thres, const uint16_t *d_prof, const int64_t *d_prof_off,
+                        const int64_t *d_seq_off, int nreads, int64_t total_bases, char *d_labels,
+                        uint8_t *d_packed, const int64_t *d_pack_off, int64_t *d_counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Label accuracy: replaces the counting of src/class2acc.c:141-316 (default report) for an estimate and a truth label
+ * string that are already on the device, both in the layout of `labels` above.  An accumulator, so batches add up.
+ *
+ *   Per read  over positions i >= K-1: rtot = rlen-(K-1), rcor = equal labels, rfne = truth E and estimate not E,
+ *             rcomp[4] = truth composition.  Reads with rlen < K contribute nothing.
+ *   cfm       [truth][estimate], order E, R, H, D as class2acc prints it (its stoc); counts every read.
+ *   Filter    a read with (double)rcomp[E]/rtot*100 > max_e_pct (class2acc -f, default 100) is left out of all nine
+ *             totals and counted in n_reads_filtered.  Otherwise it goes to "repeat" when
+ *             (double)rcomp[R]/rtot*100 > rep_pct (-r, default 0), else to "normal".  The device evaluates exactly
+ *             these double expressions (divide, then multiply, no contraction), so the decisions are the host tool's.
+ *   Invalid   a character other than E H D R at a position >= K-1 of either string is tallied in n_invalid, counted
+ *             nowhere else, and makes every later cp_acc_read return CP_EINVAL (deferred; `stats` is still filled).
+ * All sums are integers: the result is the same bit for bit whatever the batching or the read order.
+ */
+typedef struct cp_acc cp_acc;
+typedef struct
+  { int64_t cfm[4][4];
+    int64_t ntot, ncor, nfne;                            /* reads that passed the filter */
+    int64_t ntot_normal, ncor_normal, nfne_normal;
+    int64_t ntot_repeat, ncor_repeat, nfne_repeat;
+    int64_t n_reads, n_reads_filtered, n_invalid;
+  } cp_acc_stats;
+int  cp_acc_create(int K, double max_e_pct, double rep_pct, cp_acc **out);
+void cp_acc_destroy(cp_acc *a);
+/* Asynchronous on `stream`. */
+int  cp_acc_add(cp_acc *a, const char *d_est, const char *d_truth, const int64_t *d_seq_off, int nreads,
+                int64_t total_bases, void *stream);
+/* Synchronises. */
+int  cp_acc_read(cp_acc *a, cp_acc_stats *out);
+
 #ifdef __cplusplus
 }
 #endif
