@@ -19,6 +19,8 @@ SYMBOLS = [
     "cp_label_runs", "cp_label_runs_capacity", "cp_expand_label_runs",
     "cp_kmer_table_create", "cp_kmer_table_destroy", "cp_kmer_table_add", "cp_kmer_table_stats",
     "cp_kmer_table_consensus", "cp_kmer_table_export",
+    "cp_kmer_counts_create", "cp_kmer_counts_destroy", "cp_kmer_counts_add", "cp_kmer_counts_profiles",
+    "cp_kmer_counts_hist", "cp_kmer_counts_stats",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -31,6 +33,12 @@ class KmerStats(C.Structure):
                 ("label_total", C.c_int64 * 4), ("cns_total", C.c_int64 * 4), ("s_fixed_hi", C.c_uint64),
                 ("s_fixed_lo", C.c_uint64), ("consistency", C.c_double), ("slots", C.c_int64), ("bytes", C.c_int64),
                 ("growths", C.c_int64)]
+
+
+class KmerCountStats(C.Structure):
+    """cp_kmer_count_stats of include/classpro_amd.h."""
+    _fields_ = [("n_kmers", C.c_int64), ("n_skipped", C.c_int64), ("n_distinct", C.c_int64), ("slots", C.c_int64),
+                ("bytes", C.c_int64), ("growths", C.c_int64)]
 
 
 class AccStats(C.Structure):
@@ -115,6 +123,13 @@ def lib():
     L.cp_kmer_table_consensus.argtypes = [vp, vp, vp, i32, i64, vp, vp]
     L.cp_kmer_table_export.argtypes = [vp, vp, vp, vp, i64]
     L.cp_kmer_table_export.restype = i64
+    L.cp_kmer_counts_create.argtypes = [i32, i64, C.POINTER(vp)]
+    L.cp_kmer_counts_destroy.argtypes = [vp]
+    L.cp_kmer_counts_destroy.restype = None
+    L.cp_kmer_counts_add.argtypes = [vp, vp, vp, i32, i64, vp]
+    L.cp_kmer_counts_profiles.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp]
+    L.cp_kmer_counts_hist.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    L.cp_kmer_counts_stats.argtypes = [vp, C.POINTER(KmerCountStats)]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -137,6 +137,26 @@ class Batch:
         return b
 
     @classmethod
+    def from_seqs(cls, seqs, K, device="cuda:0"):
+        """A batch of reads alone: `prof` has room for every k-mer count (rlen-(K-1) per read, none for a read shorter
+        than K) but is not filled; `KmerCounts.profiles(batch)` fills it on the device."""
+        b = cls.__new__(cls)
+        b.device = dev = torch.device(device)
+        rl = np.array([len(s) for s in seqs], np.int64)
+        b.seq_off_h = np.zeros(len(seqs) + 1, np.int64)
+        b.prof_off_h = np.zeros(len(seqs) + 1, np.int64)
+        np.cumsum(rl, out=b.seq_off_h[1:])
+        np.cumsum(np.maximum(rl - (K - 1), 0), out=b.prof_off_h[1:])
+        b.nreads, b.total_bases, b.total_kmers = len(seqs), int(b.seq_off_h[-1]), int(b.prof_off_h[-1])
+        flat = np.frombuffer(b"".join(bytes(s) for s in seqs), np.uint8)
+        b.seq = torch.from_numpy(flat.copy() if len(flat) else np.zeros(1, np.uint8)).to(dev)
+        b.prof = torch.empty(max(b.total_kmers, 8), dtype=torch.int16, device=dev)
+        b.seq_off = torch.from_numpy(b.seq_off_h).to(dev)
+        b.prof_off = torch.from_numpy(b.prof_off_h).to(dev)
+        b.labels = torch.zeros(max(b.total_bases, 1), dtype=torch.uint8, device=dev)
+        return b
+
+    @classmethod
     def from_reads(cls, seqs, profiles, device="cuda:0"):
         from .synth import pack_batch
         return cls(*pack_batch(seqs, profiles), device=device)
@@ -404,6 +424,84 @@ class KmerTable:
         m = check(self.L.cp_kmer_table_export(self.t, hi.ctypes.data, lo.ctypes.data, cnt.ctypes.data, n))
         assert m == n
         return hi[:n], lo[:n], cnt[:n]
+
+
+class KmerCounts:
+    """K-mer count table on the device (cp_kmer_counts_*; semantics in include/classpro_amd.h): counts every canonical
+    k-mer of the batches added, then gives the per-read count profiles and the FASTK histogram that ClassPro starts
+    from.  initial_slots only matters for tests that force growth."""
+
+    def __init__(self, K, device="cuda:0", initial_slots=0):
+        from ._lib import KmerCountStats
+        self.L = lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("classpro_amd runs on a HIP device only")
+        torch.cuda.set_device(self.device)
+        self.K = K
+        self._Stats = KmerCountStats
+        t = C.c_void_p()
+        check(self.L.cp_kmer_counts_create(K, int(initial_slots), C.byref(t)))
+        self.t = t
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "t", None):
+            self.L.cp_kmer_counts_destroy(self.t)
+            self.t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_tensors(self, seq, seq_off):
+        """Adds a batch given as device tensors in the flat layout: seq uint8, seq_off int64 [n+1]."""
+        n = seq_off.numel() - 1
+        total = int(seq_off[-1].item()) if n > 0 else 0
+        check(self.L.cp_kmer_counts_add(self.t, seq.data_ptr(), seq_off.data_ptr(), n, total, self._stream()))
+
+    def add(self, b):
+        """Adds the reads of a `Batch`."""
+        check(self.L.cp_kmer_counts_add(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.nreads, b.total_bases,
+                                        self._stream()))
+
+    def profiles(self, batch):
+        """Count profiles of a `Batch` (its `prof` tensor is filled in place, ready for Classifier.classify) or of a
+        tuple of device tensors (seq uint8, seq_off int64 [n+1]): a uint16 device tensor in the `prof` layout, read r at
+        prof_off[r] = sum of max(rlen-(K-1), 0) over the reads before it."""
+        if isinstance(batch, Batch):
+            seq, seq_off, prof_off, n, total = batch.seq, batch.seq_off, batch.prof_off, batch.nreads, batch.total_bases
+            nk, out = batch.total_kmers, batch.prof
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+            prof_off = torch.zeros(n + 1, dtype=torch.int64, device=seq_off.device)
+            torch.cumsum((seq_off[1:] - seq_off[:-1] - (self.K - 1)).clamp(min=0), 0, out=prof_off[1:])
+            nk = int(prof_off[-1].item())
+            out = torch.empty(max(nk, 8), dtype=torch.int16, device=seq_off.device)
+        check(self.L.cp_kmer_counts_profiles(self.t, seq.data_ptr(), seq_off.data_ptr(), prof_off.data_ptr(), n, total,
+                                             out.data_ptr(), self._stream()))
+        return out.view(torch.uint16)[:nk]
+
+    def hist(self):
+        """The FASTK histogram of the table as `hist_covs` and `fastk.write_fastk` take it:
+        (1, 32767, ilowcnt, ihighcnt, int64[32767])."""
+        h = np.zeros(32767, np.int64)
+        il, ih = C.c_int64(), C.c_int64()
+        check(self.L.cp_kmer_counts_hist(self.t, h.ctypes.data, C.byref(il), C.byref(ih)))
+        return 1, 32767, il.value, ih.value, h
+
+    def stats(self):
+        """dict: n_kmers, n_skipped, n_distinct, slots, bytes, growths.  Raises ClassProError (CP_EINVAL) once after a
+        profile pass that met a k-mer that was never added."""
+        s = self._Stats()
+        check(self.L.cp_kmer_counts_stats(self.t, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
 
 def _stream_of(dev):

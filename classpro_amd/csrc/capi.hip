@@ -1160,5 +1160,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // per-k-mer label table (class2cns): kmer_table.hip
 #include "kmer_table.hip"
 
+// k-mer count table, count profiles and histogram (kprof): kmer_counts.hip
+#include "kmer_counts.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

@@ -1,0 +1,386 @@
+// kmer_counts.hip -- k-mer count table on the device (kprof): how often each distinct canonical k-mer occurs in the
+// batches added, then the per-read count profiles and the FASTK histogram of those counts.  Semantics:
+// include/classpro_amd.h, "K-mer count table".  Included by capi.hip after kmer_table.hip (set_err, HIPCHK and the
+// library's error contract are shared); keys, hash, claim protocol, lookup and walk come from kt_common.h.
+//
+// One slot per key: hi, lo, a 64-bit count that cannot wrap (at most one add per base ever seen), and a pad word that
+// keeps the slot at 32 bytes: a slot then never spans two 64-byte memory requests, and a probe costs what a probe of the
+// label table costs (measured against a build without the pad word).
+//   insert     find or claim the slot, one 64-bit atomic add; a probe run past KT_PROBE sets the position's bit in a
+//              failure bitmap, the host grows the table and replays exactly those positions;
+//   profile    a read-only lookup per position; a block stages its 16384 cells in LDS and stores them as 32-bit words;
+//   histogram  a slot sweep, counts below 256 binned in LDS per block, the tail by 64-bit global atomics.
+// The per-lane tallies (claims, failures, skips, adds) are summed over the wave first: one atomic per wave and counter.
+
+#define KC_ERR_ABSENT 1u                   // a profile pass met a k-mer that was never added
+#define KC_LOW_BINS   256                  // histogram bins kept in LDS per block
+#define KC_CELLS      (KT_BLOCK*KT_CHUNK)  // k-mer positions (at most that many profile cells) per block
+
+struct kc_slot { unsigned long long hi, lo, cnt, pad; };
+static_assert(sizeof(kc_slot) == 32, "one 32-byte slot per key");
+
+struct kc_ctl                                                                 // device-side counters of one table
+  { unsigned long long n_fail;            // failed inserts of the last add / replay launch
+    unsigned long long n_occ;             // occupied slots = distinct keys
+    unsigned long long n_skip;            // k-mer positions skipped (a byte other than upper-case A C G T)
+    unsigned long long n_rfail;           // failed inserts of the last rehash
+    unsigned long long n_add;             // counted occurrences
+    unsigned int err, pad;
+  };
+
+// adds the wave's sum of v to *dst (one atomic per wave; every lane of the wave must call)
+__device__ static inline void kc_wave_add(unsigned long long *dst, unsigned long long v)
+{ for (int w = warpSize/2; w > 0; w >>= 1) v += __shfl_down(v,w);
+  if ((threadIdx.x & (warpSize-1)) == 0 && v) atomicAdd(dst,v);
+}
+
+// One add pass (REPLAY = false) or a replay of the positions whose bit is set in fail_in (REPLAY = true).
+template <bool REPLAY>
+__global__ void __launch_bounds__(KT_BLOCK) kc_add_kernel(kc_slot *tab, unsigned long long mask, const char *seq,
+                                                          const int64_t *seq_off, int nreads, int64_t total, int K,
+                                                          const unsigned int *fail_in, unsigned int *fail_out,
+                                                          kc_ctl *ctl)
+{ const int64_t p0 = ((int64_t)blockIdx.x*blockDim.x+threadIdx.x)*KT_CHUNK;
+  unsigned long long nfail = 0, nocc = 0, nadd = 0, nskip = 0;
+  if (p0 < total)
+    nskip = kt_walk<true>(seq,seq_off,nreads,total,K,p0,
+      [&](int64_t j, unsigned long long hi, unsigned long long lo)
+      { if (REPLAY && !((fail_in[j >> 5] >> (j & 31)) & 1u)) return;
+        bool claimed = false;
+        kc_slot *e = kt_find_or_claim(tab,mask,hi,lo,&claimed);
+        nocc += claimed;
+        if (!e)
+          { atomicOr(&fail_out[j >> 5],1u << (j & 31));
+            nfail++;
+            return;
+          }
+        atomicAdd(&e->cnt,1ull);
+        nadd++;
+      });
+  kc_wave_add(&ctl->n_fail,nfail);
+  kc_wave_add(&ctl->n_occ,nocc);
+  kc_wave_add(&ctl->n_add,nadd);
+  if (!REPLAY) kc_wave_add(&ctl->n_skip,nskip);
+}
+
+__global__ void __launch_bounds__(KT_BLOCK) kc_fill_kernel(kc_slot *tab, unsigned long long n)
+{ for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { kc_slot e = {};
+      e.hi = e.lo = KT_EMPTY;
+      tab[s] = e;
+    }
+}
+
+// every occupied slot of `old` into `tab` (distinct keys: each lane claims a slot of its own, then stores its count)
+__global__ void __launch_bounds__(KT_BLOCK) kc_rehash_kernel(const kc_slot *old, unsigned long long n_old, kc_slot *tab,
+                                                             unsigned long long mask, kc_ctl *ctl)
+{ unsigned long long nfail = 0;
+  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n_old;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kc_slot o = old[s];
+      if (o.lo == KT_EMPTY) continue;
+      bool claimed = false;
+      kc_slot *e = kt_find_or_claim(tab,mask,o.hi,o.lo,&claimed);
+      if (!e || !claimed) { nfail++; continue; }
+      e->cnt = o.cnt;
+    }
+  if (nfail) atomicAdd(&ctl->n_rfail,nfail);
+}
+
+// The prof cell of the k-mer position j of read r is prof_off[r] + j - seq_off[r] - (K-1).  Cells follow the k-mer
+// positions in order, so the cells of a block's KC_CELLS positions are one contiguous run [q0, q0+n): staged in LDS,
+// then stored by the whole block, two cells per lane and store.
+__global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab, unsigned long long mask,
+                                                              const char *seq, const int64_t *seq_off,
+                                                              const int64_t *prof_off, int nreads, int64_t total, int K,
+                                                              uint16_t *prof, kc_ctl *ctl)
+{ __shared__ uint16_t cell[KC_CELLS];
+  __shared__ int64_t run[2];
+  const int64_t b0 = (int64_t)blockIdx.x*KC_CELLS, b1 = min(b0+(int64_t)KC_CELLS,total);
+  if (threadIdx.x < 2)                                   // first cell at or after position b0 / b1
+    { const int64_t p = threadIdx.x ? b1 : b0;
+      int lo_r = 0, hi_r = nreads;
+      while (hi_r-lo_r > 1)
+        { const int mid = (lo_r+hi_r) >> 1;
+          if (seq_off[mid] <= p) lo_r = mid; else hi_r = mid;
+        }
+      const int64_t in = p-seq_off[lo_r]-(K-1), len = prof_off[lo_r+1]-prof_off[lo_r];
+      run[threadIdx.x] = p >= total ? prof_off[nreads] : prof_off[lo_r]+min(max(in,(int64_t)0),len);
+    }
+  __syncthreads();
+  const int64_t q0 = run[0];
+  const int64_t n = min(max(run[1]-q0,(int64_t)0),min((int64_t)KC_CELLS,prof_off[nreads]-q0));
+  const int64_t p0 = b0+(int64_t)threadIdx.x*KT_CHUNK;
+  unsigned int err = 0;
+  int cur = -1;                                          // the read whose cell base is held
+  int64_t base = 0;
+  if (p0 < total)
+    kt_walk_all<true>(seq,seq_off,nreads,total,K,p0,
+      [&](int r, int64_t j, bool ok, unsigned long long hi, unsigned long long lo)
+      { if (r != cur) { cur = r; base = prof_off[r]-seq_off[r]-(K-1)-q0; }
+        unsigned long long c = 0;
+        if (ok)
+          { const kc_slot *e = kt_lookup(tab,mask,hi,lo);
+            if (e) c = min(e->cnt,(unsigned long long)CP_MAX_KMER_CNT);
+            else err |= KC_ERR_ABSENT;                   // a k-mer that was never added: the caller's error
+          }
+        const int64_t i = base+j;
+        if ((unsigned long long)i < (unsigned long long)n) cell[i] = (uint16_t)c;
+      });
+  if (err) atomicOr(&ctl->err,err);
+  __syncthreads();
+  if (n <= 0) return;
+  uint16_t *dst = prof+q0;
+  const int head = (int)(((uintptr_t)dst >> 1) & 1);     // cells before the first 4-byte boundary
+  const int64_t npair = (n-head) >> 1;
+  if (threadIdx.x == 0)
+    { if (head) dst[0] = cell[0];
+      if ((n-head) & 1) dst[n-1] = cell[n-1];
+    }
+  for (int64_t i = threadIdx.x; i < npair; i += KT_BLOCK)
+    *(unsigned int *)(dst+head+2*i) = (unsigned int)cell[head+2*i] | ((unsigned int)cell[head+2*i+1] << 16);
+}
+
+// hist[c-1] += distinct keys with count c (c < 32767), hist[32766] += those with >= 32767, hist[32767] += the
+// occurrences of the latter (ihighcnt)
+__global__ void __launch_bounds__(KT_BLOCK) kc_hist_kernel(const kc_slot *tab, unsigned long long n,
+                                                           unsigned long long *hist)
+{ __shared__ unsigned int low[KC_LOW_BINS];
+  for (int i = threadIdx.x; i < KC_LOW_BINS; i += KT_BLOCK) low[i] = 0;
+  __syncthreads();
+  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kc_slot e = tab[s];
+      if (e.lo == KT_EMPTY || e.cnt == 0) continue;
+      if (e.cnt <= KC_LOW_BINS) atomicAdd(&low[e.cnt-1],1u);
+      else if (e.cnt < CP_MAX_KMER_CNT) atomicAdd(&hist[e.cnt-1],1ull);
+      else
+        { atomicAdd(&hist[CP_MAX_KMER_CNT-1],1ull);
+          atomicAdd(&hist[CP_MAX_KMER_CNT],e.cnt);
+        }
+    }
+  __syncthreads();
+  for (int i = threadIdx.x; i < KC_LOW_BINS; i += KT_BLOCK)
+    if (low[i]) atomicAdd(&hist[i],(unsigned long long)low[i]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+
+struct cp_kmer_counts
+  { int K, device;
+    kc_slot *tab;
+    unsigned long long slots;
+    kc_ctl *ctl;                         // device
+    kc_ctl *h_ctl;                       // pinned host copy
+    unsigned int *fail[2];               // failure bitmaps, 1 bit per base position of a batch
+    size_t fail_words;
+    int64_t growths;
+    bool unsized;                        // created with initial_slots = 0 and nothing added yet: the first add sizes it
+    hipStream_t stream;                  // stream of the last call that queued work
+  };
+
+static int kc_alloc_table(kc_slot **out, unsigned long long slots, hipStream_t st)
+{ void *p = nullptr;
+  hipError_t e = hipMalloc(&p,(size_t)slots*sizeof(kc_slot));
+  if (e != hipSuccess)
+    { (void)hipGetLastError();
+      char m[160];
+      snprintf(m,sizeof(m),"cp_kmer_counts: hipMalloc(%llu slots, %llu bytes): %s",slots,
+               (unsigned long long)(slots*sizeof(kc_slot)),hipGetErrorString(e));
+      return set_err(CP_ENOMEM,m);
+    }
+  kc_fill_kernel<<<kt_grid(slots),KT_BLOCK,0,st>>>((kc_slot *)p,slots);
+  *out = (kc_slot *)p;
+  return CP_OK;
+}
+
+static int kc_sync_ctl(cp_kmer_counts *t, hipStream_t st)
+{ HIPCHK(hipMemcpyAsync(t->h_ctl,t->ctl,sizeof(kc_ctl),hipMemcpyDeviceToHost,st));
+  HIPCHK(hipStreamSynchronize(st));
+  return CP_OK;
+}
+
+// rehash into a table of at least `want` slots (a power of two, > slots); the old table stays intact on failure
+static int kc_grow(cp_kmer_counts *t, unsigned long long want, hipStream_t st)
+{ for (int attempt = 0; attempt < 4; attempt++, want <<= 1)
+    { kc_slot *nt = nullptr;
+      int rc = kc_alloc_table(&nt,want,st);
+      if (rc != CP_OK) return rc;
+      HIPCHK(hipMemsetAsync(&t->ctl->n_rfail,0,sizeof(unsigned long long),st));
+      kc_rehash_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,nt,want-1,t->ctl);
+      HIPCHK(hipGetLastError());
+      rc = kc_sync_ctl(t,st);
+      if (rc != CP_OK) { (void)hipFree(nt); return rc; }
+      if (t->h_ctl->n_rfail == 0)
+        { HIPCHK(hipFree(t->tab));
+          t->tab = nt;
+          t->slots = want;
+          t->growths++;
+          return CP_OK;
+        }
+      HIPCHK(hipFree(nt));                                 // a probe run too long in the new table: larger still
+    }
+  return set_err(CP_ENOMEM,"cp_kmer_counts: rehash kept failing its probe bound");
+}
+
+extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_counts **out)
+{ if (!out) return set_err(CP_EINVAL,"cp_kmer_counts_create: null out");
+  *out = nullptr;
+  if (K < 2 || K > 63)
+    return set_err(CP_EINVAL,"cp_kmer_counts_create: K must lie in [2, 63] (a key holds 2K <= 126 bits)");
+  if (initial_slots < 0 || initial_slots > ((int64_t)1 << 40))
+    return set_err(CP_EINVAL,"cp_kmer_counts_create: bad initial_slots");
+  cp_kmer_counts *t = new (std::nothrow) cp_kmer_counts();
+  if (!t) return set_err(CP_ENOMEM,"cp_kmer_counts_create: out of memory");
+  t->K = K;
+  t->unsized = initial_slots == 0;
+  t->slots = kt_pow2_at_least(initial_slots > 0 ? (unsigned long long)initial_slots : (1ull << 20));
+  hipError_t e = hipGetDevice(&t->device);
+  if (e == hipSuccess) e = hipMalloc(&t->ctl,sizeof(kc_ctl));
+  if (e == hipSuccess) e = hipHostMalloc(&t->h_ctl,sizeof(kc_ctl),hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemset(t->ctl,0,sizeof(kc_ctl));
+  int rc = CP_OK;
+  if (e == hipSuccess)
+    { rc = kc_alloc_table(&t->tab,t->slots,nullptr);
+      if (rc == CP_OK) e = hipStreamSynchronize(nullptr);
+    }
+  if (e != hipSuccess || rc != CP_OK)
+    { if (e != hipSuccess) rc = set_err(CP_EHIP,std::string("cp_kmer_counts_create: ")+hipGetErrorString(e));
+      cp_kmer_counts_destroy(t);
+      return rc;
+    }
+  *out = t;
+  return CP_OK;
+}
+
+extern "C" void cp_kmer_counts_destroy(cp_kmer_counts *t)
+{ if (!t) return;
+  (void)hipDeviceSynchronize();
+  if (t->tab) (void)hipFree(t->tab);
+  if (t->ctl) (void)hipFree(t->ctl);
+  if (t->h_ctl) (void)hipHostFree(t->h_ctl);
+  for (int i = 0; i < 2; i++)
+    if (t->fail[i]) (void)hipFree(t->fail[i]);
+  delete t;
+}
+
+extern "C" int cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                                  int64_t total_bases, void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_counts_add: bad argument");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_add: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  t->stream = st;
+  const size_t words = (size_t)((total_bases+31)/32);
+  if (words > t->fail_words)
+    { HIPCHK(hipStreamSynchronize(st));
+      for (int i = 0; i < 2; i++)
+        { if (t->fail[i]) { (void)hipFree(t->fail[i]); t->fail[i] = nullptr; }
+          if (hipMalloc(&t->fail[i],words*4) != hipSuccess)
+            { (void)hipGetLastError();
+              t->fail_words = 0;
+              return set_err(CP_ENOMEM,"cp_kmer_counts_add: cannot allocate the failure bitmap");
+            }
+        }
+      t->fail_words = words;
+    }
+  if (t->unsized)
+    { // The first batch into a table of the default size: room for every k-mer of the batch at half load, so that it
+      // does not run through a table it cannot fit into (each failed insert costs KT_PROBE probes and a replay).  The
+      // table is empty, so there is nothing to rehash; when the allocation fails the usual growth takes over.
+      t->unsized = false;
+      const unsigned long long want = kt_pow2_at_least(2*(unsigned long long)total_bases);
+      kc_slot *nt = nullptr;
+      if (want > t->slots && kc_alloc_table(&nt,want,st) == CP_OK)
+        { HIPCHK(hipStreamSynchronize(st));
+          HIPCHK(hipFree(t->tab));
+          t->tab = nt;
+          t->slots = want;
+        }
+    }
+  const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
+  HIPCHK(hipMemsetAsync(t->fail[0],0,words*4,st));
+  HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
+  kc_add_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,nullptr,
+                                               t->fail[0],t->ctl);
+  HIPCHK(hipGetLastError());
+  // the one read-back: failed inserts and occupancy.  Failures: grow, replay only them; then keep the load <= 1/2.
+  for (int round = 0; ; round++)
+    { int rc = kc_sync_ctl(t,st);
+      if (rc != CP_OK) return rc;
+      const unsigned long long nfail = t->h_ctl->n_fail, nocc = t->h_ctl->n_occ;
+      if (nfail == 0 && 2*nocc <= t->slots) return CP_OK;
+      if (round >= 16) return set_err(CP_ENOMEM,"cp_kmer_counts_add: the table did not settle after 16 growth steps");
+      rc = kc_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+nfail))),st);
+      if (rc != CP_OK) return rc;
+      if (nfail == 0) continue;
+      HIPCHK(hipMemsetAsync(t->fail[1],0,words*4,st));
+      HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
+      kc_add_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,t->fail[0],
+                                                  t->fail[1],t->ctl);
+      HIPCHK(hipGetLastError());
+      std::swap(t->fail[0],t->fail[1]);
+    }
+}
+
+extern "C" int cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off,
+                                       const int64_t *d_prof_off, int nreads, int64_t total_bases, uint16_t *d_prof,
+                                       void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_counts_profiles: bad argument");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off || !d_prof_off || !d_prof)
+    return set_err(CP_EINVAL,"cp_kmer_counts_profiles: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  t->stream = st;
+  const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
+  kc_profile_kernel<<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,nreads,total_bases,t->K,d_prof,
+                                            t->ctl);
+  HIPCHK(hipGetLastError());
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt)
+{ if (!t || !hist || !ilowcnt || !ihighcnt) return set_err(CP_EINVAL,"cp_kmer_counts_hist: bad argument");
+  hipStream_t st = t->stream;
+  const size_t bytes = sizeof(unsigned long long)*(CP_MAX_KMER_CNT+1);
+  unsigned long long *d_hist = nullptr;
+  if (hipMalloc(&d_hist,bytes) != hipSuccess)
+    { (void)hipGetLastError();
+      return set_err(CP_ENOMEM,"cp_kmer_counts_hist: cannot allocate the device histogram");
+    }
+  std::vector<unsigned long long> h((size_t)CP_MAX_KMER_CNT+1);
+  hipError_t e = hipMemsetAsync(d_hist,0,bytes,st);
+  if (e == hipSuccess)
+    { kc_hist_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,d_hist);
+      e = hipGetLastError();
+    }
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(),d_hist,bytes,hipMemcpyDeviceToHost,st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_hist);
+  if (e != hipSuccess) return set_err(CP_EHIP,std::string("cp_kmer_counts_hist: ")+hipGetErrorString(e));
+  for (int c = 0; c < CP_MAX_KMER_CNT; c++) hist[c] = (int64_t)h[(size_t)c];
+  *ilowcnt = (int64_t)h[0];
+  *ihighcnt = (int64_t)h[(size_t)CP_MAX_KMER_CNT];
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out)
+{ if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_counts_stats: bad argument");
+  hipStream_t st = t->stream;
+  int rc = kc_sync_ctl(t,st);
+  if (rc != CP_OK) return rc;
+  if (t->h_ctl->err)                                       // deferred device errors: reported once, then cleared
+    { HIPCHK(hipMemsetAsync(&t->ctl->err,0,sizeof(unsigned int),st));
+      HIPCHK(hipStreamSynchronize(st));
+      return set_err(CP_EINVAL,"cp_kmer_counts: a profile pass met a k-mer that was never added (its cell is 0)");
+    }
+  out->n_kmers = (int64_t)t->h_ctl->n_add;
+  out->n_skipped = (int64_t)t->h_ctl->n_skip;
+  out->n_distinct = (int64_t)t->h_ctl->n_occ;
+  out->slots = (int64_t)t->slots;
+  out->bytes = (int64_t)(t->slots*sizeof(kc_slot)+2*t->fail_words*4);
+  out->growths = t->growths;
+  return CP_OK;
+}

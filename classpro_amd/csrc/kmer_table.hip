@@ -4,21 +4,12 @@
 // HIPCHK and the library's error contract are shared).
 //
 // The table is open addressing with linear probing, one 32-byte slot per key: hi = key bits 125..63, lo = key bits
-// 62..0, four u32 counts.  A key has at most 126 bits, so the all-ones word never is a half of a key and marks an
-// EMPTY half.  An insert never waits on another lane: it CASes hi from EMPTY (or finds it equal), then lo from EMPTY
-// (or finds it equal), and adds one count; a slot's (hi, lo) once set never changes, so every insert of one key stops
-// at the same slot (the first one of its probe sequence whose final key is that key).  Probing is bounded
-// (KT_PROBE); an insert that runs past the bound sets its position's bit in a failure bitmap and adds nothing.  The
-// host then grows the table (rehash into at least twice the slots) and replays exactly the failed positions.
-#include <algorithm>
+// 62..0, four u32 counts.  Keys, the hash, the claim protocol, the lookup and the walk over a batch's k-mers are shared
+// with the count table (kmer_counts.hip): kt_common.h.  An insert finds or claims its key's slot and adds one count; one
+// that runs past the probe bound (KT_PROBE) sets its position's bit in a failure bitmap and adds nothing.  The host then
+// grows the table (rehash into at least twice the slots) and replays exactly the failed positions.
+#include "kt_common.h"
 
-typedef unsigned __int128 kt_u128;
-
-#define KT_EMPTY  0xFFFFFFFFFFFFFFFFull
-#define KT_M63    0x7FFFFFFFFFFFFFFFull
-#define KT_PROBE  64                       // slots looked at per insert / lookup before an insert counts as failed
-#define KT_CHUNK  64                       // consecutive k-mer positions one lane rolls its key over
-#define KT_BLOCK  256
 #define KT_ERR_LABEL    1u                 // a counted position held a label other than E/H/D/R
 #define KT_ERR_OVERFLOW 2u                 // a count passed 2^32-1
 
@@ -37,19 +28,6 @@ struct kt_ctl                                                                 //
 struct kt_part                                                                // one block's share of the statistics
   { unsigned long long n_distinct, n_unanimous, label_total[4], cns_total[4], s_hi, s_lo; };
 
-__host__ __device__ static inline unsigned long long kt_mix(unsigned long long x)
-{ x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-
-__device__ static inline unsigned long long kt_home(unsigned long long hi, unsigned long long lo)
-{ return kt_mix(lo ^ kt_mix(hi ^ 0x9e3779b97f4a7c15ull)); }
-
-__device__ static inline int kt_base(unsigned char c)                        // A C G T -> 0..3, anything else -1
-{ return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
-
 __device__ static inline int kt_label(unsigned char c)                       // E H D R -> 0..3, anything else -1
 { return c == 'E' ? 0 : c == 'H' ? 1 : c == 'D' ? 2 : c == 'R' ? 3 : -1; }
 
@@ -59,88 +37,6 @@ __host__ __device__ static inline int kt_consensus(const unsigned int *c)
   for (int l = 1; l < 4; l++)
     if (c[l] >= c[best]) best = l;
   return best;
-}
-
-__device__ static inline unsigned long long kt_load(const unsigned long long *p)
-{ return __hip_atomic_load(p,__ATOMIC_RELAXED,__HIP_MEMORY_SCOPE_AGENT); }
-
-// Finds or claims the slot of (hi, lo); returns it, or NULL after KT_PROBE slots.  *claimed: this lane set lo.
-__device__ static inline kt_slot *kt_find_or_claim(kt_slot *tab, unsigned long long mask, unsigned long long hi,
-                                                   unsigned long long lo, bool *claimed)
-{ unsigned long long s = kt_home(hi,lo) & mask;
-  for (int p = 0; p < KT_PROBE; p++, s = (s+1) & mask)
-    { kt_slot *e = tab+s;
-      unsigned long long h = kt_load(&e->hi);
-      if (h == KT_EMPTY)
-        { const unsigned long long o = atomicCAS(&e->hi,KT_EMPTY,hi);
-          h = (o == KT_EMPTY) ? hi : o;
-        }
-      if (h != hi) continue;
-      unsigned long long w = kt_load(&e->lo);
-      if (w == KT_EMPTY)
-        { const unsigned long long o = atomicCAS(&e->lo,KT_EMPTY,lo);
-          if (o == KT_EMPTY) { w = lo; *claimed = true; }
-          else w = o;
-        }
-      if (w == lo) return e;
-    }
-  return nullptr;
-}
-
-// Read-only lookup (the table is not written while it runs).
-__device__ static inline const kt_slot *kt_lookup(const kt_slot *tab, unsigned long long mask, unsigned long long hi,
-                                                  unsigned long long lo)
-{ unsigned long long s = kt_home(hi,lo) & mask;
-  for (int p = 0; p < KT_PROBE; p++, s = (s+1) & mask)
-    { const kt_slot *e = tab+s;
-      const unsigned long long h = e->hi;
-      if (h == KT_EMPTY) return nullptr;
-      if (h == hi && e->lo == lo) return e;
-    }
-  return nullptr;
-}
-
-// Walks the k-mer positions [p0, p0+KT_CHUNK) of the flat batch (global base index j, k-mer = seq[j-K+1..j] of j's
-// read, j >= read start + K-1), rolling the forward key and its reverse complement one base at a time.  Calls
-// f(j, hi, lo) for every k-mer of upper-case A C G T only; returns the number of the others.
-template <bool CANON, class F>
-__device__ static inline unsigned long long kt_walk(const char *seq, const int64_t *seq_off, int nreads, int64_t total,
-                                                    int K, int64_t p0, F f)
-{ const int64_t p1 = min(p0+(int64_t)KT_CHUNK,total);
-  int lo_r = 0, hi_r = nreads;                          // the read holding p0: seq_off[r] <= p0 < seq_off[r+1]
-  while (hi_r-lo_r > 1)
-    { const int mid = (lo_r+hi_r) >> 1;
-      if (seq_off[mid] <= p0) lo_r = mid; else hi_r = mid;
-    }
-  const kt_u128 kmask = (((kt_u128)1) << (2*K))-1;
-  const int rshift = 2*K-2;
-  unsigned long long nskip = 0;
-  int r = lo_r;
-  for (int64_t p = p0; p < p1 && r < nreads; r++)
-    { const int64_t rs = seq_off[r], re = seq_off[r+1];
-      if (re <= p) continue;                            // empty reads
-      const int64_t q1 = min(p1,re);
-      const int64_t first = max(p,rs+K-1);
-      if (first < q1)
-        { kt_u128 fw = 0, rc = 0;
-          int valid = 0;
-          for (int64_t j = first-K+1; j < q1; j++)
-            { const int b = kt_base((unsigned char)seq[j]);
-              if (b < 0) { valid = 0; fw = 0; rc = 0; }
-              else
-                { fw = ((fw << 2) | (kt_u128)b) & kmask;
-                  rc = (rc >> 2) | (((kt_u128)(3-b)) << rshift);
-                  valid++;
-                }
-              if (j < first) continue;
-              if (valid < K) { nskip++; continue; }
-              const kt_u128 key = (CANON && rc < fw) ? rc : fw;
-              f(j,(unsigned long long)(key >> 63),(unsigned long long)key & KT_M63);
-            }
-        }
-      p = q1;
-    }
-  return nskip;
 }
 
 // One add pass (REPLAY = false) or a replay of the positions whose bit is set in fail_in (REPLAY = true).
@@ -286,9 +182,6 @@ struct cp_kmer_table
     hipStream_t stream;                  // stream of the last call that queued work
   };
 
-static int kt_grid(unsigned long long n)
-{ return (int)std::min<unsigned long long>((n+KT_BLOCK-1)/KT_BLOCK,8192); }
-
 static int kt_alloc_table(kt_slot **out, unsigned long long slots, hipStream_t st)
 { void *p = nullptr;
   hipError_t e = hipMalloc(&p,(size_t)slots*sizeof(kt_slot));
@@ -331,12 +224,6 @@ static int kt_grow(cp_kmer_table *t, unsigned long long want, hipStream_t st)
       HIPCHK(hipFree(nt));                                 // a probe run too long in the new table: larger still
     }
   return set_err(CP_ENOMEM,"cp_kmer_table: rehash kept failing its probe bound");
-}
-
-static unsigned long long kt_pow2_at_least(unsigned long long n)
-{ unsigned long long s = 64;
-  while (s < n) s <<= 1;
-  return s;
 }
 
 extern "C" int cp_kmer_table_create(int K, int canonical, int64_t initial_slots, cp_kmer_table **out)

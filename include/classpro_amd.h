@@ -315,6 +315,62 @@ int  cp_kmer_table_consensus(cp_kmer_table *t, const char *d_seq, const int64_t 
 int64_t cp_kmer_table_export(cp_kmer_table *t, uint64_t *hi, uint64_t *lo, uint32_t *counts4, int64_t capacity);
 
 /* ------------------------------------------------------------------------------------------
+ * K-mer count table (kprof): how often each distinct k-mer occurs in a read set, then the per-read count profiles and
+ * the histogram that `FastK -k<K> -t1 -p` leaves for ClassPro, counted on the device.  Three passes: add every batch,
+ * then profile every batch, and sweep the table once for the histogram.
+ *
+ *   Key          always canonical: min(forward, reverse complement), 2 bits per base, as FastK counts; the same key as
+ *                cp_kmer_table with canonical = 1.  A k-mer that is its own reverse complement counts once per
+ *                occurrence.  2 <= K <= 63; any other K is CP_EINVAL.
+ *   Occurrences  the k-mer ending at read position i, for i in [K-1, rlen).  Reads shorter than K contribute nothing
+ *                and their span of prof_off is empty: prof_off[r+1] - prof_off[r] = max(rlen_r - (K-1), 0).
+ *   Count        the number of occurrences over everything added so far, exact: the counter has 64 bits and cannot
+ *                wrap.  Only what is given out is clamped to CP_MAX_KMER_CNT, so a profile holds counts in [0, 32767]
+ *                as cp_decode_profiles leaves them.
+ *   Other bytes  a k-mer holding a byte other than upper-case A C G T is not counted; its profile cell is 0 and it is
+ *                tallied in n_skipped (the rule of cp_kmer_table).  FastK's own treatment of such bases is not part
+ *                of the reference tree and is not reproduced.
+ *   Absent       a profile pass over a k-mer that is not in the table (a batch that was never added) writes 0 and
+ *                makes the next cp_kmer_counts_stats return CP_EINVAL, once (the contract of cp_kmer_table_consensus);
+ *                the table stays usable.
+ *   Histogram    low = 1, high = 32767: hist[c-1] = distinct keys with exactly c occurrences for c < 32767,
+ *                hist[32766] = distinct keys with >= 32767; ilowcnt = the occurrences of the keys with count <= 1
+ *                (= hist[0]); ihighcnt = the occurrences of the keys with count >= 32767.  The two are what
+ *                Load_Histogram / Modify_Histogram (libfastk.c:92-93, 116-123) keep in the hidden cells to switch
+ *                between distinct k-mers and occurrences.
+ * All sums are integers: profiles, histogram and statistics do not depend on the batching or the read order.
+ *
+ * The table grows as cp_kmer_table does: inserts past the probe bound are replayed after a rehash into at least twice
+ * the slots, and it also grows past half load.  With initial_slots = 0 the first batch added sizes the still empty
+ * table for all its k-mers at half load (nothing to rehash, not a growth step); a positive initial_slots is taken as
+ * it is and exists so that tests can force growth.  A growth step that cannot allocate returns CP_ENOMEM and leaves
+ * the table as it was.  One GPU per table; offsets are 64-bit throughout.
+ */
+typedef struct cp_kmer_counts cp_kmer_counts;
+typedef struct
+  { int64_t n_kmers;               /* counted occurrences */
+    int64_t n_skipped;             /* occurrences skipped: a byte other than upper-case A C G T */
+    int64_t n_distinct;            /* distinct keys */
+    int64_t slots, bytes;          /* table slots now; device bytes held (slots + failure bitmaps) */
+    int64_t growths;               /* growth steps so far */
+  } cp_kmer_count_stats;
+int  cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_counts **out);
+void cp_kmer_counts_destroy(cp_kmer_counts *t);
+/* Pass 1: counts every k-mer occurrence of a batch (flat layout; neither labels nor profiles are needed).  Asynchronous
+ * on `stream` except for one read-back of the failed-insert and occupancy counters (and the growth, when it grows). */
+int  cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                        int64_t total_bases, void *stream);
+/* Pass 2: d_prof[d_prof_off[r] + i] = min(count of the k-mer at positions [i, i+K) of read r, 32767).  Asynchronous on
+ * `stream`. */
+int  cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off,
+                             const int64_t *d_prof_off, int nreads, int64_t total_bases, uint16_t *d_prof,
+                             void *stream);
+/* The FASTK histogram of the table into a host array of 32767 (see Histogram).  Synchronises. */
+int  cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt);
+/* Synchronises; reports a deferred device error (CP_EINVAL, see Absent) first. */
+int  cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
