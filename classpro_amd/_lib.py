@@ -20,7 +20,7 @@ SYMBOLS = [
     "cp_kmer_table_create", "cp_kmer_table_destroy", "cp_kmer_table_add", "cp_kmer_table_stats",
     "cp_kmer_table_consensus", "cp_kmer_table_export",
     "cp_kmer_counts_create", "cp_kmer_counts_destroy", "cp_kmer_counts_add", "cp_kmer_counts_profiles",
-    "cp_kmer_counts_hist", "cp_kmer_counts_stats",
+    "cp_kmer_counts_hist", "cp_kmer_counts_stats", "cp_kmer_counts_rel_labels",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -130,6 +130,7 @@ def lib():
     L.cp_kmer_counts_profiles.argtypes = [vp, vp, vp, vp, i32, i64, vp, vp]
     L.cp_kmer_counts_hist.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.cp_kmer_counts_stats.argtypes = [vp, C.POINTER(KmerCountStats)]
+    L.cp_kmer_counts_rel_labels.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

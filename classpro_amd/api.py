@@ -488,6 +488,51 @@ class KmerCounts:
                                              out.data_ptr(), self._stream()))
         return out.view(torch.uint16)[:nk]
 
+    def rel_labels(self, batch, packed=False, profiles=False, counts=None):
+        """cp_kmer_counts_rel_labels: the labels of a batch of ANOTHER sequence set against this table, the count c of
+        each k-mer giving E (0: absent, or a byte other than upper-case A C G T), H (1), D (2) or R (>= 3) after
+        min(K-1, rlen) 'N' per read.  `batch` is a `Batch` or a tuple of device tensors (seq uint8, seq_off int64
+        [n+1]).  Returns (labels, counts), or (labels, prof, counts) with profiles=True: labels a uint8 device tensor of
+        seq_off[n] characters that `LabelAccuracy.add` takes as it is -- or, with packed=True, the 2-bit bytes of
+        cp_pack_labels and their int64 offsets as (packed, pack_off); prof the relative profile, min(c, 32767) as uint16
+        in the `prof` layout (a `Batch`'s own `prof` tensor is filled in place, as `profiles()` does); counts an int64
+        device tensor [4], order E, H, D, R.  Pass a previous `counts` tensor to go on adding to it.  The table is not
+        changed and an absent k-mer is no error.  Nothing is copied to the host."""
+        if isinstance(batch, Batch):
+            seq, seq_off, n, total = batch.seq, batch.seq_off, batch.nreads, batch.total_bases
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+        dev = seq_off.device
+        prof = prof_off = None
+        nk = 0
+        if profiles:
+            if isinstance(batch, Batch):
+                prof, prof_off, nk = batch.prof, batch.prof_off, batch.total_kmers
+            else:
+                prof_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+                torch.cumsum((seq_off[1:] - seq_off[:-1] - (self.K - 1)).clamp(min=0), 0, out=prof_off[1:])
+                nk = int(prof_off[-1].item()) if n > 0 else 0
+                prof = torch.empty(max(nk, 8), dtype=torch.int16, device=dev)
+        if counts is None:
+            counts = torch.zeros(4, dtype=torch.int64, device=dev)
+        lab = pk = pack_off = None
+        if packed:
+            pack_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            torch.cumsum((seq_off[1:] - seq_off[:-1] + 3) >> 2, 0, out=pack_off[1:])
+            pk = torch.empty(max(int(pack_off[-1].item()) if n > 0 else 0, 1), dtype=torch.uint8, device=dev)
+        else:
+            lab = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        check(self.L.cp_kmer_counts_rel_labels(self.t, seq.data_ptr(), seq_off.data_ptr(), n, total, ptr(prof),
+                                               ptr(prof_off), ptr(lab), ptr(pk), ptr(pack_off), counts.data_ptr(),
+                                               self._stream()))
+        out = (pk, pack_off) if packed else lab[:total]
+        if profiles:
+            return out, prof.view(torch.uint16)[:nk], counts
+        return out, counts
+
     def hist(self):
         """The FASTK histogram of the table as `hist_covs` and `fastk.write_fastk` take it:
         (1, 32767, ilowcnt, ihighcnt, int64[32767])."""

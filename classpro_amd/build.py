@@ -14,6 +14,7 @@ CLI = os.path.join(_HERE, "ClassPro")          # drop-in command line (csrc/host
 CNS = os.path.join(_HERE, "class2cns")         # per-k-mer label consensus (csrc/host/class2cns.cpp; its flags use the GPU)
 GS = os.path.join(_HERE, "ClassGS")             # global-threshold labels and their accuracy (csrc/host/classgs.cpp; uses the GPU)
 KPROF = os.path.join(_HERE, "kprof")           # count profiles and histogram from reads (csrc/host/kprof.cpp; uses the GPU)
+G2C = os.path.join(_HERE, "genome2class")      # ground-truth labels from a genome (csrc/host/genome2class.cpp; uses the GPU)
 TOOLS = {"prof2class": "prof2class.cpp", "class2acc": "class2acc.cpp"}   # host-only evaluation tools
 # -ffp-contract=off: the decision path compares doubles against thresholds and truncates them to
 # ints (class_rel.c:449,483); fused multiply-adds would change those values.
@@ -54,7 +55,7 @@ def _run(cmd, verbose):
 
 def build(force=False, verbose=False):
     # the HIP objects: library, command line, synthetic-set generator
-    outs, side, key = [OUT, CLI, CNS, GS, KPROF, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
+    outs, side, key = [OUT, CLI, CNS, GS, KPROF, G2C, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
     if not _fresh(outs, side, key, force):
         if os.path.exists(side):
             os.remove(side)
@@ -67,6 +68,8 @@ def build(force=False, verbose=False):
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "classgs.cpp"), "-o", GS,
               "-L" + _HERE, "-lclasspro_amd", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "kprof.cpp"), "-o", KPROF,
+              "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "genome2class.cpp"), "-o", G2C,
               "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
               os.path.join(CSRC, "synth", "synth_gen.hip"), "-o", SYNTH], verbose)

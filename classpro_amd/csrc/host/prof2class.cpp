@@ -9,6 +9,7 @@
 #include <unistd.h>
 #include "host_io.h"
 #include "dazz_db.h"
+#include "class_record.h"
 #include "../cp_host_setup.h"
 
 static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
@@ -54,7 +55,7 @@ int main(int argc, char **argv)
   std::vector<char> obuf(1 << 22);
   setvbuf(out,obuf.data(),_IOFBF,obuf.size());
 
-  const int Km1 = P.kmer-1, rlen_max = is_db ? db.maxlen : 60000;          // prof2class.c:154-160
+  const int Km1 = P.kmer-1, rlen_max = is_db ? db.maxlen : CLASS_FASTX_RLEN_MAX;          // prof2class.c:154-160
   std::vector<uint16_t> profile(60001);
   std::string asgn, header;
   for (int64_t id = 0; id < P.nreads; id++)
@@ -67,7 +68,7 @@ int main(int argc, char **argv)
       else
         { rlen = fx.next();
           if (rlen < 0) { rlen = 0; fx.seq.clear(); }                      // the reference does not check kseq_read here
-          header = "@"+fx.name+" "+(fx.have_comment ? fx.comment : std::string("(null)"));
+          header = fastx_class_header(fx);
         }
       if (rlen > rlen_max)
         die("rlen (%d) > rlen_max (%d)\n",rlen,rlen_max);
@@ -78,9 +79,6 @@ int main(int argc, char **argv)
         { profile.resize((size_t)plen);
           cp_host_decode_profile(code,clen,profile.data(),plen);
         }
-      fputs(header.c_str(),out); fputc('\n',out);
-      fwrite(fx.seq.data(),1,fx.seq.size(),out);
-      fputs("\n+\n",out);
       if (rlen <= Km1)                                                     // prof2class.c:203-208
         asgn.assign((size_t)rlen,'N');
       else
@@ -90,8 +88,7 @@ int main(int argc, char **argv)
               asgn.push_back(c == 0 ? 'E' : c == 1 ? 'H' : c == 2 ? 'D' : 'R');
             }
         }
-      fwrite(asgn.data(),1,asgn.size(),out);
-      fputc('\n',out);
+      write_class_record(out,header,fx.seq.data(),fx.seq.size(),asgn.data(),asgn.size());
     }
   fclose(out);
   return 0;

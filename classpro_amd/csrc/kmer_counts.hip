@@ -9,6 +9,7 @@
 //   insert     find or claim the slot, one 64-bit atomic add; a probe run past KT_PROBE sets the position's bit in a
 //              failure bitmap, the host grows the table and replays exactly those positions;
 //   profile    a read-only lookup per position; a block stages its 16384 cells in LDS and stores them as 32-bit words;
+//   rel labels a read-only lookup per position of a batch of another sequence set; labels staged in LDS (see there);
 //   histogram  a slot sweep, counts below 256 binned in LDS per block, the tail by 64-bit global atomics.
 // The per-lane tallies (claims, failures, skips, adds) are summed over the wave first: one atomic per wave and counter.
 
@@ -90,15 +91,13 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_rehash_kernel(const kc_slot *old,
 
 // The prof cell of the k-mer position j of read r is prof_off[r] + j - seq_off[r] - (K-1).  Cells follow the k-mer
 // positions in order, so the cells of a block's KC_CELLS positions are one contiguous run [q0, q0+n): staged in LDS,
-// then stored by the whole block, two cells per lane and store.
-__global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab, unsigned long long mask,
-                                                              const char *seq, const int64_t *seq_off,
-                                                              const int64_t *prof_off, int nreads, int64_t total, int K,
-                                                              uint16_t *prof, kc_ctl *ctl)
-{ __shared__ uint16_t cell[KC_CELLS];
-  __shared__ int64_t run[2];
-  const int64_t b0 = (int64_t)blockIdx.x*KC_CELLS, b1 = min(b0+(int64_t)KC_CELLS,total);
-  if (threadIdx.x < 2)                                   // first cell at or after position b0 / b1
+// then stored by the whole block, two cells per lane and store.  The two halves are shared by the profile kernel and
+// the relative-label kernel.
+
+// threads 0 and 1: the first cell at or after position b0 / b1 into run[0] / run[1]
+__device__ static inline void kc_cell_run(const int64_t *seq_off, const int64_t *prof_off, int nreads, int64_t total,
+                                          int K, int64_t b0, int64_t b1, int64_t *run)
+{ if (threadIdx.x < 2)
     { const int64_t p = threadIdx.x ? b1 : b0;
       int lo_r = 0, hi_r = nreads;
       while (hi_r-lo_r > 1)
@@ -108,6 +107,29 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab
       const int64_t in = p-seq_off[lo_r]-(K-1), len = prof_off[lo_r+1]-prof_off[lo_r];
       run[threadIdx.x] = p >= total ? prof_off[nreads] : prof_off[lo_r]+min(max(in,(int64_t)0),len);
     }
+}
+
+// the whole block: cell[0..n) to dst[0..n) as 32-bit words, the cell before the first 4-byte boundary and the last odd
+// one on their own
+__device__ static inline void kc_store_cells(const uint16_t *cell, uint16_t *dst, int64_t n)
+{ const int head = (int)(((uintptr_t)dst >> 1) & 1);     // cells before the first 4-byte boundary
+  const int64_t npair = (n-head) >> 1;
+  if (threadIdx.x == 0)
+    { if (head) dst[0] = cell[0];
+      if ((n-head) & 1) dst[n-1] = cell[n-1];
+    }
+  for (int64_t i = threadIdx.x; i < npair; i += KT_BLOCK)
+    *(unsigned int *)(dst+head+2*i) = (unsigned int)cell[head+2*i] | ((unsigned int)cell[head+2*i+1] << 16);
+}
+
+__global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab, unsigned long long mask,
+                                                              const char *seq, const int64_t *seq_off,
+                                                              const int64_t *prof_off, int nreads, int64_t total, int K,
+                                                              uint16_t *prof, kc_ctl *ctl)
+{ __shared__ uint16_t cell[KC_CELLS];
+  __shared__ int64_t run[2];
+  const int64_t b0 = (int64_t)blockIdx.x*KC_CELLS, b1 = min(b0+(int64_t)KC_CELLS,total);
+  kc_cell_run(seq_off,prof_off,nreads,total,K,b0,b1,run);
   __syncthreads();
   const int64_t q0 = run[0];
   const int64_t n = min(max(run[1]-q0,(int64_t)0),min((int64_t)KC_CELLS,prof_off[nreads]-q0));
@@ -131,15 +153,150 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab
   if (err) atomicOr(&ctl->err,err);
   __syncthreads();
   if (n <= 0) return;
-  uint16_t *dst = prof+q0;
-  const int head = (int)(((uintptr_t)dst >> 1) & 1);     // cells before the first 4-byte boundary
-  const int64_t npair = (n-head) >> 1;
-  if (threadIdx.x == 0)
-    { if (head) dst[0] = cell[0];
-      if ((n-head) & 1) dst[n-1] = cell[n-1];
+  kc_store_cells(cell,prof+q0,n);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Relative labels (genome2class): every k-mer of a batch looked up in a table of ANOTHER sequence set, the count c
+// turned into E (0, absent or a byte other than A C G T), H (1), D (2) or R (>= 3).  Semantics: include/classpro_amd.h,
+// "Relative labels".  A block owns the KC_CELLS consecutive BASE positions [b0, b1), so its run of label characters is
+// labels[b0..b1) and needs no search.  It fills an LDS stage with 'N', walks its positions (one lookup each) and
+// overwrites the k-mer positions; then the whole block stores the stage.
+//   characters  the stage is shifted by the destination's offset from a 16-byte boundary, so both the LDS reads and the
+//               global stores of the middle are aligned 16-byte ones; head and tail go out byte by byte.
+//   packed      four labels per byte counted from the start of each read (cp_pack_labels).  A byte belongs to the block
+//               that holds its FIRST position (the rule of cp_threshold_labels: a group goes with its first position),
+//               so every byte has one writer.  Such a byte may need up to three labels past b1: threads 0..2 look those
+//               up themselves before the walk (they are tallied and profiled by the next block, not here).  Per read
+//               of the block the bytes go out as 32-bit words between a byte-wise head and tail.
+//   profile     the cell stage and store of kc_profile_kernel.
+//   counts      tallied per lane, summed per wave, one atomic per wave and counter.
+// The table is only read and ctl is not touched: an absent k-mer is the normal case here.
+
+#define KC_STAGE (KC_CELLS+32)             // label stage: 15 bytes of shift, 3 positions past b1, rounded up
+
+__device__ static inline unsigned kc_code(unsigned char c)                   // ctos: N, E -> 0, R -> 1, H -> 2, D -> 3
+{ return c == 'R' ? 1u : c == 'H' ? 2u : c == 'D' ? 3u : 0u; }
+
+template <bool PROF, bool LAB, bool PACK>
+__global__ void __launch_bounds__(KT_BLOCK) kc_rel_kernel(const kc_slot *tab, unsigned long long mask, const char *seq,
+                                                          const int64_t *seq_off, const int64_t *prof_off,
+                                                          const int64_t *pack_off, int nreads, int64_t total, int K,
+                                                          uint16_t *prof, char *labels, uint8_t *packed,
+                                                          unsigned long long *counts)
+{ constexpr bool STAGE = LAB || PACK;
+  __shared__ uint16_t cell[PROF ? KC_CELLS : 1];
+  __shared__ __attribute__((aligned(16))) unsigned char stage[STAGE ? KC_STAGE : 16];
+  __shared__ int64_t run[2];
+  const int64_t b0 = (int64_t)blockIdx.x*KC_CELLS, b1 = min(b0+(int64_t)KC_CELLS,total);
+  const int shift = LAB ? (int)((uintptr_t)(labels+b0) & 15) : 0;
+  if (PROF) kc_cell_run(seq_off,prof_off,nreads,total,K,b0,b1,run);
+  if (STAGE)
+    for (int i = threadIdx.x; i < KC_STAGE/4; i += KT_BLOCK) ((unsigned int *)stage)[i] = 0x4E4E4E4Eu;   // "NNNN"
+  __syncthreads();
+  int64_t q0 = 0, n = 0;
+  if (PROF)
+    { q0 = run[0];
+      n = min(max(run[1]-q0,(int64_t)0),min((int64_t)KC_CELLS,prof_off[nreads]-q0));
     }
-  for (int64_t i = threadIdx.x; i < npair; i += KT_BLOCK)
-    *(unsigned int *)(dst+head+2*i) = (unsigned int)cell[head+2*i] | ((unsigned int)cell[head+2*i+1] << 16);
+  auto label_of = [&](bool ok, unsigned long long hi, unsigned long long lo, unsigned long long *cnt) -> unsigned
+    { unsigned long long c = 0;
+      if (ok)
+        { const kc_slot *e = kt_lookup(tab,mask,hi,lo);
+          if (e) c = e->cnt;
+        }
+      *cnt = c;
+      return (unsigned)min(c,3ull);                      // index in E, H, D, R
+    };
+  if (PACK && threadIdx.x < 3)                           // the labels past b1 that a byte begun before b1 holds
+    { const int64_t j = b1+threadIdx.x;
+      int lo_r = 0, hi_r = nreads;                       // the read holding b1-1
+      while (hi_r-lo_r > 1)
+        { const int mid = (lo_r+hi_r) >> 1;
+          if (seq_off[mid] <= b1-1) lo_r = mid; else hi_r = mid;
+        }
+      const int64_t rs = seq_off[lo_r], re = seq_off[lo_r+1];
+      if (j < re && j-rs >= K-1 && rs+((j-rs) & ~(int64_t)3) < b1)
+        { const kt_u128 kmask = (((kt_u128)1) << (2*K))-1;
+          kt_u128 fw = 0, rc = 0;
+          bool ok = true;
+          for (int64_t i = j-K+1; i <= j; i++)
+            { const int b = kt_base((unsigned char)seq[i]);
+              if (b < 0) { ok = false; break; }
+              fw = ((fw << 2) | (kt_u128)b) & kmask;
+              rc = (rc >> 2) | (((kt_u128)(3-b)) << (2*K-2));
+            }
+          const kt_u128 key = rc < fw ? rc : fw;
+          unsigned long long c;
+          const unsigned x = label_of(ok,(unsigned long long)(key >> 63),(unsigned long long)key & KT_M63,&c);
+          stage[shift+(j-b0)] = (unsigned char)((0x52444845u >> (8*x)) & 0xffu);              // "EHDR"
+        }
+    }
+  const int64_t p0 = b0+(int64_t)threadIdx.x*KT_CHUNK;
+  unsigned int tally[4] = { 0, 0, 0, 0 };                // this lane's labels, order E, H, D, R
+  int cur = -1;                                          // the read whose cell base is held
+  int64_t base = 0;
+  if (p0 < total)
+    kt_walk_all<true>(seq,seq_off,nreads,total,K,p0,
+      [&](int r, int64_t j, bool ok, unsigned long long hi, unsigned long long lo)
+      { unsigned long long c;
+        const unsigned x = label_of(ok,hi,lo,&c);
+        tally[0] += x == 0; tally[1] += x == 1; tally[2] += x == 2; tally[3] += x == 3;
+        if (STAGE) stage[shift+(j-b0)] = (unsigned char)((0x52444845u >> (8*x)) & 0xffu);
+        if (PROF)
+          { if (r != cur) { cur = r; base = prof_off[r]-seq_off[r]-(K-1)-q0; }
+            const int64_t i = base+j;
+            if ((unsigned long long)i < (unsigned long long)n)
+              cell[i] = (uint16_t)min(c,(unsigned long long)CP_MAX_KMER_CNT);
+          }
+      });
+  if (counts)
+    for (int k = 0; k < 4; k++) kc_wave_add(counts+k,tally[k]);
+  __syncthreads();
+  if (PROF && n > 0) kc_store_cells(cell,prof+q0,n);
+  if (LAB)
+    { char *dst = labels+b0;
+      const int64_t nb = b1-b0;
+      const int64_t head = min(nb,(int64_t)((16-shift) & 15));
+      const int64_t nvec = (nb-head) >> 4, tail = head+16*nvec;
+      if ((int64_t)threadIdx.x < head) dst[threadIdx.x] = (char)stage[shift+threadIdx.x];
+      for (int64_t i = threadIdx.x; i < nvec; i += KT_BLOCK)
+        *(uint4 *)(dst+head+16*i) = *(const uint4 *)(stage+shift+head+16*i);
+      if ((int64_t)threadIdx.x < nb-tail) dst[tail+threadIdx.x] = (char)stage[shift+tail+threadIdx.x];
+    }
+  if (PACK)
+    { int r = 0, hi_r = nreads;                          // the read holding b0
+      while (hi_r-r > 1)
+        { const int mid = (r+hi_r) >> 1;
+          if (seq_off[mid] <= b0) r = mid; else hi_r = mid;
+        }
+      for (; r < nreads; r++)
+        { const int64_t rs = seq_off[r], re = seq_off[r+1];
+          if (rs >= b1) break;
+          const int64_t i0 = (max(rs,b0)-rs+3) >> 2, i1 = (min(re,b1)-rs+3) >> 2;   // bytes whose first position is ours
+          if (i0 >= i1) continue;
+          const int64_t s0 = shift+(rs-b0);              // label of read position l: stage[s0+l] (only l >= 4*i0 is read)
+          const int64_t rlen = re-rs;
+          auto byte_at = [&](int64_t i) -> unsigned
+            { const int64_t l = 4*i;
+              unsigned b = 0;
+#pragma unroll
+              for (int q = 0; q < 4; q++)
+                if (l+q < rlen) b |= kc_code(stage[s0+l+q]) << (6-2*q);
+              return b;
+            };
+          uint8_t *dst = packed+pack_off[r]+i0;
+          const int64_t nb = i1-i0;
+          const int64_t head = min(nb,(int64_t)((4-((uintptr_t)dst & 3)) & 3));
+          const int64_t nw = (nb-head) >> 2, tail = head+4*nw;
+          if ((int64_t)threadIdx.x < head) dst[threadIdx.x] = (uint8_t)byte_at(i0+threadIdx.x);
+          for (int64_t w = threadIdx.x; w < nw; w += KT_BLOCK)
+            { const int64_t i = i0+head+4*w;
+              *(unsigned int *)(dst+head+4*w) = byte_at(i) | (byte_at(i+1) << 8) | (byte_at(i+2) << 16) | (byte_at(i+3) << 24);
+            }
+          if ((int64_t)threadIdx.x < nb-tail) dst[tail+threadIdx.x] = (uint8_t)byte_at(i0+tail+threadIdx.x);
+        }
+    }
 }
 
 // hist[c-1] += distinct keys with count c (c < 32767), hist[32766] += those with >= 32767, hist[32767] += the
@@ -337,6 +494,39 @@ extern "C" int cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, con
   const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
   kc_profile_kernel<<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,nreads,total_bases,t->K,d_prof,
                                             t->ctl);
+  HIPCHK(hipGetLastError());
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                                         int64_t total_bases, uint16_t *d_prof, const int64_t *d_prof_off,
+                                         char *d_labels, uint8_t *d_packed, const int64_t *d_pack_off,
+                                         int64_t *d_counts, void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: bad argument");
+  if (!d_prof != !d_prof_off) return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: d_prof and d_prof_off go together");
+  if (!d_packed != !d_pack_off)
+    return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: d_packed and d_pack_off go together");
+  if (!d_prof && !d_labels && !d_packed && !d_counts)
+    return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: no output wanted");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  t->stream = st;
+  const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
+  unsigned long long *cnt = (unsigned long long *)d_counts;
+#define KC_REL(P,L,B) kc_rel_kernel<P,L,B><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,d_pack_off, \
+                                                                   nreads,total_bases,t->K,d_prof,d_labels,d_packed,cnt)
+  switch ((d_prof ? 4 : 0) | (d_labels ? 2 : 0) | (d_packed ? 1 : 0))
+    { case 0: KC_REL(false,false,false); break;
+      case 1: KC_REL(false,false,true); break;
+      case 2: KC_REL(false,true,false); break;
+      case 3: KC_REL(false,true,true); break;
+      case 4: KC_REL(true,false,false); break;
+      case 5: KC_REL(true,false,true); break;
+      case 6: KC_REL(true,true,false); break;
+      default: KC_REL(true,true,true); break;
+    }
+#undef KC_REL
   HIPCHK(hipGetLastError());
   return CP_OK;
 }

@@ -371,6 +371,28 @@ int  cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int
 int  cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out);
 
 /* ------------------------------------------------------------------------------------------
+ * Relative labels (genome2class): the ground truth of a read set from a count table of ANOTHER sequence set, the
+ * assembly.  What `FastK -p:genome` + prof2class give (src/prof2class.c:241-254), in one pass over a batch in the flat
+ * layout; the batch need not be (and usually is not) what was added to `t`.
+ *
+ *   Key       one canonical lookup per k-mer position, the key of "K-mer count table".  c = the count in the table.
+ *   Label     c == 0 -> E, 1 -> H, 2 -> D, >= 3 -> R.  Read r gets 'N' on its first min(K-1, rlen_r) positions (the
+ *             read rule of cp_threshold_labels); reads shorter than K and empty reads are legal.
+ *   Absent    a k-mer that is not in the table has c = 0, and so has one that holds a byte other than upper-case
+ *             A C G T.  Neither is an error: the call never sets the table's deferred error and never changes the
+ *             table (cp_kmer_counts_stats and cp_kmer_counts_hist give the same before and after).
+ *   Outputs   each optional (NULL = not wanted, at least one required; a pair with one half NULL is CP_EINVAL):
+ *             d_prof   + d_prof_off [nreads+1]: min(c, 32767) in the cell layout of cp_kmer_counts_profiles;
+ *             d_labels [total_bases]  the characters;
+ *             d_packed + d_pack_off [nreads+1]: the 2-bit layout of cp_pack_labels, written directly;
+ *             d_counts int64 [4] on the device, order E, H, D, R, ADDED TO, so several batches accumulate.
+ * All results are integers and do not depend on the batching or the read order.  Asynchronous on `stream`.
+ */
+int  cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                               int64_t total_bases, uint16_t *d_prof, const int64_t *d_prof_off, char *d_labels,
+                               uint8_t *d_packed, const int64_t *d_pack_off, int64_t *d_counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
