@@ -61,16 +61,10 @@ def build(force=False, verbose=False):
             os.remove(side)
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         _run([hipcc] + FLAGS + [os.path.join(CSRC, "capi.hip"), "-o", OUT], verbose)
-        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "classpro_main.cpp"), "-o", CLI,
-              "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
-        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "class2cns.cpp"), "-o", CNS,
-              "-L" + _HERE, "-lclasspro_amd", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
-        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "classgs.cpp"), "-o", GS,
-              "-L" + _HERE, "-lclasspro_amd", "-lz", "-Wl,-rpath,$ORIGIN"], verbose)
-        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "kprof.cpp"), "-o", KPROF,
-              "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
-        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", "genome2class.cpp"), "-o", G2C,
-              "-L" + _HERE, "-lclasspro_amd", "-lz", "-lpthread", "-Wl,-rpath,$ORIGIN"], verbose)
+        for src, out, pthread in (("classpro_main.cpp", CLI, True), ("class2cns.cpp", CNS, False), ("classgs.cpp", GS, False),
+                                  ("kprof.cpp", KPROF, True), ("genome2class.cpp", G2C, True)):
+            _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", src), "-o", out,
+                  "-L" + _HERE, "-lclasspro_amd", "-lz"] + ["-lpthread"] * pthread + ["-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
               os.path.join(CSRC, "synth", "synth_gen.hip"), "-o", SYNTH], verbose)
         with open(side, "w") as f:

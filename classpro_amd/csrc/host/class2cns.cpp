@@ -15,23 +15,14 @@
 //   -c  canonical k-mers (a k-mer and its reverse complement share one entry) for -u, -x and -C; under -u each line
 //       then carries the canonical k-mer's text.
 //   -v  a summary on stderr: distinct, unanimous and skipped k-mers, table size.
-#include <hip/hip_runtime.h>
 #include <charconv>
 #include <cmath>
-#include "host_io.h"
-#include "../../../include/classpro_amd.h"
+#include "gpu_tool.h"
+#include "class_record.h"
 
 static const char *USAGE = "[-v] [-c] [-u] [-x] [-C<out.class>] <estimate>.class <fastk_root>[.prof]";
 
 static const int64_t BATCH_BASES = (int64_t)256 << 20;        // bases per device batch
-
-static void cp_die(int rc, const char *what)
-{ die("%s: %s: %s (%d)\n",PROG,what,cp_last_error(),rc); }
-
-static void hip_die(hipError_t e, const char *what)
-{ die("%s: %s: %s\n",PROG,what,hipGetErrorString(e)); }
-
-#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
 
 // host and device buffers of one batch of records (pinned host memory)
 struct Batch
@@ -226,12 +217,7 @@ int main(int argc, char **argv)
           HCHK(hipMemcpy(b.h_lab,b.d_lab,b.nbases,hipMemcpyDeviceToHost));
           for (int i = 0; i < b.nreads; i++)
             { const int64_t s = b.h_off[i], n = b.h_off[i+1]-s;
-              fputs(headers[(size_t)i].c_str(),out);
-              fputc('\n',out);
-              fwrite(b.h_seq+s,1,(size_t)n,out);
-              fputs("\n+\n",out);
-              fwrite(b.h_lab+s,1,(size_t)n,out);
-              fputc('\n',out);
+              write_class_record(out,headers[(size_t)i],b.h_seq+s,(size_t)n,b.h_lab+s,(size_t)n);
             }
         });
       rc = cp_kmer_table_stats(T,&st);                              // a k-mer missing from the table would show here

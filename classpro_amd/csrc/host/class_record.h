@@ -1,5 +1,5 @@
-// class_record.h -- what prof2class and genome2class share: the header of a FASTX read as the reference's tools print
-// it and one record of a .class file.
+// class_record.h -- the header of a FASTX read as the reference's tools print it and one record of a .class file, for
+// every tool that writes one.
 #pragma once
 #include "host_io.h"
 

@@ -13,43 +13,13 @@
 //   -A  <truth.class> is read in step with the input (names and lengths checked with class2acc's messages), the truth
 //       labels go up with the batch and cp_acc_add counts on the labels still in HBM; after the output is written,
 //       stdout gets exactly what `class2acc <source_root>.GS.class <truth.class>` prints with default options.
-#include <hip/hip_runtime.h>
-#include <fcntl.h>
-#include "host_io.h"
+#include "gpu_tool.h"
 #include "dazz_db.h"
-#include "acc_report.h"
-#include "../../../include/classpro_amd.h"
+#include "class_record.h"
 
 static const char *USAGE = "<source_root> <E/H_thres> <H/D_thres> <D/R_thres>";
 
-static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
-                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };          // ClassGS.c:20-23
-
 static const int64_t BATCH_BASES = (int64_t)64 << 20;        // bases per device batch
-
-static void cp_die(int rc, const char *what)
-{ die("%s: %s: %s (%d)\n",PROG,what,cp_last_error(),rc); }
-
-static void hip_die(hipError_t e, const char *what)
-{ die("%s: %s: %s\n",PROG,what,hipGetErrorString(e)); }
-
-#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
-
-// a device buffer that only grows
-template <class T>
-struct DevBuf
-  { T *p = nullptr;
-    size_t cap = 0;
-    T *need(size_t n)
-    { if (n > cap)
-        { if (p) HCHK(hipFree(p));
-          cap = n+n/4+64;
-          HCHK(hipMalloc((void **)&p,cap*sizeof(T)));
-        }
-      return p;
-    }
-    void up(const std::vector<T> &h) { need(h.size()+1); if (!h.empty()) HCHK(hipMemcpy(p,h.data(),h.size()*sizeof(T),hipMemcpyHostToDevice)); }
-  };
 
 struct Batch
   { std::vector<std::string> headers;
@@ -99,7 +69,7 @@ int main(int argc, char **argv)
   fprintf(stderr,"E < %d <= H < %d <= D < %d <= R\n",thres[0],thres[1],thres[2]);
 
   int ext;
-  for (ext = 0; ext < 10; ext++)
+  for (ext = 0; ext < 10; ext++)                                 // ClassGS.c:20-23: the root as given, not split
     { int fd = open((root+EXT[ext]).c_str(),O_RDONLY);
       if (fd >= 0) { close(fd); break; }
     }
@@ -169,12 +139,7 @@ int main(int argc, char **argv)
       if (bases > 0) HCHK(hipMemcpy(D.h_lab.data(),D.lab.p,(size_t)bases,hipMemcpyDeviceToHost));
       for (int i = 0; i < n; i++)
         { const int64_t s = B.soff[(size_t)i], len = B.soff[(size_t)i+1]-s;
-          fputs(B.headers[(size_t)i].c_str(),out);
-          fputc('\n',out);
-          fwrite(B.seq.data()+s,1,(size_t)len,out);
-          fputs("\n+\n",out);
-          fwrite(D.h_lab.data()+s,1,(size_t)len,out);
-          fputc('\n',out);
+          write_class_record(out,B.headers[(size_t)i],B.seq.data()+s,(size_t)len,D.h_lab.data()+s,(size_t)len);
         }
       B.clear();
     };
@@ -229,16 +194,7 @@ int main(int argc, char **argv)
     { if (tru.next() >= 0)
         die("# seqs in %s < # seqs in %s\n",out_path.c_str(),truth_path);
       AccTotals T;
-      if (D.acc)
-        { cp_acc_stats st;
-          const int rc = cp_acc_read(D.acc,&st);
-          if (rc != CP_OK) cp_die(rc,"cp_acc_read");
-          for (int i = 0; i < 4; i++)
-            for (int j = 0; j < 4; j++) T.cfm[i][j] = st.cfm[i][j];
-          T.ntot = st.ntot; T.ncor = st.ncor; T.nfne = st.nfne;
-          T.ntot_normal = st.ntot_normal; T.ncor_normal = st.ncor_normal; T.nfne_normal = st.nfne_normal;
-          T.ntot_repeat = st.ntot_repeat; T.ncor_repeat = st.ncor_repeat; T.nfne_repeat = st.nfne_repeat;
-        }
+      if (D.acc) T = acc_totals(D.acc);
       print_acc_report(stdout,T);
       fflush(stdout);
     }

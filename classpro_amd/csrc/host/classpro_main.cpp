@@ -59,8 +59,6 @@ static void remember_mapping(const void *m, size_t len);      // (SIGBUS handlin
 static const char *USAGE = "[-vs] [-T<int(4)>] [-c<int>] [-r<int(20000)>] "
                            "[-P<tmp_dir(./)>] [-N<fastk_root>] [-M<model_path>] "
                            "<source>[.db|.dam|.f[ast][aq][.gz]";                      // const.c:14-17
-static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
-                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };          // ClassPro.h:326-330
 
 #define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) die("%s: %s: %s\n",PROG,#call,hipGetErrorString(e_)); } while (0)
 #define CPOK(call)  do { if ((call) < 0) die("%s\n",cp_last_error()); } while (0)
@@ -578,13 +576,8 @@ int main(int argc, char **argv)
     die("Usage: %s %s\n",PROG,USAGE);
   if (verbose) fprintf(stderr,"Info about inputs:\n");
 
-  std::string path = path_to(pos[0]), root;
-  int idx;
-  for (idx = 0; idx < 10; idx++)
-    { root = root_of(pos[0],EXT[idx]);
-      int fd = open((path+"/"+root+EXT[idx]).c_str(),O_RDONLY);
-      if (fd >= 0) { close(fd); break; }
-    }
+  std::string path, root;
+  const int idx = find_source(pos[0],&path,&root);
   if (idx == 10)
     die("Cannot open %s as a .db|.dam or .f{ast}[aq][.gz] file\n",pos[0].c_str());
   if (pos.size() != 1)

@@ -36,95 +36,13 @@
 //   genome2class: Cannot open <name> as a .db|.dam or .f{ast}[aq][.gz] file       genome or source
 //   genome2class: Cannot open <path> for 'w'                                      <out_root>.class, with -p <out_root>.prof
 //   genome2class: Cannot open <est.class> [errno=<n>]
-#include <hip/hip_runtime.h>
-#include <fcntl.h>
-#include "host_io.h"
-#include "dazz_db.h"
-#include "class_record.h"
-#include "acc_report.h"
+#include "gpu_tool.h"
+#include "read_source.h"
+#include "prof_writer.h"
 #include "thread_pool.h"
-#include "../../../include/classpro_amd.h"
 
 static const char *USAGE = "[-v] [-p] [-k<int(40)>] [-T<int(4)>] [-b<int(67108864)>] [-N<out_root>] [-A<est.class>]\n"
                            "                    <genome>[.f[ast][aq][.gz]|.db|.dam] <source>[.db|.dam|.f[ast][aq][.gz]]";
-
-static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
-                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };
-
-static void cp_die(int rc, const char *what)
-{ die("%s: %s: %s (%d)\n",PROG,what,cp_last_error(),rc); }
-
-static void hip_die(hipError_t e, const char *what)
-{ die("%s: %s: %s\n",PROG,what,hipGetErrorString(e)); }
-
-#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
-
-// a device buffer that only grows
-template <class T>
-struct DevBuf
-  { T *p = nullptr;
-    size_t cap = 0;
-    T *need(size_t n)
-    { if (n > cap)
-        { if (p) HCHK(hipFree(p));
-          cap = n+n/4+64;
-          HCHK(hipMalloc((void **)&p,cap*sizeof(T)));
-        }
-      return p;
-    }
-    void up(const std::vector<T> &h) { need(h.size()+1); if (!h.empty()) HCHK(hipMemcpy(p,h.data(),h.size()*sizeof(T),hipMemcpyHostToDevice)); }
-  };
-
-// the sequences of an input, one after the other; rewind() starts the next pass
-struct Source
-  { std::string path;
-    bool is_db = false, is_dam = false;
-    DazzDB db;
-    FastxReader *fx = nullptr;
-    int next_db = 0;
-    std::string seq, header;
-    bool find(const std::string &name, std::string *dir, std::string *root)    // false: none of the ten forms exists
-    { *dir = path_to(name);
-      for (int idx = 0; idx < 10; idx++)
-        { *root = root_of(name,EXT[idx]);
-          const std::string full = *dir+"/"+*root+EXT[idx];
-          int fd = ::open(full.c_str(),O_RDONLY);
-          if (fd < 0) continue;
-          close(fd);
-          path = full;
-          is_db = idx <= 1; is_dam = idx == 1;
-          return true;
-        }
-      return false;
-    }
-    void open()
-    { if (is_db) { db.open(path,is_dam); return; }
-      fx = new FastxReader(path.c_str());
-      if (!fx->f) die("%s: Cannot open %s [errno=%d]\n",PROG,path.c_str(),errno);
-    }
-    void rewind()
-    { next_db = 0;
-      if (is_db) return;
-      delete fx;
-      fx = nullptr;
-      open();
-    }
-    bool next()                                                   // the next sequence into seq, its .class header into header
-    { if (is_db)
-        { if (next_db >= db.nreads) return false;
-          header = db.header(next_db);
-          db.load(next_db++,seq);
-          return true;
-        }
-      if (fx->next() < 0)
-        { if (fx->bad_qual) die("%s: %s: a quality string is not as long as its sequence\n",PROG,path.c_str());
-          return false;
-        }
-      seq.swap(fx->seq);
-      header = fastx_class_header(*fx);
-      return true;
-    }
-  };
 
 struct Batch
   { std::vector<std::string> headers;
@@ -132,13 +50,6 @@ struct Batch
     std::vector<int64_t> soff{0}, poff{0}, koff{0};                  // bases, profile cells, packed label bytes
     void clear() { headers.clear(); seq.clear(); est.clear(); soff.assign(1,0); poff.assign(1,0); koff.assign(1,0); }
     int n() const { return (int)soff.size()-1; }
-  };
-
-struct Part
-  { FILE *f = nullptr;
-    std::string name;
-    int64_t first = 0, n = 0, bytes = 0;
-    std::vector<int64_t> ends;
   };
 
 int main(int argc, char **argv)
@@ -269,29 +180,16 @@ int main(int argc, char **argv)
         }
     }
   const int nparts = want_prof ? (int)std::min<int64_t>(nthreads,nreads_known) : 0;
-  std::vector<Part> parts((size_t)nparts);
-  if (want_prof)
-    { if (fwrite(&K,4,1,fs) != 1 || fwrite(&nparts,4,1,fs) != 1 || fclose(fs) != 0)
-        die("%s: Cannot write %s\n",PROG,stub_path.c_str());
-      for (int p = 0; p < nparts; p++)
-        { Part &P = parts[(size_t)p];
-          P.first = nreads_known*p/nparts;
-          P.n = nreads_known*(p+1)/nparts-P.first;
-          P.name = odir+"/."+oname+".prof."+std::to_string(p+1);
-          P.f = fopen(P.name.c_str(),"wb");
-          if (!P.f) die("%s: Cannot open %s for 'w'\n",PROG,P.name.c_str());
-          P.ends.reserve((size_t)P.n);
-        }
-    }
+  ProfWriter W;
+  if (want_prof) W.open(fs,stub_path,K,nparts,nreads_known,odir,oname);
   ThreadPool pool(nthreads);
   Batch B;
   std::vector<uint8_t> h_pack;
   std::vector<uint16_t> h_prof;
   std::vector<std::string> text((size_t)nthreads);                   // per thread: the records of its reads of the batch
   std::vector<std::vector<uint8_t>> code((size_t)nthreads);          // per thread: the profile codes of its reads
-  std::vector<int64_t> clen, tskip((size_t)nthreads,0);
-  int64_t nreads = 0, nbases = 0, done = 0;
-  int part = 0;
+  std::vector<int64_t> tskip((size_t)nthreads,0);
+  int64_t nreads = 0, nbases = 0;
   auto flush = [&]()
     { const int n = B.n();
       if (n == 0) return;
@@ -319,7 +217,7 @@ int main(int argc, char **argv)
           if (cells > 0) HCHK(hipMemcpy(h_prof.data(),d_prof.p,(size_t)cells*2,hipMemcpyDeviceToHost));
         }
       HCHK(hipDeviceSynchronize());
-      clen.assign((size_t)n,0);
+      W.clen.assign((size_t)n,0);
       const int nt = std::min(nthreads,n);
       pool.parallel_for(nt,[&](int64_t t)                            // thread t: a contiguous range of the batch's reads
         { const int r0 = (int)((int64_t)n*t/nt), r1 = (int)((int64_t)n*(t+1)/nt);
@@ -349,7 +247,7 @@ int main(int argc, char **argv)
                 { const int64_t np = B.poff[(size_t)r+1]-B.poff[(size_t)r];
                   const int64_t l = cp_encode_profile(h_prof.data()+B.poff[(size_t)r],(int)np,c.data()+o,(int64_t)c.size()-o);
                   if (l < 0) cp_die((int)l,"cp_encode_profile");
-                  clen[(size_t)r] = l;
+                  W.clen[(size_t)r] = l;
                   o += l;
                 }
             }
@@ -358,19 +256,7 @@ int main(int argc, char **argv)
       for (int t = 0; t < nt; t++)
         { const std::string &x = text[(size_t)t];
           if (!x.empty() && fwrite(x.data(),1,x.size(),out) != x.size()) die("%s: Cannot write %s\n",PROG,class_path.c_str());
-          if (!want_prof) continue;
-          const int r0 = (int)((int64_t)n*t/nt), r1 = (int)((int64_t)n*(t+1)/nt);
-          int64_t o = 0;
-          for (int r = r0; r < r1; r++, done++)
-            { while (done >= parts[(size_t)part].first+parts[(size_t)part].n) part++;
-              Part &P = parts[(size_t)part];
-              const int64_t l = clen[(size_t)r];
-              if (l > 0 && fwrite(code[(size_t)t].data()+o,1,(size_t)l,P.f) != (size_t)l)
-                die("%s: Cannot write %s\n",PROG,P.name.c_str());
-              o += l;
-              P.bytes += l;
-              P.ends.push_back(P.bytes);
-            }
+          if (want_prof) W.append((int)((int64_t)n*t/nt),(int)((int64_t)n*(t+1)/nt),code[(size_t)t].data());
         }
       B.clear();
     };
@@ -411,16 +297,7 @@ int main(int argc, char **argv)
   flush();
   if (want_prof && nreads != nreads_known) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
   if (fclose(out) != 0) die("%s: Cannot write %s\n",PROG,class_path.c_str());
-  for (int p = 0; p < nparts; p++)
-    { Part &P = parts[(size_t)p];
-      if (fclose(P.f) != 0) die("%s: Cannot write %s\n",PROG,P.name.c_str());
-      const std::string nm = odir+"/."+oname+".pidx."+std::to_string(p+1);
-      FILE *f = fopen(nm.c_str(),"wb");
-      if (!f) die("%s: Cannot open %s for 'w'\n",PROG,nm.c_str());
-      bool ok = fwrite(&K,4,1,f) == 1 && fwrite(&P.first,8,1,f) == 1 && fwrite(&P.n,8,1,f) == 1
-                && (P.n == 0 || fwrite(P.ends.data(),8,(size_t)P.n,f) == (size_t)P.n);
-      if (fclose(f) != 0 || !ok) die("%s: Cannot write %s\n",PROG,nm.c_str());
-    }
+  W.close();
   if (est_path && est.next() >= 0)
     die("# seqs in %s > # seqs in %s\n",est_path,class_path.c_str());
 
@@ -437,16 +314,7 @@ int main(int argc, char **argv)
     fprintf(stderr,"%s: %lld k-mer positions of the reads hold a byte other than upper-case A C G T: their label is E\n",
             PROG,(long long)rskip);
   if (est_path)
-    { AccTotals A;
-      cp_acc_stats as;
-      rc = cp_acc_read(acc,&as);
-      if (rc != CP_OK) cp_die(rc,"cp_acc_read");
-      for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) A.cfm[i][j] = as.cfm[i][j];
-      A.ntot = as.ntot; A.ncor = as.ncor; A.nfne = as.nfne;
-      A.ntot_normal = as.ntot_normal; A.ncor_normal = as.ncor_normal; A.nfne_normal = as.nfne_normal;
-      A.ntot_repeat = as.ntot_repeat; A.ncor_repeat = as.ncor_repeat; A.nfne_repeat = as.nfne_repeat;
-      print_acc_report(stdout,A);
+    { print_acc_report(stdout,acc_totals(acc));
       fflush(stdout);
       cp_acc_destroy(acc);
     }

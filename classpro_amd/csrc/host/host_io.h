@@ -1,8 +1,9 @@
-// host_io.h -- host-side readers shared by the command-line tools (ClassPro, prof2class, class2acc):
+// host_io.h -- host-side readers shared by the command-line tools: the forms of a <source> argument,
 // FASTX with kseq.h semantics, the FASTK profile index / histogram files, gene_core-style option
 // parsing.  Plain C++; no device code.
 #pragma once
 #include <zlib.h>
+#include <fcntl.h>
 #include <strings.h>
 #include <unistd.h>
 #include <cstdio>
@@ -38,6 +39,24 @@ static std::string root_of(const std::string &name, const char *suffix)
   if (f.size() > sl && strcasecmp(f.c_str()+f.size()-sl,suffix) == 0)
     return f.substr(0,f.size()-sl);
   return f;
+}
+
+// ---- the forms of a <source> argument, in the order they are tried (ClassPro.h:326-330) ----------
+static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
+                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };
+
+// The first of the ten forms of `name` that opens: its index in EXT, or 10 when there is none.  *dir is name's
+// directory and *root its file name without that suffix: the file is *dir/*root+EXT[index].  The caller says what
+// could not be opened, each tool in its own words.
+static int find_source(const std::string &name, std::string *dir, std::string *root)
+{ *dir = path_to(name);
+  int idx;
+  for (idx = 0; idx < 10; idx++)
+    { *root = root_of(name,EXT[idx]);
+      int fd = open((*dir+"/"+*root+EXT[idx]).c_str(),O_RDONLY);
+      if (fd >= 0) { close(fd); break; }
+    }
+  return idx;
 }
 
 // ---- integer options, gene_core.h:46-77 ----------------------------------------------------------

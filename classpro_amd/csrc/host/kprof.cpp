@@ -13,91 +13,20 @@
 //      nparts = min(T, reads) holds the reads [reads*p/nparts, reads*(p+1)/nparts).
 // A k-mer with a byte other than upper-case A C G T is not counted and gets count 0; how many there were is always said
 // on stderr.  FastK's own treatment of such bases is not reproduced.
-#include <hip/hip_runtime.h>
-#include <fcntl.h>
-#include "host_io.h"
-#include "dazz_db.h"
+#include "gpu_tool.h"
+#include "read_source.h"
+#include "prof_writer.h"
 #include "thread_pool.h"
-#include "../../../include/classpro_amd.h"
 
 static const char *USAGE = "[-v] [-k<int(40)>] [-T<int(4)>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]";
 
-static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
-                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };
-
 static const int64_t BATCH_BASES = (int64_t)64 << 20;        // bases per device batch
-
-static void cp_die(int rc, const char *what)
-{ die("%s: %s: %s (%d)\n",PROG,what,cp_last_error(),rc); }
-
-static void hip_die(hipError_t e, const char *what)
-{ die("%s: %s: %s\n",PROG,what,hipGetErrorString(e)); }
-
-#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
-
-// a device buffer that only grows
-template <class T>
-struct DevBuf
-  { T *p = nullptr;
-    size_t cap = 0;
-    T *need(size_t n)
-    { if (n > cap)
-        { if (p) HCHK(hipFree(p));
-          cap = n+n/4+64;
-          HCHK(hipMalloc((void **)&p,cap*sizeof(T)));
-        }
-      return p;
-    }
-    void up(const std::vector<T> &h) { need(h.size()+1); if (!h.empty()) HCHK(hipMemcpy(p,h.data(),h.size()*sizeof(T),hipMemcpyHostToDevice)); }
-  };
-
-// the reads of the source, one after the other; rewind() starts the next pass
-struct Source
-  { std::string path;
-    bool is_db, is_dam;
-    DazzDB db;
-    FastxReader *fx = nullptr;
-    int next_db = 0;
-    std::string seq;
-    void open()
-    { if (is_db) { db.open(path,is_dam); return; }
-      fx = new FastxReader(path.c_str());
-      if (!fx->f) die("%s: Cannot open %s [errno=%d]\n",PROG,path.c_str(),errno);
-    }
-    void rewind()
-    { next_db = 0;
-      if (is_db) return;
-      delete fx;
-      fx = nullptr;
-      open();
-    }
-    bool next()                                                   // the next read into seq
-    { if (is_db)
-        { if (next_db >= db.nreads) return false;
-          db.load(next_db++,seq);
-          return true;
-        }
-      if (fx->next() < 0)
-        { if (fx->bad_qual) die("%s: %s: a quality string is not as long as its sequence\n",PROG,path.c_str());
-          return false;
-        }
-      seq.swap(fx->seq);
-      return true;
-    }
-  };
 
 struct Batch
   { std::vector<char> seq;
     std::vector<int64_t> soff{0}, poff{0};
     void clear() { seq.clear(); soff.assign(1,0); poff.assign(1,0); }
     int n() const { return (int)soff.size()-1; }
-  };
-
-struct Part
-  { FILE *f = nullptr;
-    std::string name;
-    int64_t first = 0, n = 0, bytes = 0;
-    std::vector<int64_t> ends;
   };
 
 int main(int argc, char **argv)
@@ -128,18 +57,10 @@ int main(int argc, char **argv)
   if (K < 2 || K > 63)
     die("%s: K-mer length must lie in [2, 63] (%d)\n",PROG,K);
 
-  std::string path = path_to(pos[0]), root;
-  int idx;
-  for (idx = 0; idx < 10; idx++)
-    { root = root_of(pos[0],EXT[idx]);
-      int fd = open((path+"/"+root+EXT[idx]).c_str(),O_RDONLY);
-      if (fd >= 0) { close(fd); break; }
-    }
-  if (idx == 10)
-    die("%s: Cannot open %s as a .db|.dam or .f{ast}[aq][.gz] file\n",PROG,pos[0].c_str());
   Source S;
-  S.path = path+"/"+root+EXT[idx];
-  S.is_db = idx <= 1; S.is_dam = idx == 1;
+  std::string path, root;
+  if (!S.find(pos[0],&path,&root))
+    die("%s: Cannot open %s as a .db|.dam or .f{ast}[aq][.gz] file\n",PROG,pos[0].c_str());
   if (out_root.empty()) out_root = path+"/"+root;
   const std::string odir = path_to(out_root), oname = root_of(out_root,"");
   const std::string hist_path = odir+"/"+oname+".hist", stub_path = odir+"/"+oname+".prof";
@@ -210,24 +131,11 @@ int main(int argc, char **argv)
 
   // ---- pass 2: profiles ----
   const int nparts = (int)std::min<int64_t>(nthreads,nreads);
-  if (fwrite(&K,4,1,fs) != 1 || fwrite(&nparts,4,1,fs) != 1 || fclose(fs) != 0)
-    die("%s: Cannot write %s\n",PROG,stub_path.c_str());
-  std::vector<Part> parts((size_t)nparts);
-  for (int p = 0; p < nparts; p++)
-    { Part &P = parts[(size_t)p];
-      P.first = nreads*p/nparts;
-      P.n = nreads*(p+1)/nparts-P.first;
-      P.name = odir+"/."+oname+".prof."+std::to_string(p+1);
-      P.f = fopen(P.name.c_str(),"wb");
-      if (!P.f) die("%s: Cannot open %s for 'w'\n",PROG,P.name.c_str());
-      P.ends.reserve((size_t)P.n);
-    }
+  ProfWriter W;
+  W.open(fs,stub_path,K,nparts,nreads,odir,oname);
   ThreadPool pool(nthreads);
   std::vector<uint16_t> h_prof;
   std::vector<std::vector<uint8_t>> code((size_t)nthreads);          // per thread: the codes of its reads of the batch
-  std::vector<int64_t> clen;                                         // per read of the batch
-  int64_t done = 0;                                                  // reads written so far
-  int part = 0;
   auto profile = [&]()
     { const int n = B.n();
       if (n == 0) return;
@@ -240,7 +148,7 @@ int main(int argc, char **argv)
       h_prof.resize((size_t)cells+1);
       if (cells > 0) HCHK(hipMemcpy(h_prof.data(),d_prof.p,(size_t)cells*2,hipMemcpyDeviceToHost));
       else HCHK(hipDeviceSynchronize());
-      clen.assign((size_t)n,0);
+      W.clen.assign((size_t)n,0);
       const int nt = std::min(nthreads,n);
       pool.parallel_for(nt,[&](int64_t t)                            // thread t: a contiguous range of the batch's reads
         { const int r0 = (int)((int64_t)n*t/nt), r1 = (int)((int64_t)n*(t+1)/nt);
@@ -251,24 +159,12 @@ int main(int argc, char **argv)
             { const int64_t np = B.poff[(size_t)r+1]-B.poff[(size_t)r];
               const int64_t l = cp_encode_profile(h_prof.data()+B.poff[(size_t)r],(int)np,c.data()+o,(int64_t)c.size()-o);
               if (l < 0) cp_die((int)l,"cp_encode_profile");
-              clen[(size_t)r] = l;
+              W.clen[(size_t)r] = l;
               o += l;
             }
         });
       for (int t = 0; t < nt; t++)
-        { const int r0 = (int)((int64_t)n*t/nt), r1 = (int)((int64_t)n*(t+1)/nt);
-          int64_t o = 0;
-          for (int r = r0; r < r1; r++, done++)
-            { while (done >= parts[(size_t)part].first+parts[(size_t)part].n) part++;
-              Part &P = parts[(size_t)part];
-              const int64_t l = clen[(size_t)r];
-              if (l > 0 && fwrite(code[(size_t)t].data()+o,1,(size_t)l,P.f) != (size_t)l)
-                die("%s: Cannot write %s\n",PROG,P.name.c_str());
-              o += l;
-              P.bytes += l;
-              P.ends.push_back(P.bytes);
-            }
-        }
+        W.append((int)((int64_t)n*t/nt),(int)((int64_t)n*(t+1)/nt),code[(size_t)t].data());
       B.clear();
     };
   S.rewind();
@@ -283,16 +179,7 @@ int main(int argc, char **argv)
   if (again != nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
   rc = cp_kmer_counts_stats(T,&st);
   if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_stats");
-  for (int p = 0; p < nparts; p++)
-    { Part &P = parts[(size_t)p];
-      if (fclose(P.f) != 0) die("%s: Cannot write %s\n",PROG,P.name.c_str());
-      const std::string nm = odir+"/."+oname+".pidx."+std::to_string(p+1);
-      FILE *f = fopen(nm.c_str(),"wb");
-      if (!f) die("%s: Cannot open %s for 'w'\n",PROG,nm.c_str());
-      bool ok = fwrite(&K,4,1,f) == 1 && fwrite(&P.first,8,1,f) == 1 && fwrite(&P.n,8,1,f) == 1
-                && (P.n == 0 || fwrite(P.ends.data(),8,(size_t)P.n,f) == (size_t)P.n);
-      if (fclose(f) != 0 || !ok) die("%s: Cannot write %s\n",PROG,nm.c_str());
-    }
+  W.close();
   if (verbose)
     fprintf(stderr,"%lld reads, %lld bases, %lld k-mers counted, %lld distinct, %lld skipped, %lld slots, %lld growth steps, "
                    "%d profile parts\n",(long long)nreads,(long long)nbases,(long long)st.n_kmers,(long long)st.n_distinct,

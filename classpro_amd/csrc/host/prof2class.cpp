@@ -5,15 +5,10 @@
 //   prof2class <relative_profile>[.prof] <source>[.db|.dam|.f[ast][aq][.gz]]
 // writes <dir of profile>/<profile root>.class with one "@name comment\nseq\n+\nlabels\n" record per
 // read, K-1 leading 'N's.  Sources: FASTX (kseq semantics) or a Dazzler .db/.dam (dazz_db.h).
-#include <fcntl.h>
-#include <unistd.h>
 #include "host_io.h"
 #include "dazz_db.h"
 #include "class_record.h"
 #include "../cp_host_setup.h"
-
-static const char *EXT[10] = { ".db", ".dam", ".fastq", ".fasta", ".fq", ".fa",
-                               ".fastq.gz", ".fasta.gz", ".fq.gz", ".fa.gz" };          // prof2class.c:22-24
 
 int main(int argc, char **argv)
 { PROG = "prof2class";
@@ -31,14 +26,11 @@ int main(int argc, char **argv)
   std::string out_path = path_to(pos[0])+"/"+root_of(pos[0],".prof")+".class";
   FILE *out = fopen(out_path.c_str(),"w");
   if (!out) die("%s: Cannot open %s for 'w'\n",PROG,out_path.c_str());
-  std::string source; int idx;
-  for (idx = 0; idx < 10; idx++)
-    { source = path_to(pos[1])+"/"+root_of(pos[1],EXT[idx])+EXT[idx];
-      int fd = open(source.c_str(),O_RDONLY);
-      if (fd >= 0) { close(fd); break; }
-    }
+  std::string dir, root;
+  const int idx = find_source(pos[1],&dir,&root);                          // prof2class.c:22-24
   if (idx == 10)
     die("Cannot open %s as a .db|.dam or .f{ast}[aq][.gz] file\n",pos[1].c_str());
+  const std::string source = dir+"/"+root+EXT[idx];
   const bool is_db = idx <= 1, is_dam = idx == 1;
 
   Profiles P;

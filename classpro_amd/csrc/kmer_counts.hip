@@ -1,7 +1,9 @@
 // kmer_counts.hip -- k-mer count table on the device (kprof): how often each distinct canonical k-mer occurs in the
 // batches added, then the per-read count profiles and the FASTK histogram of those counts.  Semantics:
 // include/classpro_amd.h, "K-mer count table".  Included by capi.hip after kmer_table.hip (set_err, HIPCHK and the
-// library's error contract are shared); keys, hash, claim protocol, lookup and walk come from kt_common.h.
+// library's error contract are shared); keys, hash, claim protocol, lookup and walk come from kt_common.h, the table's
+// life cycle (creation, growth, the add driver, destruction) from kt_store.h.  This file holds what is the count
+// table's own: slot, counters, the add, profile, relative-label and histogram kernels and their entry points.
 //
 // One slot per key: hi, lo, a 64-bit count that cannot wrap (at most one add per base ever seen), and a pad word that
 // keeps the slot at 32 bytes: a slot then never spans two 64-byte memory requests, and a probe costs what a probe of the
@@ -12,19 +14,16 @@
 //   rel labels a read-only lookup per position of a batch of another sequence set; labels staged in LDS (see there);
 //   histogram  a slot sweep, counts below 256 binned in LDS per block, the tail by 64-bit global atomics.
 // The per-lane tallies (claims, failures, skips, adds) are summed over the wave first: one atomic per wave and counter.
+#include "kt_store.h"
 
 #define KC_ERR_ABSENT 1u                   // a profile pass met a k-mer that was never added
 #define KC_LOW_BINS   256                  // histogram bins kept in LDS per block
 #define KC_CELLS      (KT_BLOCK*KT_CHUNK)  // k-mer positions (at most that many profile cells) per block
 
 struct kc_slot { unsigned long long hi, lo, cnt, pad; };
-static_assert(sizeof(kc_slot) == 32, "one 32-byte slot per key");
 
 struct kc_ctl                                                                 // device-side counters of one table
-  { unsigned long long n_fail;            // failed inserts of the last add / replay launch
-    unsigned long long n_occ;             // occupied slots = distinct keys
-    unsigned long long n_skip;            // k-mer positions skipped (a byte other than upper-case A C G T)
-    unsigned long long n_rfail;           // failed inserts of the last rehash
+  { unsigned long long n_fail, n_occ, n_skip, n_rfail;                        // the store's: kt_store.h
     unsigned long long n_add;             // counted occurrences
     unsigned int err, pad;
   };
@@ -62,31 +61,6 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_add_kernel(kc_slot *tab, unsigned
   kc_wave_add(&ctl->n_occ,nocc);
   kc_wave_add(&ctl->n_add,nadd);
   if (!REPLAY) kc_wave_add(&ctl->n_skip,nskip);
-}
-
-__global__ void __launch_bounds__(KT_BLOCK) kc_fill_kernel(kc_slot *tab, unsigned long long n)
-{ for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
-       s += (unsigned long long)gridDim.x*blockDim.x)
-    { kc_slot e = {};
-      e.hi = e.lo = KT_EMPTY;
-      tab[s] = e;
-    }
-}
-
-// every occupied slot of `old` into `tab` (distinct keys: each lane claims a slot of its own, then stores its count)
-__global__ void __launch_bounds__(KT_BLOCK) kc_rehash_kernel(const kc_slot *old, unsigned long long n_old, kc_slot *tab,
-                                                             unsigned long long mask, kc_ctl *ctl)
-{ unsigned long long nfail = 0;
-  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n_old;
-       s += (unsigned long long)gridDim.x*blockDim.x)
-    { const kc_slot o = old[s];
-      if (o.lo == KT_EMPTY) continue;
-      bool claimed = false;
-      kc_slot *e = kt_find_or_claim(tab,mask,o.hi,o.lo,&claimed);
-      if (!e || !claimed) { nfail++; continue; }
-      e->cnt = o.cnt;
-    }
-  if (nfail) atomicAdd(&ctl->n_rfail,nfail);
 }
 
 // The prof cell of the k-mer position j of read r is prof_off[r] + j - seq_off[r] - (K-1).  Cells follow the k-mer
@@ -325,62 +299,9 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_hist_kernel(const kc_slot *tab, u
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 
-struct cp_kmer_counts
-  { int K, device;
-    kc_slot *tab;
-    unsigned long long slots;
-    kc_ctl *ctl;                         // device
-    kc_ctl *h_ctl;                       // pinned host copy
-    unsigned int *fail[2];               // failure bitmaps, 1 bit per base position of a batch
-    size_t fail_words;
-    int64_t growths;
-    bool unsized;                        // created with initial_slots = 0 and nothing added yet: the first add sizes it
-    hipStream_t stream;                  // stream of the last call that queued work
+struct cp_kmer_counts : kt_store<kc_slot,kc_ctl>
+  { bool unsized;                        // created with initial_slots = 0 and nothing added yet: the first add sizes it
   };
-
-static int kc_alloc_table(kc_slot **out, unsigned long long slots, hipStream_t st)
-{ void *p = nullptr;
-  hipError_t e = hipMalloc(&p,(size_t)slots*sizeof(kc_slot));
-  if (e != hipSuccess)
-    { (void)hipGetLastError();
-      char m[160];
-      snprintf(m,sizeof(m),"cp_kmer_counts: hipMalloc(%llu slots, %llu bytes): %s",slots,
-               (unsigned long long)(slots*sizeof(kc_slot)),hipGetErrorString(e));
-      return set_err(CP_ENOMEM,m);
-    }
-  kc_fill_kernel<<<kt_grid(slots),KT_BLOCK,0,st>>>((kc_slot *)p,slots);
-  *out = (kc_slot *)p;
-  return CP_OK;
-}
-
-static int kc_sync_ctl(cp_kmer_counts *t, hipStream_t st)
-{ HIPCHK(hipMemcpyAsync(t->h_ctl,t->ctl,sizeof(kc_ctl),hipMemcpyDeviceToHost,st));
-  HIPCHK(hipStreamSynchronize(st));
-  return CP_OK;
-}
-
-// rehash into a table of at least `want` slots (a power of two, > slots); the old table stays intact on failure
-static int kc_grow(cp_kmer_counts *t, unsigned long long want, hipStream_t st)
-{ for (int attempt = 0; attempt < 4; attempt++, want <<= 1)
-    { kc_slot *nt = nullptr;
-      int rc = kc_alloc_table(&nt,want,st);
-      if (rc != CP_OK) return rc;
-      HIPCHK(hipMemsetAsync(&t->ctl->n_rfail,0,sizeof(unsigned long long),st));
-      kc_rehash_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,nt,want-1,t->ctl);
-      HIPCHK(hipGetLastError());
-      rc = kc_sync_ctl(t,st);
-      if (rc != CP_OK) { (void)hipFree(nt); return rc; }
-      if (t->h_ctl->n_rfail == 0)
-        { HIPCHK(hipFree(t->tab));
-          t->tab = nt;
-          t->slots = want;
-          t->growths++;
-          return CP_OK;
-        }
-      HIPCHK(hipFree(nt));                                 // a probe run too long in the new table: larger still
-    }
-  return set_err(CP_ENOMEM,"cp_kmer_counts: rehash kept failing its probe bound");
-}
 
 extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_counts **out)
 { if (!out) return set_err(CP_EINVAL,"cp_kmer_counts_create: null out");
@@ -391,21 +312,10 @@ extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_count
     return set_err(CP_EINVAL,"cp_kmer_counts_create: bad initial_slots");
   cp_kmer_counts *t = new (std::nothrow) cp_kmer_counts();
   if (!t) return set_err(CP_ENOMEM,"cp_kmer_counts_create: out of memory");
-  t->K = K;
   t->unsized = initial_slots == 0;
-  t->slots = kt_pow2_at_least(initial_slots > 0 ? (unsigned long long)initial_slots : (1ull << 20));
-  hipError_t e = hipGetDevice(&t->device);
-  if (e == hipSuccess) e = hipMalloc(&t->ctl,sizeof(kc_ctl));
-  if (e == hipSuccess) e = hipHostMalloc(&t->h_ctl,sizeof(kc_ctl),hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemset(t->ctl,0,sizeof(kc_ctl));
-  int rc = CP_OK;
-  if (e == hipSuccess)
-    { rc = kc_alloc_table(&t->tab,t->slots,nullptr);
-      if (rc == CP_OK) e = hipStreamSynchronize(nullptr);
-    }
-  if (e != hipSuccess || rc != CP_OK)
-    { if (e != hipSuccess) rc = set_err(CP_EHIP,std::string("cp_kmer_counts_create: ")+hipGetErrorString(e));
-      cp_kmer_counts_destroy(t);
+  const int rc = kt_init(t,"cp_kmer_counts",K,initial_slots);
+  if (rc != CP_OK)
+    { cp_kmer_counts_destroy(t);
       return rc;
     }
   *out = t;
@@ -414,12 +324,7 @@ extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_count
 
 extern "C" void cp_kmer_counts_destroy(cp_kmer_counts *t)
 { if (!t) return;
-  (void)hipDeviceSynchronize();
-  if (t->tab) (void)hipFree(t->tab);
-  if (t->ctl) (void)hipFree(t->ctl);
-  if (t->h_ctl) (void)hipHostFree(t->h_ctl);
-  for (int i = 0; i < 2; i++)
-    if (t->fail[i]) (void)hipFree(t->fail[i]);
+  kt_free(t);
   delete t;
 }
 
@@ -429,57 +334,15 @@ extern "C" int cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const in
   if (nreads == 0 || total_bases == 0) return CP_OK;
   if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_add: null device pointer");
   hipStream_t st = (hipStream_t)stream;
-  t->stream = st;
-  const size_t words = (size_t)((total_bases+31)/32);
-  if (words > t->fail_words)
-    { HIPCHK(hipStreamSynchronize(st));
-      for (int i = 0; i < 2; i++)
-        { if (t->fail[i]) { (void)hipFree(t->fail[i]); t->fail[i] = nullptr; }
-          if (hipMalloc(&t->fail[i],words*4) != hipSuccess)
-            { (void)hipGetLastError();
-              t->fail_words = 0;
-              return set_err(CP_ENOMEM,"cp_kmer_counts_add: cannot allocate the failure bitmap");
-            }
-        }
-      t->fail_words = words;
-    }
-  if (t->unsized)
-    { // The first batch into a table of the default size: room for every k-mer of the batch at half load, so that it
-      // does not run through a table it cannot fit into (each failed insert costs KT_PROBE probes and a replay).  The
-      // table is empty, so there is nothing to rehash; when the allocation fails the usual growth takes over.
-      t->unsized = false;
-      const unsigned long long want = kt_pow2_at_least(2*(unsigned long long)total_bases);
-      kc_slot *nt = nullptr;
-      if (want > t->slots && kc_alloc_table(&nt,want,st) == CP_OK)
-        { HIPCHK(hipStreamSynchronize(st));
-          HIPCHK(hipFree(t->tab));
-          t->tab = nt;
-          t->slots = want;
-        }
-    }
   const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
-  HIPCHK(hipMemsetAsync(t->fail[0],0,words*4,st));
-  HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
-  kc_add_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,nullptr,
-                                               t->fail[0],t->ctl);
-  HIPCHK(hipGetLastError());
-  // the one read-back: failed inserts and occupancy.  Failures: grow, replay only them; then keep the load <= 1/2.
-  for (int round = 0; ; round++)
-    { int rc = kc_sync_ctl(t,st);
-      if (rc != CP_OK) return rc;
-      const unsigned long long nfail = t->h_ctl->n_fail, nocc = t->h_ctl->n_occ;
-      if (nfail == 0 && 2*nocc <= t->slots) return CP_OK;
-      if (round >= 16) return set_err(CP_ENOMEM,"cp_kmer_counts_add: the table did not settle after 16 growth steps");
-      rc = kc_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+nfail))),st);
-      if (rc != CP_OK) return rc;
-      if (nfail == 0) continue;
-      HIPCHK(hipMemsetAsync(t->fail[1],0,words*4,st));
-      HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
-      kc_add_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,t->fail[0],
-                                                  t->fail[1],t->ctl);
-      HIPCHK(hipGetLastError());
-      std::swap(t->fail[0],t->fail[1]);
-    }
+  return kt_add(t,total_bases,st,&t->unsized,[&](bool replay, const unsigned int *fail_in, unsigned int *fail_out)
+    { if (replay)
+        kc_add_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,fail_in,
+                                                    fail_out,t->ctl);
+      else
+        kc_add_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,fail_in,
+                                                     fail_out,t->ctl);
+    });
 }
 
 extern "C" int cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off,
@@ -559,7 +422,7 @@ extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *il
 extern "C" int cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out)
 { if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_counts_stats: bad argument");
   hipStream_t st = t->stream;
-  int rc = kc_sync_ctl(t,st);
+  int rc = kt_sync_ctl(t,st);
   if (rc != CP_OK) return rc;
   if (t->h_ctl->err)                                       // deferred device errors: reported once, then cleared
     { HIPCHK(hipMemsetAsync(&t->ctl->err,0,sizeof(unsigned int),st));

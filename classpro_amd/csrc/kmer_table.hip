@@ -1,26 +1,24 @@
 // kmer_table.hip -- per-k-mer label table on the device (class2cns): how often each distinct k-mer of a labelled batch
 // got each of the labels E/H/D/R, the consensus label per k-mer and the consistency figure of the reference's
 // scripts/agg2cons.py.  Semantics: include/classpro_amd.h, "Per-k-mer label table".  Included by capi.hip (set_err,
-// HIPCHK and the library's error contract are shared).
+// HIPCHK and the library's error contract are shared).  This file holds what is the label table's own: slot, counters,
+// the add, statistics, consensus and export kernels and their entry points.
 //
 // The table is open addressing with linear probing, one 32-byte slot per key: hi = key bits 125..63, lo = key bits
 // 62..0, four u32 counts.  Keys, the hash, the claim protocol, the lookup and the walk over a batch's k-mers are shared
 // with the count table (kmer_counts.hip): kt_common.h.  An insert finds or claims its key's slot and adds one count; one
 // that runs past the probe bound (KT_PROBE) sets its position's bit in a failure bitmap and adds nothing.  The host then
-// grows the table (rehash into at least twice the slots) and replays exactly the failed positions.
-#include "kt_common.h"
+// grows the table (rehash into at least twice the slots) and replays exactly the failed positions: kt_store.h, which
+// holds the life cycle of both tables (creation, growth, the add driver, destruction).
+#include "kt_store.h"
 
 #define KT_ERR_LABEL    1u                 // a counted position held a label other than E/H/D/R
 #define KT_ERR_OVERFLOW 2u                 // a count passed 2^32-1
 
 struct kt_slot { unsigned long long hi, lo; unsigned int cnt[4]; };          // cnt in label order E, H, D, R
-static_assert(sizeof(kt_slot) == 32, "one 32-byte slot per key");
 
 struct kt_ctl                                                                 // device-side counters of one table
-  { unsigned long long n_fail;            // failed inserts of the last add / replay launch
-    unsigned long long n_occ;             // occupied slots = distinct keys
-    unsigned long long n_skip;            // k-mer positions skipped (a base other than upper-case A C G T)
-    unsigned long long n_rfail;           // failed inserts of the last rehash
+  { unsigned long long n_fail, n_occ, n_skip, n_rfail;                        // the store's: kt_store.h
     unsigned long long n_out;             // export: entries written
     unsigned int err, pad;
   };
@@ -68,32 +66,6 @@ __global__ void __launch_bounds__(KT_BLOCK) kt_add_kernel(kt_slot *tab, unsigned
   if (nocc) atomicAdd(&ctl->n_occ,nocc);
   if (!REPLAY && nskip) atomicAdd(&ctl->n_skip,nskip);
   if (err) atomicOr(&ctl->err,err);
-}
-
-__global__ void __launch_bounds__(KT_BLOCK) kt_fill_kernel(kt_slot *tab, unsigned long long n)
-{ for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
-       s += (unsigned long long)gridDim.x*blockDim.x)
-    { kt_slot e;
-      e.hi = e.lo = KT_EMPTY;
-      e.cnt[0] = e.cnt[1] = e.cnt[2] = e.cnt[3] = 0;
-      tab[s] = e;
-    }
-}
-
-// every occupied slot of `old` into `tab` (distinct keys: each lane claims a slot of its own, then stores its counts)
-__global__ void __launch_bounds__(KT_BLOCK) kt_rehash_kernel(const kt_slot *old, unsigned long long n_old, kt_slot *tab,
-                                                             unsigned long long mask, kt_ctl *ctl)
-{ unsigned long long nfail = 0;
-  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n_old;
-       s += (unsigned long long)gridDim.x*blockDim.x)
-    { const kt_slot o = old[s];
-      if (o.lo == KT_EMPTY) continue;
-      bool claimed = false;
-      kt_slot *e = kt_find_or_claim(tab,mask,o.hi,o.lo,&claimed);
-      if (!e || !claimed) { nfail++; continue; }
-      e->cnt[0] = o.cnt[0]; e->cnt[1] = o.cnt[1]; e->cnt[2] = o.cnt[2]; e->cnt[3] = o.cnt[3];
-    }
-  if (nfail) atomicAdd(&ctl->n_rfail,nfail);
 }
 
 // per-block partial statistics over the occupied slots (integer sums only: the result does not depend on the order)
@@ -169,62 +141,10 @@ __global__ void __launch_bounds__(KT_BLOCK) kt_export_kernel(const kt_slot *tab,
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 
-struct cp_kmer_table
-  { int K, canonical, device;
-    kt_slot *tab;
-    unsigned long long slots;
-    kt_ctl *ctl;                         // device
-    kt_ctl *h_ctl;                       // pinned host copy
-    unsigned int *fail[2];               // failure bitmaps, 1 bit per base position of a batch
-    size_t fail_words;
-    int64_t growths;
+struct cp_kmer_table : kt_store<kt_slot,kt_ctl>
+  { int canonical;
     bool overflowed;                     // sticky: a count passed 2^32-1
-    hipStream_t stream;                  // stream of the last call that queued work
   };
-
-static int kt_alloc_table(kt_slot **out, unsigned long long slots, hipStream_t st)
-{ void *p = nullptr;
-  hipError_t e = hipMalloc(&p,(size_t)slots*sizeof(kt_slot));
-  if (e != hipSuccess)
-    { (void)hipGetLastError();
-      char m[160];
-      snprintf(m,sizeof(m),"cp_kmer_table: hipMalloc(%llu slots, %llu bytes): %s",slots,
-               (unsigned long long)(slots*sizeof(kt_slot)),hipGetErrorString(e));
-      return set_err(CP_ENOMEM,m);
-    }
-  kt_fill_kernel<<<kt_grid(slots),KT_BLOCK,0,st>>>((kt_slot *)p,slots);
-  *out = (kt_slot *)p;
-  return CP_OK;
-}
-
-static int kt_sync_ctl(cp_kmer_table *t, hipStream_t st)
-{ HIPCHK(hipMemcpyAsync(t->h_ctl,t->ctl,sizeof(kt_ctl),hipMemcpyDeviceToHost,st));
-  HIPCHK(hipStreamSynchronize(st));
-  return CP_OK;
-}
-
-// rehash into a table of at least `want` slots (a power of two, > slots); the old table stays intact on failure
-static int kt_grow(cp_kmer_table *t, unsigned long long want, hipStream_t st)
-{ for (int attempt = 0; attempt < 4; attempt++, want <<= 1)
-    { kt_slot *nt = nullptr;
-      int rc = kt_alloc_table(&nt,want,st);
-      if (rc != CP_OK) return rc;
-      HIPCHK(hipMemsetAsync(&t->ctl->n_rfail,0,sizeof(unsigned long long),st));
-      kt_rehash_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,nt,want-1,t->ctl);
-      HIPCHK(hipGetLastError());
-      rc = kt_sync_ctl(t,st);
-      if (rc != CP_OK) { (void)hipFree(nt); return rc; }
-      if (t->h_ctl->n_rfail == 0)
-        { HIPCHK(hipFree(t->tab));
-          t->tab = nt;
-          t->slots = want;
-          t->growths++;
-          return CP_OK;
-        }
-      HIPCHK(hipFree(nt));                                 // a probe run too long in the new table: larger still
-    }
-  return set_err(CP_ENOMEM,"cp_kmer_table: rehash kept failing its probe bound");
-}
 
 extern "C" int cp_kmer_table_create(int K, int canonical, int64_t initial_slots, cp_kmer_table **out)
 { if (!out) return set_err(CP_EINVAL,"cp_kmer_table_create: null out");
@@ -235,20 +155,10 @@ extern "C" int cp_kmer_table_create(int K, int canonical, int64_t initial_slots,
     return set_err(CP_EINVAL,"cp_kmer_table_create: bad initial_slots");
   cp_kmer_table *t = new (std::nothrow) cp_kmer_table();
   if (!t) return set_err(CP_ENOMEM,"cp_kmer_table_create: out of memory");
-  t->K = K; t->canonical = canonical ? 1 : 0;
-  t->slots = kt_pow2_at_least(initial_slots > 0 ? (unsigned long long)initial_slots : (1ull << 20));
-  hipError_t e = hipGetDevice(&t->device);
-  if (e == hipSuccess) e = hipMalloc(&t->ctl,sizeof(kt_ctl));
-  if (e == hipSuccess) e = hipHostMalloc(&t->h_ctl,sizeof(kt_ctl),hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemset(t->ctl,0,sizeof(kt_ctl));
-  int rc = CP_OK;
-  if (e == hipSuccess)
-    { rc = kt_alloc_table(&t->tab,t->slots,nullptr);
-      if (rc == CP_OK) e = hipStreamSynchronize(nullptr);
-    }
-  if (e != hipSuccess || rc != CP_OK)
-    { if (e != hipSuccess) rc = set_err(CP_EHIP,std::string("cp_kmer_table_create: ")+hipGetErrorString(e));
-      cp_kmer_table_destroy(t);
+  t->canonical = canonical ? 1 : 0;
+  const int rc = kt_init(t,"cp_kmer_table",K,initial_slots);
+  if (rc != CP_OK)
+    { cp_kmer_table_destroy(t);
       return rc;
     }
   *out = t;
@@ -257,12 +167,7 @@ extern "C" int cp_kmer_table_create(int K, int canonical, int64_t initial_slots,
 
 extern "C" void cp_kmer_table_destroy(cp_kmer_table *t)
 { if (!t) return;
-  (void)hipDeviceSynchronize();
-  if (t->tab) (void)hipFree(t->tab);
-  if (t->ctl) (void)hipFree(t->ctl);
-  if (t->h_ctl) (void)hipHostFree(t->h_ctl);
-  for (int i = 0; i < 2; i++)
-    if (t->fail[i]) (void)hipFree(t->fail[i]);
+  kt_free(t);
   delete t;
 }
 
@@ -272,51 +177,15 @@ extern "C" int cp_kmer_table_add(cp_kmer_table *t, const char *d_seq, const int6
   if (nreads == 0 || total_bases == 0) return CP_OK;
   if (!d_seq || !d_seq_off || !d_labels) return set_err(CP_EINVAL,"cp_kmer_table_add: null device pointer");
   hipStream_t st = (hipStream_t)stream;
-  t->stream = st;
-  const size_t words = (size_t)((total_bases+31)/32);
-  if (words > t->fail_words)
-    { HIPCHK(hipStreamSynchronize(st));
-      for (int i = 0; i < 2; i++)
-        { if (t->fail[i]) { (void)hipFree(t->fail[i]); t->fail[i] = nullptr; }
-          if (hipMalloc(&t->fail[i],words*4) != hipSuccess)
-            { (void)hipGetLastError();
-              t->fail_words = 0;
-              return set_err(CP_ENOMEM,"cp_kmer_table_add: cannot allocate the failure bitmap");
-            }
-        }
-      t->fail_words = words;
-    }
   const int grid = (int)((total_bases+(int64_t)KT_BLOCK*KT_CHUNK-1)/((int64_t)KT_BLOCK*KT_CHUNK));
-  HIPCHK(hipMemsetAsync(t->fail[0],0,words*4,st));
-  HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
-  if (t->canonical)
-    kt_add_kernel<true,false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,t->K,
-                                                      nullptr,t->fail[0],t->ctl);
-  else
-    kt_add_kernel<false,false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,t->K,
-                                                       nullptr,t->fail[0],t->ctl);
-  HIPCHK(hipGetLastError());
-  // the one read-back: failed inserts and occupancy.  Failures: grow, replay only them; then keep the load <= 1/2.
-  for (int round = 0; ; round++)
-    { int rc = kt_sync_ctl(t,st);
-      if (rc != CP_OK) return rc;
-      const unsigned long long nfail = t->h_ctl->n_fail, nocc = t->h_ctl->n_occ;
-      if (nfail == 0 && 2*nocc <= t->slots) return CP_OK;
-      if (round >= 16) return set_err(CP_ENOMEM,"cp_kmer_table_add: the table did not settle after 16 growth steps");
-      rc = kt_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+nfail))),st);
-      if (rc != CP_OK) return rc;
-      if (nfail == 0) continue;
-      HIPCHK(hipMemsetAsync(t->fail[1],0,words*4,st));
-      HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
-      if (t->canonical)
-        kt_add_kernel<true,true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,
-                                                         t->K,t->fail[0],t->fail[1],t->ctl);
-      else
-        kt_add_kernel<false,true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases,
-                                                          t->K,t->fail[0],t->fail[1],t->ctl);
-      HIPCHK(hipGetLastError());
-      std::swap(t->fail[0],t->fail[1]);
-    }
+  return kt_add(t,total_bases,st,nullptr,[&](bool replay, const unsigned int *fail_in, unsigned int *fail_out)
+    {
+#define KT_ADD(C,R) kt_add_kernel<C,R><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_labels,nreads,total_bases, \
+                                                               t->K,fail_in,fail_out,t->ctl)
+      if (t->canonical) { if (replay) KT_ADD(true,true); else KT_ADD(true,false); }
+      else { if (replay) KT_ADD(false,true); else KT_ADD(false,false); }
+#undef KT_ADD
+    });
 }
 
 // n_distinct * 2^64 / S, correctly rounded (S >= n_distinct * 2^64 > 0): 64 significant quotient bits by restoring

@@ -1,6 +1,7 @@
-// kt_common.h -- what the two device k-mer tables share: the label table of kmer_table.hip (class2cns) and the count
-// table of kmer_counts.hip (kprof).  Keys, the hash, the lock-free claim protocol over any slot type that begins with
-// the two key words, the read-only lookup, and the rolling walk over the k-mers of a flat batch.
+// kt_common.h -- what the two device k-mer tables share on the device: the label table of kmer_table.hip (class2cns)
+// and the count table of kmer_counts.hip (kprof).  Keys, the hash, the lock-free claim protocol over any slot type that
+// begins with the two key words, the read-only lookup, and the rolling walk over the k-mers of a flat batch.  The host
+// side they share (creation, growth by rehash, the add driver, destruction) is kt_store.h, which includes this file.
 //
 // Both tables are open addressing with linear probing.  A slot starts with hi = key bits 125..63 and lo = key bits
 // 62..0.  A key has at most 126 bits, so the all-ones word never is a half of a key and marks an EMPTY half.  An

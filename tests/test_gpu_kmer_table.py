@@ -166,6 +166,32 @@ def test_growth(torch_dev):
     T.close()
 
 
+@pytest.mark.parametrize("canonical", [False, True], ids=["forward", "canonical"])
+def test_growth_across_batches(torch_dev, canonical):
+    """Three batches of about 39 400 new keys each into 64 slots: the first grows the table to 2^17 slots inside its add,
+    the second passes half of that, so its growth rehashes a table that already holds the counts of an earlier batch."""
+    from classpro_amd.api import KmerTable
+    rng = np.random.default_rng(17)
+    k = 31
+    recs = []
+    for i in range(60):
+        s = bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 2000)])
+        recs.append((b"b%d" % i, s, _labels(random.Random(100 + i), len(s), k)))
+    t, skipped = O.table(recs, k, canonical)
+    got = []
+    for slots in (64, 1 << 20):
+        T = KmerTable(k, canonical=canonical, initial_slots=slots)
+        for b in (recs[:20], recs[20:40], recs[40:]):
+            T.add_tensors(*flat(torch_dev, b))
+        got.append((T.entries(), check_table(T, t, skipped)))
+        T.close()
+    (e_small, s_small), (e_big, s_big) = got
+    assert s_small["growths"] >= 2 and s_big["growths"] == 0 and s_big["slots"] == 1 << 20
+    assert all(np.array_equal(x, y) for x, y in zip(e_small, e_big))
+    drop = ("slots", "bytes", "growths")
+    assert {k_: v for k_, v in s_small.items() if k_ not in drop} == {k_: v for k_, v in s_big.items() if k_ not in drop}
+
+
 def test_consensus(torch_dev, labelled):
     from classpro_amd.api import KmerTable
     k = 5

@@ -88,6 +88,8 @@ def test_library_matches_oracle(torch_dev, small):
     _, seqs, want = small
     s = check(run_table(torch_dev, seqs, K), want)
     assert s["n_distinct"] > 1000 and s["n_skipped"] == 0 and s["slots"] >= 2 * s["n_distinct"]
+    total = sum(len(x) for x in seqs)                  # a first batch past the default table: sized for it, no growth
+    assert 2 * total > 1 << 20 and s["growths"] == 0 and s["slots"] == 1 << (2 * total - 1).bit_length()
     b = Batch.from_seqs(seqs, K)                       # the Batch form fills b.prof in place
     T = KmerCounts(K)
     T.add(b)
@@ -115,6 +117,20 @@ def test_growth(torch_dev, small):
     _, seqs, want = small
     s = check(run_table(torch_dev, seqs, K, initial_slots=64), want)
     assert s["growths"] > 0 and s["slots"] >= 2 * s["n_distinct"]
+
+
+def test_growth_across_batches(torch_dev):
+    """Three batches of about 39 200 new keys each into 64 slots: the first grows the table to 2^17 slots inside its add,
+    the second passes half of that, so its growth rehashes a table that already holds the counts of an earlier batch."""
+    rng = np.random.default_rng(23)
+    seqs = [bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 2000)]) for _ in range(60)]
+    batches = [seqs[:20], seqs[20:40], seqs[40:]]
+    want = O.run(seqs, K)
+    s_small = check(run_table(torch_dev, seqs, K, batches=batches, initial_slots=64), want)
+    s_big = check(run_table(torch_dev, seqs, K, batches=batches, initial_slots=1 << 20), want)
+    assert s_small["growths"] >= 2 and s_big["growths"] == 0 and s_big["slots"] == 1 << 20
+    drop = ("slots", "bytes", "growths")
+    assert {k: v for k, v in s_small.items() if k not in drop} == {k: v for k, v in s_big.items() if k not in drop}
 
 
 def _rc(s):
