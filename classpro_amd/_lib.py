@@ -21,6 +21,7 @@ SYMBOLS = [
     "cp_kmer_table_consensus", "cp_kmer_table_export",
     "cp_kmer_counts_create", "cp_kmer_counts_destroy", "cp_kmer_counts_add", "cp_kmer_counts_profiles",
     "cp_kmer_counts_hist", "cp_kmer_counts_stats", "cp_kmer_counts_rel_labels",
+    "cp_kmer_counts_create_filtered", "cp_kmer_counts_mark", "cp_kmer_counts_filter_stats",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -39,6 +40,12 @@ class KmerCountStats(C.Structure):
     """cp_kmer_count_stats of include/classpro_amd.h."""
     _fields_ = [("n_kmers", C.c_int64), ("n_skipped", C.c_int64), ("n_distinct", C.c_int64), ("slots", C.c_int64),
                 ("bytes", C.c_int64), ("growths", C.c_int64)]
+
+
+class KmerFilterStats(C.Structure):
+    """cp_kmer_filter_stats of include/classpro_amd.h."""
+    _fields_ = [("filter_bits", C.c_int64), ("filter_bytes", C.c_int64), ("n_marked", C.c_int64),
+                ("n_counted", C.c_int64), ("n_table_keys", C.c_int64), ("n_outside", C.c_int64), ("n_false", C.c_int64)]
 
 
 class AccStats(C.Structure):
@@ -131,6 +138,9 @@ def lib():
     L.cp_kmer_counts_hist.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.cp_kmer_counts_stats.argtypes = [vp, C.POINTER(KmerCountStats)]
     L.cp_kmer_counts_rel_labels.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.cp_kmer_counts_create_filtered.argtypes = [i32, i64, i64, C.POINTER(vp)]
+    L.cp_kmer_counts_mark.argtypes = [vp, vp, vp, i32, i64, vp]
+    L.cp_kmer_counts_filter_stats.argtypes = [vp, C.POINTER(KmerFilterStats)]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

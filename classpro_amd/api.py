@@ -429,19 +429,26 @@ class KmerTable:
 class KmerCounts:
     """K-mer count table on the device (cp_kmer_counts_*; semantics in include/classpro_amd.h): counts every canonical
     k-mer of the batches added, then gives the per-read count profiles and the FASTK histogram that ClassPro starts
-    from.  initial_slots only matters for tests that force growth."""
+    from.  initial_slots only matters for tests that force growth.
 
-    def __init__(self, K, device="cuda:0", initial_slots=0):
-        from ._lib import KmerCountStats
+    With filter_bits > 0 (rounded up to a power of two in [64, 2^40]) the table is a FILTERED one, which keeps the
+    k-mers seen once out of its slots: `mark` every batch, then `add` the same batches, then `profiles`.  Profiles,
+    histogram and n_kmers, n_distinct, n_skipped are those of the unfiltered table, exactly; `rel_labels` is refused."""
+
+    def __init__(self, K, device="cuda:0", initial_slots=0, filter_bits=0):
+        from ._lib import KmerCountStats, KmerFilterStats
         self.L = lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("classpro_amd runs on a HIP device only")
         torch.cuda.set_device(self.device)
         self.K = K
-        self._Stats = KmerCountStats
+        self._Stats, self._FilterStats = KmerCountStats, KmerFilterStats
         t = C.c_void_p()
-        check(self.L.cp_kmer_counts_create(K, int(initial_slots), C.byref(t)))
+        if filter_bits:
+            check(self.L.cp_kmer_counts_create_filtered(K, int(initial_slots), int(filter_bits), C.byref(t)))
+        else:
+            check(self.L.cp_kmer_counts_create(K, int(initial_slots), C.byref(t)))
         self.t = t
 
     def _stream(self):
@@ -468,6 +475,23 @@ class KmerCounts:
         """Adds the reads of a `Batch`."""
         check(self.L.cp_kmer_counts_add(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.nreads, b.total_bases,
                                         self._stream()))
+
+    def mark_tensors(self, seq, seq_off):
+        """The mark pass of a filtered table over a batch given as device tensors (as `add_tensors`)."""
+        n = seq_off.numel() - 1
+        total = int(seq_off[-1].item()) if n > 0 else 0
+        check(self.L.cp_kmer_counts_mark(self.t, seq.data_ptr(), seq_off.data_ptr(), n, total, self._stream()))
+
+    def mark(self, b):
+        """The mark pass of a filtered table over the reads of a `Batch`: every batch is marked before the first `add`."""
+        check(self.L.cp_kmer_counts_mark(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.nreads, b.total_bases,
+                                         self._stream()))
+
+    def filter_stats(self):
+        """dict: filter_bits, filter_bytes, n_marked, n_counted, n_table_keys, n_outside, n_false (cp_kmer_filter_stats)."""
+        s = self._FilterStats()
+        check(self.L.cp_kmer_counts_filter_stats(self.t, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
     def profiles(self, batch):
         """Count profiles of a `Batch` (its `prof` tensor is filled in place, ready for Classifier.classify) or of a

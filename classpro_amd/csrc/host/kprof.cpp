@@ -1,7 +1,7 @@
 // kprof.cpp -- k-mer count profiles and histogram from reads alone: what `FastK -k<K> -t1 -p` leaves for ClassPro,
 // counted on the GPU.
 //
-//   kprof [-v] [-k<int(40)>] [-T<int(4)>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]
+//   kprof [-v] [-k<int(40)>] [-T<int(4)>] [-f<int>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]
 //
 // Writes <root>.hist, <root>.prof, .<root>.pidx.1..n and .<root>.prof.1..n (layout: classpro_amd/fastk.py), <root> being
 // the source's path without its extension, or -N.  The source is found as ClassPro finds it: the first of .db .dam
@@ -11,8 +11,13 @@
 //   1. bases up, added to the count table;
 //   2. bases up again, uint16 counts down, and the -T host threads encode them with cp_encode_profile.  Part p of
 //      nparts = min(T, reads) holds the reads [reads*p/nparts, reads*(p+1)/nparts).
+// -f<MiB> puts a singleton filter of that many MiB (rounded up to a power of two, at most 131072) in front of the table
+// ("Filtered count table" in include/classpro_amd.h): the k-mers seen once then take no slot, at the price of a third
+// pass over the reads -- mark, count, profile.  The files written are byte for byte those written without -f; absent or
+// 0 means no filter and the two passes above.
 // A k-mer with a byte other than upper-case A C G T is not counted and gets count 0; how many there were is always said
 // on stderr.  FastK's own treatment of such bases is not reproduced.
+#include <cerrno>
 #include "gpu_tool.h"
 #include "read_source.h"
 #include "prof_writer.h"
@@ -20,6 +25,7 @@
 
 static const char *USAGE = "[-v] [-k<int(40)>] [-T<int(4)>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]";
 
+static const long long MAX_FILTER_MIB = 1ll << 17;           // 2^40 bits, the library's limit
 static const int64_t BATCH_BASES = (int64_t)64 << 20;        // bases per device batch
 
 struct Batch
@@ -33,6 +39,7 @@ int main(int argc, char **argv)
 { PROG = "kprof";
   bool verbose = false;
   int K = 40, nthreads = 4;
+  int64_t filter_mib = 0;
   std::string out_root;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; i++)
@@ -48,6 +55,17 @@ int main(int argc, char **argv)
           case 'k': K = arg_int(a,"K-mer length",true); break;
           case 'T': nthreads = arg_int(a,"Number of threads",true); break;
           case 'N': out_root = a+2; break;
+          case 'f':
+            { char *end;
+              errno = 0;
+              const long long v = strtoll(a+2,&end,10);
+              if (*end != '\0' || a[2] == '\0')
+                die("%s: -f '%s' argument is not an integer\n",PROG,a+2);
+              if (errno != 0 || v < 0 || v > MAX_FILTER_MIB)
+                die("%s: Filter size must lie in [0, %lld] MiB (%s)\n",PROG,MAX_FILTER_MIB,a+2);
+              filter_mib = v;
+              break;
+            }
         }
       else
         pos.push_back(a);
@@ -73,7 +91,7 @@ int main(int argc, char **argv)
     fprintf(stderr,"Input = %s, K = %d, outputs = %s.hist, %s.prof, %s/.%s.{pidx,prof}.*\n",S.path.c_str(),K,
             (odir+"/"+oname).c_str(),(odir+"/"+oname).c_str(),odir.c_str(),oname.c_str());
 
-  // ---- pass 1: count ----
+  // ---- pass 1: count (with -f: mark, then count) ----
   const int Km1 = K-1;
   cp_kmer_counts *T = nullptr;
   DevBuf<char> d_seq;
@@ -84,7 +102,8 @@ int main(int argc, char **argv)
   auto device_up = [&]()                                            // the first device work of the process
     { if (T) return;
       HCHK(hipSetDevice(0));
-      const int rc = cp_kmer_counts_create(K,0,&T);
+      const int rc = filter_mib ? cp_kmer_counts_create_filtered(K,0,filter_mib << 23,&T)
+                                : cp_kmer_counts_create(K,0,&T);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_create");
     };
   auto push = [&]()
@@ -99,11 +118,13 @@ int main(int argc, char **argv)
       if (!B.seq.empty()) HCHK(hipMemcpy(d_seq.p,B.seq.data(),B.seq.size(),hipMemcpyHostToDevice));
       d_soff.up(B.soff);
     };
+  bool marking = filter_mib != 0;                                   // with -f: the mark pass comes first
   auto add = [&]()
     { if (B.n() == 0) return;
       upload();
-      const int rc = cp_kmer_counts_add(T,d_seq.p,d_soff.p,B.n(),B.soff.back(),nullptr);
-      if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_add");
+      const int rc = marking ? cp_kmer_counts_mark(T,d_seq.p,d_soff.p,B.n(),B.soff.back(),nullptr)
+                             : cp_kmer_counts_add(T,d_seq.p,d_soff.p,B.n(),B.soff.back(),nullptr);
+      if (rc != CP_OK) cp_die(rc,marking ? "cp_kmer_counts_mark" : "cp_kmer_counts_add");
       B.clear();
     };
   while (S.next())
@@ -114,6 +135,19 @@ int main(int argc, char **argv)
     }
   add();
   device_up();
+  if (marking)                                                      // the same reads again, counted
+    { marking = false;
+      S.rewind();
+      int64_t again = 0;
+      while (S.next())
+        { if (again >= nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+          push();
+          again++;
+          if (B.soff.back() >= BATCH_BASES) add();
+        }
+      add();
+      if (again != nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+    }
 
   cp_kmer_count_stats st;
   int rc = cp_kmer_counts_stats(T,&st);
@@ -180,10 +214,20 @@ int main(int argc, char **argv)
   rc = cp_kmer_counts_stats(T,&st);
   if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_stats");
   W.close();
+  std::string filtered;                                             // what -f adds to the -v line
+  if (verbose && filter_mib)
+    { cp_kmer_filter_stats fs;
+      rc = cp_kmer_counts_filter_stats(T,&fs);
+      if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_filter_stats");
+      char m[200];
+      snprintf(m,sizeof(m),", %lld table keys, %lld keys kept outside, %lld false positives, %lld filter bytes",
+               (long long)fs.n_table_keys,(long long)fs.n_outside,(long long)fs.n_false,(long long)fs.filter_bytes);
+      filtered = m;
+    }
   if (verbose)
     fprintf(stderr,"%lld reads, %lld bases, %lld k-mers counted, %lld distinct, %lld skipped, %lld slots, %lld growth steps, "
-                   "%d profile parts\n",(long long)nreads,(long long)nbases,(long long)st.n_kmers,(long long)st.n_distinct,
-            (long long)st.n_skipped,(long long)st.slots,(long long)st.growths,nparts);
+                   "%d profile parts%s\n",(long long)nreads,(long long)nbases,(long long)st.n_kmers,(long long)st.n_distinct,
+            (long long)st.n_skipped,(long long)st.slots,(long long)st.growths,nparts,filtered.c_str());
   if (st.n_skipped)
     fprintf(stderr,"%s: %lld k-mer positions skipped (a byte other than upper-case A C G T): their count is 0\n",PROG,
             (long long)st.n_skipped);

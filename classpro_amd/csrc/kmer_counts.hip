@@ -13,6 +13,15 @@
 //   profile    a read-only lookup per position; a block stages its 16384 cells in LDS and stores them as 32-bit words;
 //   rel labels a read-only lookup per position of a batch of another sequence set; labels staged in LDS (see there);
 //   histogram  a slot sweep, counts below 256 binned in LDS per block, the tail by 64-bit global atomics.
+// A FILTERED table (cp_kmer_counts_create_filtered) keeps the keys seen once out of the slots.  A bit
+// array in device memory stands in front of the table; a key owns one 64-bit word of it and up to four bits in that word.
+//   mark       one returning 64-bit atomic OR per position tests and sets the key's bits; only a key whose bits were all
+//              set already is claimed in the table (no count yet).  Atomics on one word are totally ordered, so of two or
+//              more occurrences of a key at most one finds a bit unset: every key that occurs twice is in the table.
+//              Failed claims go through the same failure bitmap, growth and replay; a replay does not ask the filter again.
+//   count      the keys are fixed now: a read-only lookup per position, a 64-bit atomic add on a key that is there, a
+//              tally (n_single) of those that are not -- each of them occurs exactly once.
+//   profile    the same kernel with "absent = 1".
 // The per-lane tallies (claims, failures, skips, adds) are summed over the wave first: one atomic per wave and counter.
 #include "kt_store.h"
 
@@ -26,6 +35,8 @@ struct kc_ctl                                                                 //
   { unsigned long long n_fail, n_occ, n_skip, n_rfail;                        // the store's: kt_store.h
     unsigned long long n_add;             // counted occurrences
     unsigned int err, pad;
+    unsigned long long n_mark;            // filtered table: valid k-mer positions of the mark passes
+    unsigned long long n_single;          // filtered table: positions of the count passes whose key is not in the table
   };
 
 // adds the wave's sum of v to *dst (one atomic per wave; every lane of the wave must call)
@@ -63,6 +74,77 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_add_kernel(kc_slot *tab, unsigned
   if (!REPLAY) kc_wave_add(&ctl->n_skip,nskip);
 }
 
+// The filter of a filtered table: `wmask`+1 64-bit words.  The word and the four bit positions of a key come from a hash
+// of their own: the same mixer as kt_home with another constant, word index from bits 24.., bit positions from the four
+// 6-bit fields below them (some of the four may coincide), so nothing is shared with the slot index (kt_home's low bits).
+#define KF_SALT 0xd6e8feb86659fd93ull
+
+__host__ __device__ static inline unsigned long long kf_hash(unsigned long long hi, unsigned long long lo)
+{ return kt_mix(lo ^ kt_mix(hi ^ KF_SALT)); }
+
+__host__ __device__ static inline unsigned long long kf_bits(unsigned long long h)
+{ return (1ull << (h & 63)) | (1ull << ((h >> 6) & 63)) | (1ull << ((h >> 12) & 63)) | (1ull << ((h >> 18) & 63)); }
+
+// sets the key's bits; true when all of them were set before (one device-scope atomic on one word: see the file comment)
+__device__ static inline bool kf_test_and_set(unsigned long long *filter, unsigned long long wmask,
+                                              unsigned long long hi, unsigned long long lo)
+{ const unsigned long long h = kf_hash(hi,lo), m = kf_bits(h);
+  const unsigned long long old = __hip_atomic_fetch_or(filter+((h >> 24) & wmask),m,__ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
+  return (old & m) == m;
+}
+
+// One mark pass of a filtered table (REPLAY = false) or a replay of the claims that failed (REPLAY = true: those
+// positions were judged "seen before" already, the filter is not asked again).
+template <bool REPLAY>
+__global__ void __launch_bounds__(KT_BLOCK) kc_mark_kernel(kc_slot *tab, unsigned long long mask,
+                                                           unsigned long long *filter, unsigned long long wmask,
+                                                           const char *seq, const int64_t *seq_off, int nreads,
+                                                           int64_t total, int K, const unsigned int *fail_in,
+                                                           unsigned int *fail_out, kc_ctl *ctl)
+{ const int64_t p0 = ((int64_t)blockIdx.x*blockDim.x+threadIdx.x)*KT_CHUNK;
+  unsigned long long nfail = 0, nocc = 0, nmark = 0;
+  if (p0 < total)
+    (void)kt_walk<true>(seq,seq_off,nreads,total,K,p0,
+      [&](int64_t j, unsigned long long hi, unsigned long long lo)
+      { if (REPLAY)
+          { if (!((fail_in[j >> 5] >> (j & 31)) & 1u)) return; }
+        else
+          { nmark++;
+            if (!kf_test_and_set(filter,wmask,hi,lo)) return;
+          }
+        bool claimed = false;
+        kc_slot *e = kt_find_or_claim(tab,mask,hi,lo,&claimed);
+        nocc += claimed;
+        if (!e)
+          { atomicOr(&fail_out[j >> 5],1u << (j & 31));
+            nfail++;
+          }
+      });
+  kc_wave_add(&ctl->n_fail,nfail);
+  kc_wave_add(&ctl->n_occ,nocc);
+  if (!REPLAY) kc_wave_add(&ctl->n_mark,nmark);
+}
+
+// The count pass of a filtered table: its keys are fixed, so nothing can fail and nothing grows.
+__global__ void __launch_bounds__(KT_BLOCK) kc_count_kernel(kc_slot *tab, unsigned long long mask, const char *seq,
+                                                            const int64_t *seq_off, int nreads, int64_t total, int K,
+                                                            kc_ctl *ctl)
+{ const int64_t p0 = ((int64_t)blockIdx.x*blockDim.x+threadIdx.x)*KT_CHUNK;
+  unsigned long long nadd = 0, nsingle = 0, nskip = 0;
+  if (p0 < total)
+    nskip = kt_walk<true>(seq,seq_off,nreads,total,K,p0,
+      [&](int64_t, unsigned long long hi, unsigned long long lo)
+      { const kc_slot *e = kt_lookup((const kc_slot *)tab,mask,hi,lo);
+        if (!e) { nsingle++; return; }
+        atomicAdd(&const_cast<kc_slot *>(e)->cnt,1ull);
+        nadd++;
+      });
+  kc_wave_add(&ctl->n_add,nadd);
+  kc_wave_add(&ctl->n_single,nsingle);
+  kc_wave_add(&ctl->n_skip,nskip);
+}
+
 // The prof cell of the k-mer position j of read r is prof_off[r] + j - seq_off[r] - (K-1).  Cells follow the k-mer
 // positions in order, so the cells of a block's KC_CELLS positions are one contiguous run [q0, q0+n): staged in LDS,
 // then stored by the whole block, two cells per lane and store.  The two halves are shared by the profile kernel and
@@ -96,6 +178,8 @@ __device__ static inline void kc_store_cells(const uint16_t *cell, uint16_t *dst
     *(unsigned int *)(dst+head+2*i) = (unsigned int)cell[head+2*i] | ((unsigned int)cell[head+2*i+1] << 16);
 }
 
+// ONCE: the table is a filtered one, where a valid k-mer that is absent occurs exactly once (cell 1, no error)
+template <bool ONCE>
 __global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab, unsigned long long mask,
                                                               const char *seq, const int64_t *seq_off,
                                                               const int64_t *prof_off, int nreads, int64_t total, int K,
@@ -119,6 +203,7 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_profile_kernel(const kc_slot *tab
         if (ok)
           { const kc_slot *e = kt_lookup(tab,mask,hi,lo);
             if (e) c = min(e->cnt,(unsigned long long)CP_MAX_KMER_CNT);
+            else if (ONCE) c = 1;
             else err |= KC_ERR_ABSENT;                   // a k-mer that was never added: the caller's error
           }
         const int64_t i = base+j;
@@ -301,19 +386,34 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_hist_kernel(const kc_slot *tab, u
 
 struct cp_kmer_counts : kt_store<kc_slot,kc_ctl>
   { bool unsized;                        // created with initial_slots = 0 and nothing added yet: the first add sizes it
+    unsigned long long *filter;          // a filtered table's bit array (device); null: no filter
+    unsigned long long filter_words;     // a power of two
+    bool added;                          // a filtered table has seen its first add: its keys are fixed, no mark any more
   };
 
-extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_counts **out)
-{ if (!out) return set_err(CP_EINVAL,"cp_kmer_counts_create: null out");
+static int kc_create(const char *who, int K, int64_t initial_slots, int64_t filter_bits, cp_kmer_counts **out)
+{ const std::string w(who);
+  if (!out) return set_err(CP_EINVAL,w+": null out");
   *out = nullptr;
   if (K < 2 || K > 63)
-    return set_err(CP_EINVAL,"cp_kmer_counts_create: K must lie in [2, 63] (a key holds 2K <= 126 bits)");
+    return set_err(CP_EINVAL,w+": K must lie in [2, 63] (a key holds 2K <= 126 bits)");
   if (initial_slots < 0 || initial_slots > ((int64_t)1 << 40))
-    return set_err(CP_EINVAL,"cp_kmer_counts_create: bad initial_slots");
+    return set_err(CP_EINVAL,w+": bad initial_slots");
   cp_kmer_counts *t = new (std::nothrow) cp_kmer_counts();
-  if (!t) return set_err(CP_ENOMEM,"cp_kmer_counts_create: out of memory");
+  if (!t) return set_err(CP_ENOMEM,w+": out of memory");
   t->unsized = initial_slots == 0;
-  const int rc = kt_init(t,"cp_kmer_counts",K,initial_slots);
+  int rc = kt_init(t,"cp_kmer_counts",K,initial_slots);
+  if (rc == CP_OK && filter_bits > 0)
+    { t->filter_words = kt_pow2_at_least((unsigned long long)filter_bits)/64;
+      hipError_t e = hipMalloc(&t->filter,(size_t)t->filter_words*8);
+      if (e == hipSuccess) e = hipMemset(t->filter,0,(size_t)t->filter_words*8);
+      if (e != hipSuccess)
+        { (void)hipGetLastError();
+          char m[160];
+          snprintf(m,sizeof(m),"%s: the filter of %llu bytes: %s",who,t->filter_words*8,hipGetErrorString(e));
+          rc = set_err(CP_ENOMEM,m);
+        }
+    }
   if (rc != CP_OK)
     { cp_kmer_counts_destroy(t);
       return rc;
@@ -322,9 +422,20 @@ extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_count
   return CP_OK;
 }
 
+extern "C" int cp_kmer_counts_create(int K, int64_t initial_slots, cp_kmer_counts **out)
+{ return kc_create("cp_kmer_counts_create",K,initial_slots,0,out); }
+
+extern "C" int cp_kmer_counts_create_filtered(int K, int64_t initial_slots, int64_t filter_bits, cp_kmer_counts **out)
+{ if (out) *out = nullptr;
+  if (filter_bits < 64 || filter_bits > ((int64_t)1 << 40))
+    return set_err(CP_EINVAL,"cp_kmer_counts_create_filtered: filter_bits must lie in [64, 2^40]");
+  return kc_create("cp_kmer_counts_create_filtered",K,initial_slots,filter_bits,out);
+}
+
 extern "C" void cp_kmer_counts_destroy(cp_kmer_counts *t)
 { if (!t) return;
   kt_free(t);
+  if (t->filter) (void)hipFree(t->filter);
   delete t;
 }
 
@@ -335,6 +446,13 @@ extern "C" int cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const in
   if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_add: null device pointer");
   hipStream_t st = (hipStream_t)stream;
   const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
+  if (t->filter)                                           // the count pass: the keys are fixed, nothing to read back
+    { t->stream = st;
+      t->added = true;
+      kc_count_kernel<<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,t->ctl);
+      HIPCHK(hipGetLastError());
+      return CP_OK;
+    }
   return kt_add(t,total_bases,st,&t->unsized,[&](bool replay, const unsigned int *fail_in, unsigned int *fail_out)
     { if (replay)
         kc_add_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,fail_in,
@@ -343,6 +461,32 @@ extern "C" int cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const in
         kc_add_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,fail_in,
                                                      fail_out,t->ctl);
     });
+}
+
+extern "C" int cp_kmer_counts_mark(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                                   int64_t total_bases, void *stream)
+{ if (!t || nreads < 0 || total_bases < 0) return set_err(CP_EINVAL,"cp_kmer_counts_mark: bad argument");
+  if (!t->filter) return set_err(CP_EINVAL,"cp_kmer_counts_mark: the table has no filter");
+  if (t->added)
+    return set_err(CP_EINVAL,"cp_kmer_counts_mark: the table has been added to; every batch is marked before the first add");
+  if (nreads == 0 || total_bases == 0) return CP_OK;
+  if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_mark: null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
+  if (t->unsized)                                          // the first-batch sizing of a filtered table: see the header
+    { t->unsized = false;
+      const int rc = kt_presize(t,kt_pow2_at_least((unsigned long long)total_bases/2),st);
+      if (rc != CP_OK) return rc;
+    }
+  const unsigned long long wmask = t->filter_words-1;
+  return kt_add(t,total_bases,st,(bool *)nullptr,[&](bool replay, const unsigned int *fail_in, unsigned int *fail_out)
+    { if (replay)
+        kc_mark_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,t->filter,wmask,d_seq,d_seq_off,nreads,total_bases,
+                                                     t->K,fail_in,fail_out,t->ctl);
+      else
+        kc_mark_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,t->filter,wmask,d_seq,d_seq_off,nreads,total_bases,
+                                                      t->K,fail_in,fail_out,t->ctl);
+    },false);
 }
 
 extern "C" int cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off,
@@ -355,8 +499,12 @@ extern "C" int cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, con
   hipStream_t st = (hipStream_t)stream;
   t->stream = st;
   const int grid = (int)((total_bases+(int64_t)KC_CELLS-1)/(int64_t)KC_CELLS);
-  kc_profile_kernel<<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,nreads,total_bases,t->K,d_prof,
-                                            t->ctl);
+  if (t->filter)
+    kc_profile_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,nreads,total_bases,t->K,
+                                                    d_prof,t->ctl);
+  else
+    kc_profile_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,d_prof_off,nreads,total_bases,t->K,
+                                                     d_prof,t->ctl);
   HIPCHK(hipGetLastError());
   return CP_OK;
 }
@@ -371,6 +519,8 @@ extern "C" int cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, c
     return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: d_packed and d_pack_off go together");
   if (!d_prof && !d_labels && !d_packed && !d_counts)
     return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: no output wanted");
+  if (t->filter)
+    return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: a filtered table cannot tell a count of 0 from a count of 1");
   if (nreads == 0 || total_bases == 0) return CP_OK;
   if (!d_seq || !d_seq_off) return set_err(CP_EINVAL,"cp_kmer_counts_rel_labels: null device pointer");
   hipStream_t st = (hipStream_t)stream;
@@ -394,16 +544,30 @@ extern "C" int cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, c
   return CP_OK;
 }
 
-extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt)
-{ if (!t || !hist || !ilowcnt || !ihighcnt) return set_err(CP_EINVAL,"cp_kmer_counts_hist: bad argument");
-  hipStream_t st = t->stream;
+// reads the control block back; on a filtered table whose marked and added batches differ CP_EINVAL in the name of `who`
+static int kc_sync_checked(cp_kmer_counts *t, const char *who)
+{ const int rc = kt_sync_ctl(t,t->stream);
+  if (rc != CP_OK) return rc;
+  const unsigned long long marked = t->h_ctl->n_mark, counted = t->h_ctl->n_add+t->h_ctl->n_single;
+  if (t->filter && marked != counted)
+    { char m[200];
+      snprintf(m,sizeof(m),"%s: %llu k-mers were marked and %llu added: the marked and the added batches differ",who,marked,
+               counted);
+      return set_err(CP_EINVAL,m);
+    }
+  return CP_OK;
+}
+
+// the slot sweep of the histogram into h[0..CP_MAX_KMER_CNT]; synchronises
+static int kc_sweep(cp_kmer_counts *t, std::vector<unsigned long long> &h)
+{ hipStream_t st = t->stream;
   const size_t bytes = sizeof(unsigned long long)*(CP_MAX_KMER_CNT+1);
   unsigned long long *d_hist = nullptr;
   if (hipMalloc(&d_hist,bytes) != hipSuccess)
     { (void)hipGetLastError();
       return set_err(CP_ENOMEM,"cp_kmer_counts_hist: cannot allocate the device histogram");
     }
-  std::vector<unsigned long long> h((size_t)CP_MAX_KMER_CNT+1);
+  h.resize((size_t)CP_MAX_KMER_CNT+1);
   hipError_t e = hipMemsetAsync(d_hist,0,bytes,st);
   if (e == hipSuccess)
     { kc_hist_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,d_hist);
@@ -413,6 +577,20 @@ extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *il
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipFree(d_hist);
   if (e != hipSuccess) return set_err(CP_EHIP,std::string("cp_kmer_counts_hist: ")+hipGetErrorString(e));
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt)
+{ if (!t || !hist || !ilowcnt || !ihighcnt) return set_err(CP_EINVAL,"cp_kmer_counts_hist: bad argument");
+  std::vector<unsigned long long> h;
+  int rc;
+  if (t->filter)
+    { rc = kc_sync_checked(t,"cp_kmer_counts_hist");
+      if (rc != CP_OK) return rc;
+    }
+  rc = kc_sweep(t,h);
+  if (rc != CP_OK) return rc;
+  if (t->filter) h[0] += t->h_ctl->n_single;               // the keys kept outside: each occurs once
   for (int c = 0; c < CP_MAX_KMER_CNT; c++) hist[c] = (int64_t)h[(size_t)c];
   *ilowcnt = (int64_t)h[0];
   *ihighcnt = (int64_t)h[(size_t)CP_MAX_KMER_CNT];
@@ -422,18 +600,35 @@ extern "C" int cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *il
 extern "C" int cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out)
 { if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_counts_stats: bad argument");
   hipStream_t st = t->stream;
-  int rc = kt_sync_ctl(t,st);
+  int rc = kc_sync_checked(t,"cp_kmer_counts_stats");
   if (rc != CP_OK) return rc;
   if (t->h_ctl->err)                                       // deferred device errors: reported once, then cleared
     { HIPCHK(hipMemsetAsync(&t->ctl->err,0,sizeof(unsigned int),st));
       HIPCHK(hipStreamSynchronize(st));
       return set_err(CP_EINVAL,"cp_kmer_counts: a profile pass met a k-mer that was never added (its cell is 0)");
     }
-  out->n_kmers = (int64_t)t->h_ctl->n_add;
+  out->n_kmers = (int64_t)(t->h_ctl->n_add+t->h_ctl->n_single);          // n_single is 0 without a filter
   out->n_skipped = (int64_t)t->h_ctl->n_skip;
-  out->n_distinct = (int64_t)t->h_ctl->n_occ;
+  out->n_distinct = (int64_t)(t->h_ctl->n_occ+t->h_ctl->n_single);
   out->slots = (int64_t)t->slots;
-  out->bytes = (int64_t)(t->slots*sizeof(kc_slot)+2*t->fail_words*4);
+  out->bytes = (int64_t)(t->slots*sizeof(kc_slot)+2*t->fail_words*4+t->filter_words*8);
   out->growths = t->growths;
+  return CP_OK;
+}
+
+extern "C" int cp_kmer_counts_filter_stats(cp_kmer_counts *t, cp_kmer_filter_stats *out)
+{ if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_counts_filter_stats: bad argument");
+  int rc = kt_sync_ctl(t,t->stream);
+  if (rc != CP_OK) return rc;
+  std::vector<unsigned long long> h;
+  rc = kc_sweep(t,h);
+  if (rc != CP_OK) return rc;
+  out->filter_bits = (int64_t)(t->filter_words*64);
+  out->filter_bytes = (int64_t)(t->filter_words*8);
+  out->n_marked = (int64_t)t->h_ctl->n_mark;
+  out->n_counted = (int64_t)(t->h_ctl->n_add+t->h_ctl->n_single);
+  out->n_table_keys = (int64_t)t->h_ctl->n_occ;
+  out->n_outside = (int64_t)t->h_ctl->n_single;
+  out->n_false = (int64_t)h[0];
   return CP_OK;
 }

@@ -162,28 +162,40 @@ static int kt_ensure_bitmaps(kt_store<SLOT,CTL> *t, size_t words, hipStream_t st
   return CP_OK;
 }
 
+// An EMPTY table that has fewer than `want` slots (a power of two) is replaced by one of `want`: nothing to rehash, not a
+// growth step.  When the allocation fails the table stays and the usual growth takes over.
+template <class SLOT, class CTL>
+static int kt_presize(kt_store<SLOT,CTL> *t, unsigned long long want, hipStream_t st)
+{ SLOT *nt = nullptr;
+  if (want > t->slots && kt_alloc_table(t->name,&nt,want,st) == CP_OK)
+    { HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipFree(t->tab));
+      t->tab = nt;
+      t->slots = want;
+    }
+  return CP_OK;
+}
+
 // Adds a batch of total_bases base positions on st.  launch(replay, fail_in, fail_out) queues the table's add kernel
 // over the batch: every position (replay false, fail_in null) or only those whose bit is set in fail_in; a failed
 // insert sets its position's bit in fail_out.  *presize (the count table's first-batch sizing; null: never): the first
 // batch into a table of the default size gets room for every k-mer of the batch at half load, so that it does not run
 // through a table it cannot fit into (each failed insert costs KT_PROBE probes and a replay).  The table is empty then,
-// so there is nothing to rehash; when the allocation fails the usual growth takes over.
+// so there is nothing to rehash; when the allocation fails the usual growth takes over.  fail_is_new: a failed insert
+// is, nearly always, a key the table does not hold yet, so the growth makes room for the failures too.  The mark pass of
+// a filtered count table passes false: its failures are second and later occurrences, many per key, and room for each
+// of them would give back the memory that table exists to save; it grows by doubling.
 template <class SLOT, class CTL, class F>
-static int kt_add(kt_store<SLOT,CTL> *t, int64_t total_bases, hipStream_t st, bool *presize, F launch)
+static int kt_add(kt_store<SLOT,CTL> *t, int64_t total_bases, hipStream_t st, bool *presize, F launch,
+                  bool fail_is_new = true)
 { t->stream = st;
   const size_t words = (size_t)((total_bases+31)/32);
   int rc = kt_ensure_bitmaps(t,words,st);
   if (rc != CP_OK) return rc;
   if (presize && *presize)
     { *presize = false;
-      const unsigned long long want = kt_pow2_at_least(2*(unsigned long long)total_bases);
-      SLOT *nt = nullptr;
-      if (want > t->slots && kt_alloc_table(t->name,&nt,want,st) == CP_OK)
-        { HIPCHK(hipStreamSynchronize(st));
-          HIPCHK(hipFree(t->tab));
-          t->tab = nt;
-          t->slots = want;
-        }
+      rc = kt_presize(t,kt_pow2_at_least(2*(unsigned long long)total_bases),st);
+      if (rc != CP_OK) return rc;
     }
   HIPCHK(hipMemsetAsync(t->fail[0],0,words*4,st));
   HIPCHK(hipMemsetAsync(&t->ctl->n_fail,0,sizeof(unsigned long long),st));
@@ -197,7 +209,7 @@ static int kt_add(kt_store<SLOT,CTL> *t, int64_t total_bases, hipStream_t st, bo
       if (nfail == 0 && 2*nocc <= t->slots) return CP_OK;
       if (round >= 16)
         return set_err(CP_ENOMEM,std::string(t->name)+"_add: the table did not settle after 16 growth steps");
-      rc = kt_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+nfail))),st);
+      rc = kt_grow(t,std::max(2*t->slots,kt_pow2_at_least(2*(nocc+(fail_is_new ? nfail : 0)))),st);
       if (rc != CP_OK) return rc;
       if (nfail == 0) continue;
       HIPCHK(hipMemsetAsync(t->fail[1],0,words*4,st));

@@ -371,6 +371,51 @@ int  cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int
 int  cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out);
 
 /* ------------------------------------------------------------------------------------------
+ * Filtered count table: a count table that keeps the k-mers seen ONCE out of its slots.  In a read set most distinct
+ * k-mers are sequencing errors that occur once; a profile only has to say 1 for them and the histogram only needs their
+ * number.  A bit array of filter_bits bits in device memory stands in front of the table, and there are three passes
+ * over the same batches instead of two:
+ *
+ *   mark      every batch: each k-mer occurrence tests and sets its key's bits in the filter (one 64-bit word per key,
+ *             up to four bits in it, one returning atomic OR); only a key whose bits were all set already enters the
+ *             table, without a count.  Of two or more occurrences of a key at most one can find a bit unset, in one
+ *             launch or across batches, so every key that occurs at least twice is in the table afterwards.
+ *   add       the same batches through cp_kmer_counts_add: the keys are fixed now; an occurrence whose key is in the
+ *             table is counted there, any other is tallied (its key occurs exactly once).  Nothing grows and nothing is
+ *             read back.  Other bytes are tallied in n_skipped here, as without a filter.
+ *   profiles  as before, but a valid k-mer that is not in the table gets the cell 1 and is no error.  So profiles on a
+ *             filtered table CANNOT detect a batch that was never added: its k-mers read 1, or the count of the others.
+ *
+ * Profiles, histogram, n_kmers, n_distinct and n_skipped equal those of the unfiltered table bit for bit, for any filter
+ * size, batching and order (hist[0] and ilowcnt include the keys kept outside).  A singleton whose bits were all set by
+ * other keys is a false positive: it holds a slot with the exact count 1.  Which singletons those are, and so the number
+ * of table keys, may depend on the order.  `bytes` of cp_kmer_count_stats includes the filter.
+ *
+ *   filter_bits   rounded up to a power of two; must lie in [64, 2^40], otherwise CP_EINVAL.  A rule of thumb, from a
+ *                 model and not from a measurement: 16 bits (2 bytes) per expected distinct k-mer.
+ *   Sizing        with initial_slots = 0 the first batch marked sizes the still empty table to the power of two at or
+ *                 above total_bases / 2 slots (never below the default 2^20), a quarter of the unfiltered rule: room
+ *                 for one key per four bases at half load, without reserving a slot for every k-mer of the batch.
+ *                 Then the table grows as usual, except for the size of a step: failed claims are replayed after a
+ *                 rehash (the replay does not ask the filter again) and the table grows past half load, but each step
+ *                 only doubles it.  A failed claim of a mark pass is a second or later occurrence, many per key, so
+ *                 their number says nothing about the keys still to come.
+ *   Protocol      CP_EINVAL, the table left as it was: cp_kmer_counts_mark on a table without a filter or after the
+ *                 first cp_kmer_counts_add; cp_kmer_counts_rel_labels on a filtered table (it cannot tell a count of 0
+ *                 from a count of 1); cp_kmer_counts_hist and cp_kmer_counts_stats while n_marked != n_counted (the
+ *                 marked and the added batches differ; the message gives both numbers).
+ */
+typedef struct { int64_t filter_bits, filter_bytes, n_marked, n_counted, n_table_keys, n_outside, n_false; } cp_kmer_filter_stats;
+int  cp_kmer_counts_create_filtered(int K, int64_t initial_slots, int64_t filter_bits, cp_kmer_counts **out);
+/* The mark pass over a batch.  Asynchronous on `stream` except for the read-back and growth of cp_kmer_counts_add. */
+int  cp_kmer_counts_mark(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
+                         int64_t total_bases, void *stream);
+/* Synchronises; legal at any time and on any count table (filter_bits = 0 without a filter).  n_marked / n_counted: valid
+ * k-mer occurrences of the mark / add passes so far; n_table_keys: keys that hold a slot; n_outside: keys kept outside
+ * (known once the batches are added); n_false: table keys with count 1 (a slot sweep). */
+int  cp_kmer_counts_filter_stats(cp_kmer_counts *t, cp_kmer_filter_stats *out);
+
+/* ------------------------------------------------------------------------------------------
  * Relative labels (genome2class): the ground truth of a read set from a count table of ANOTHER sequence set, the
  * assembly.  What `FastK -p:genome` + prof2class give (src/prof2class.c:241-254), in one pass over a batch in the flat
  * layout; the batch need not be (and usually is not) what was added to `t`.

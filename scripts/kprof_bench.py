@@ -1,6 +1,6 @@
 """K-mer count table (kprof, cp_kmer_counts_*) on BASELINE configs[2]: one JSON line.
 
-    python scripts/kprof_bench.py [--genome 200e6] [--cov 40] [--batch-mbases 500] [--counts-only]
+    python scripts/kprof_bench.py [--genome 200e6] [--cov 40] [--batch-mbases 500] [--counts-only] [--filter-log2 N ...]
 
 The 8-Gbase configs[2] set is generated on the device (DeviceSynth, the set of bench.py) in sub-batches of 500 Mbases.
 Reported for the count table: the add rate with growth from the default size and again with the table pre-sized (no
@@ -13,6 +13,13 @@ the classifier) and its consensus pass, each measured twice; the spread between 
 table does a subset of that work per occurrence, so `add_ok` / `profile_ok` say whether its rates are not lower:
 rate >= mean of the two baseline repeats - their spread.  --counts-only skips the baselines (for a run under a profiler,
 or of another build of the library named by CLASSPRO_AMD_LIB).
+
+--filter-log2 N ... adds a leg per N, under the key "filtered": the FILTERED count table (KmerCounts(filter_bits=2^N),
+DESIGN.md 9.10) on the same batches -- mark, count and profile rates, table keys, keys kept outside, false positives,
+final slots and bytes, and the peak device bytes of the build (filter + failure bitmaps + table + the old table during
+the last rehash; computed from the first-batch sizing, the final slots and the growth steps: exact when every step
+doubled the table, "peak_exact", otherwise the bound final + final/2) -- and whether its statistics and low histogram
+bins equal the unfiltered table's.  Without the flag the output is what it was.
 """
 import argparse
 import json
@@ -40,6 +47,7 @@ def parse():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--batch-mbases", type=float, default=500)
     ap.add_argument("--counts-only", action="store_true")
+    ap.add_argument("--filter-log2", type=int, nargs="+", default=[])
     return ap.parse_args()
 
 
@@ -157,6 +165,53 @@ def count_table(ds, batches, initial_slots, clf=None):
     return out
 
 
+def filtered_table(ds, batches, log2_bits, unfiltered):
+    """The filtered count table: mark, count and profile rates over the same batches, and what the filter kept out."""
+    dev = ds.device
+    T = KmerCounts(K, device=str(dev), filter_bits=1 << log2_bits)
+    filter_bytes = T.filter_stats()["filter_bytes"]
+    t_mark = t_add = t_prof = 0.0
+    first_bases = None
+    bases = 0
+    for first, count in batches:
+        b = Batch.from_device(ds.reads(first, count))
+        t_mark += timed(dev, lambda: T.mark(b))
+        bases += b.total_bases
+        if first_bases is None:
+            first_bases = b.total_bases
+        del b
+    for first, count in batches:
+        b = Batch.from_device(ds.reads(first, count))
+        t_add += timed(dev, lambda: T.add(b))
+        del b
+    s, f = T.stats(), T.filter_stats()
+    low, high, il, ih, h = T.hist()
+    for first, count in batches:
+        b = Batch.from_device(ds.reads(first, count))
+        dst = torch.empty_like(b.prof)
+        t_prof += timed(dev, lambda: T.L.cp_kmer_counts_profiles(T.t, b.seq.data_ptr(), b.seq_off.data_ptr(),
+                                                                 b.prof_off.data_ptr(), b.nreads, b.total_bases,
+                                                                 dst.data_ptr(), T._stream()))
+        del b, dst
+    T.stats()
+    T.close()
+    torch.cuda.empty_cache()
+    single = int(h[0])
+    sized = max(1 << 20, 1 << (first_bases // 2 - 1).bit_length())         # the first-batch sizing of a filtered table
+    peak = s["bytes"] + (32 * (s["slots"] // 2) if s["growths"] else 0)    # bytes: table + failure bitmaps + filter
+    return dict(filter_log2=log2_bits, filter_bytes=filter_bytes, mark_gbases_per_s=bases / t_mark / 1e9, mark_s=t_mark,
+                count_gbases_per_s=bases / t_add / 1e9, count_s=t_add, profile_gbases_per_s=bases / t_prof / 1e9,
+                profile_s=t_prof, n_kmers=s["n_kmers"], distinct=s["n_distinct"], skipped=s["n_skipped"],
+                table_keys=f["n_table_keys"], outside=f["n_outside"], false_positives=f["n_false"],
+                false_share_of_singletons=f["n_false"] / max(single, 1), slots=s["slots"], table_bytes=s["bytes"],
+                growths=s["growths"], peak_bytes=peak, peak_exact=s["slots"] == sized << s["growths"],
+                hist_low_bins=[int(x) for x in h[:4]], ilowcnt=il, ihighcnt=ih,
+                same_as_unfiltered=(s["n_kmers"] == unfiltered["n_kmers"] and s["n_distinct"] == unfiltered["distinct"]
+                                    and s["n_skipped"] == unfiltered["skipped"] and il == unfiltered["ilowcnt"]
+                                    and ih == unfiltered["ihighcnt"]
+                                    and [int(x) for x in h[:4]] == unfiltered["hist_low_bins_counted"]))
+
+
 def main():
     a = parse()
     dev = torch.device("cuda:0")
@@ -186,6 +241,8 @@ def main():
                              >= res["baseline_consensus_gbases_per_s"] - res["baseline_consensus_spread"])
         res["profile_ok_vs_forward"] = (cnt["profile_gbases_per_s"] >= res["label_forward"]["consensus_gbases_per_s"][0]
                                         - res["baseline_consensus_spread"])
+    if a.filter_log2:
+        res["filtered"] = [filtered_table(ds, batches, n, cnt) for n in a.filter_log2]
     res["value"], res["unit"] = cnt["add_gbases_per_s"], "Gbases/s"
     clf.close()
     print(json.dumps(res))
