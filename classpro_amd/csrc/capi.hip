@@ -1149,6 +1149,8 @@ extern "C" int cp_debug_live_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_live_prof),8); }
 extern "C" int cp_debug_emit_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_emit_prof),8); }
+extern "C" int cp_debug_unrel_prof(unsigned long long *out4)
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out4,HIP_SYMBOL(g_unrel_prof),4); }
 extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 { HIPCHK(hipDeviceSynchronize());
   CHK(prof_read(out36,HIP_SYMBOL(g_phase_max),12));

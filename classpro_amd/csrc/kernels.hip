@@ -863,6 +863,7 @@ __device__ __forceinline__ cp_intvl cp_soa_get(const cp_soa &S, int64_t at)
 #ifdef CP_PROF_WALK
 __device__ unsigned long long g_phase_max[12], g_phase_sum[12], g_phase_arg[12];
 __device__ unsigned long long g_live_prof[8];
+__device__ unsigned long long g_unrel_prof[4];          // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] in the rest of the rounds, [2] of the kernel; [3] waves
 __device__ unsigned long long g_emit_prof[8];           // wave time inside the emission loop: [0] boundaries, [1] make_interval, [2] find_rel, [3] record stores, [4] compaction
 #ifdef CP_PROF_INNER
 #define EM_LT0() unsigned long long em_t = wall_clock64()
@@ -2694,9 +2695,6 @@ struct unrel_grp_lds
     uint16_t key[G][MAXN+4];             // min(cb,ce) of those, padded with 0xffff to a multiple of four (the sort reads four per load); then: the order
     uint64_t rel[G][2][MAXN/64];         // [0] reliable & H, [1] reliable & D
     uint64_t need[G][MAXN/64];           // second sweep: intervals whose inputs changed since the first sweep evaluated them
-    int16_t  mail_idx[G][8];             // interval, new class and order position of each speculative slot of a round
-    int16_t  mail_pos[G][8];
-    int8_t   mail_s[G][8];
   };
 
 __device__ __forceinline__ int bits_left(const uint64_t *bits, int idx)       // nearest set bit < idx
@@ -2737,6 +2735,9 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   const int g = lane/L, ql = lane%L, gbase = g*L;
   for (int blk = blockIdx.x; blk*G < nreads; blk += gridDim.x)     // groups of a block, as in k_classify_rel_grp
   {
+#ifdef CP_PROF_WALK
+  const unsigned long long ur_t0 = wall_clock64();
+#endif
   const int slot = blk*G+g;
   const int r = (slot < nreads) ? perm[slot] : nreads;
   int N = (r < nreads) ? nintvl[r] : 0;
@@ -2836,9 +2837,12 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   // The reference updates the non-fixed intervals one after the other (class_unrel.c:260-274), and an
   // update costs one Bessel recurrence of latency.  An update reads the neighbouring intervals' classes
   // and the reliable-H / reliable-D sets, which most updates leave untouched, so the K = L/8 groups of 8
-  // lanes of a read take K consecutive updates at once (slots), and one lane then commits them in order:
+  // lanes of a read take K consecutive updates at once (slots), which are then committed in order:
   // a slot is committed only if no earlier slot of the round changed the class of one of its neighbours
-  // or either set; otherwise the round ends there and the next one starts from that update.
+  // or either set; otherwise the round ends there and the next one starts from that update.  Where the
+  // round ends is a closed form of the slots' own (interval, old class, new class), computed by every lane
+  // of the read; the committed slots' lead lanes then write at once (tests/test_unrel_commit_rule.py holds
+  // the closed form against the serial loop it replaced).
   //
   // THE SECOND SWEEP ONLY RE-EVALUATES WHAT CAN HAVE CHANGED (round 5).  update_state(idx) is a function of the constant fields
   // of interval idx, of "asgn == H" / "asgn == D" of its two neighbours (class_unrel.c:126,145) and of the nearest
@@ -2860,6 +2864,10 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   bool done = (N == 0) || (nnf == 0);
 #ifdef CP_PROF_WALK
   int prof_rounds[2] = { 0, 0 };
+  unsigned long long ur_commit = 0, ur_rest = 0, ur_t = wall_clock64();
+#define UR_STAMP(acc) do { const unsigned long long t_ = wall_clock64(); acc += t_-ur_t; ur_t = t_; } while (0)
+#else
+#define UR_STAMP(acc) ((void)0)
 #endif
   while (__ballot(!done) != 0)
       { int mypos = it+sub;                                // order position of this slot's update
@@ -2982,55 +2990,66 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
             if (logpmax < vH) { logpmax = vH; snew = CP_HAPLO; }
             if (logpmax < vD) { logpmax = vD; snew = CP_DIPLO; }
           }
-        if (role == 0)
-          { S.mail_idx[g][sub] = (int16_t)idx;
-            S.mail_pos[g][sub] = (int16_t)mypos;
-            S.mail_s[g][sub] = (int8_t)(act ? snew : -1);
-          }
         wave_sync();                                           // every slot has read the old state
-        int newit = cover;
-        if (ql == 0 && !done)                                  // commit the round's slots in order
-          { bool sets_changed = false;
-            int changed[K], nch = 0;
-            for (int j = 0; j < K; j++)
-              { const int sj = S.mail_s[g][j], ij = S.mail_idx[g][j];
-                if (sj < 0) break;                             // no update in this slot
-                bool clash = sets_changed;
-                for (int m = 0; m < nch; m++)
-                  clash = clash || changed[m] == ij-1 || changed[m] == ij+1;
-                if (clash) { newit = S.mail_pos[g][j]; break; }        // computed from a state an earlier slot changed
-                const int old = S.asgn[g][ij];
-                S.need[g][ij >> 6] &= ~(1ull << (ij & 63));    // evaluated on the state as it is now
-                if (old != sj)
-                  { const bool ohd = old == CP_HAPLO || old == CP_DIPLO, nhd = sj == CP_HAPLO || sj == CP_DIPLO;
-                    if (ohd || nhd)                            // the neighbours' "asgn == s" tests
-                      { if (ij > 0)   S.need[g][(ij-1) >> 6] |= 1ull << ((ij-1) & 63);
-                        if (ij+1 < N) S.need[g][(ij+1) >> 6] |= 1ull << ((ij+1) & 63);
-                      }
-                    if (S.isrel[g][ij] && (ohd || nhd))
-                      { const uint64_t bit = 1ull << (ij & 63);
-                        for (int q = 0; q < 2; q++)            // ij leaves / joins the reliable-H (q = 0) or the reliable-D set
-                          { const int sq = q ? CP_DIPLO : CP_HAPLO;
-                            if (old != sq && sj != sq) continue;
-                            int lo = bits_left(S.rel[g][q],ij), hi = bits_right(S.rel[g][q],ij,nwords);   // (ij's own bit plays no part)
-                            if (lo < 0) lo = 0;
-                            if (hi < 0) hi = N-1;
-                            for (int w = lo >> 6; w <= (hi >> 6); w++)
-                              { const uint64_t ml = (w == (lo >> 6)) ? (~0ull << (lo & 63)) : ~0ull;
-                                const uint64_t mh = (w == (hi >> 6)) ? (~0ull >> (63-(hi & 63))) : ~0ull;
-                                S.need[g][w] |= ml & mh;
-                              }
-                            if (old == sq) S.rel[g][q][ij >> 6] &= ~bit; else S.rel[g][q][ij >> 6] |= bit;
-                            sets_changed = true;
-                          }
-                      }
-                    S.asgn[g][ij] = (int8_t)sj;
-                    if (ohd || nhd) changed[nch++] = ij;       // (a change among E, R and "no class yet" is no input of anybody's update)
-                    if (pass == 1 && (ohd || nhd)) { newit = S.mail_pos[g][j]+1; break; }   // positions behind it were skipped on bits this change may have set
+        UR_STAMP(ur_rest);
+        // Commit the round's slots in order (every lane of a read computes where the round stops; the slots' lead lanes
+        // write).  Serially: slot j is committed unless an earlier slot of the round changed the H-or-D-ness of one of
+        // its index neighbours or either reliable set; the round ends at the first slot without an update (the rest of
+        // [it,cover) is settled), at the first such clash (that update is next), or, in the second sweep, behind the
+        // first committed change to or from H / D.  The slots hold distinct intervals, so a slot's old class is what
+        // it reads now, and every slot before the first stop is committed: "an earlier committed slot" is "an earlier slot".
+        const bool lead = role == 0, upd = act && snew >= 0;
+        int old = 0;
+        bool hd = false, setc = false;
+        if (lead && upd)
+          { old = S.asgn[g][idx];
+            const bool ohd = old == CP_HAPLO || old == CP_DIPLO, nhd = snew == CP_HAPLO || snew == CP_DIPLO;
+            hd = old != snew && (ohd || nhd);                  // (a change among E, R and "no class yet" is no input of anybody's update)
+            setc = hd && S.isrel[g][idx];                      // idx leaves / joins the reliable-H or the reliable-D set
+          }
+        const uint64_t m_hd = __ballot(hd), m_setc = __ballot(setc);
+        const int osl = gbase+8*(role & (K-1));                // lane `role` of a slot looks at slot `role`
+        const int oidx = __shfl(idx,osl);
+        const bool cl = role < sub && (((m_setc >> osl) & 1) || (((m_hd >> osl) & 1) && (oidx == idx-1 || oidx == idx+1)));
+        constexpr uint64_t LEADS = 0x0101010101010101ull & ((L == 64) ? ~0ull : ((1ull << L)-1));
+        const uint64_t clm = (__ballot(cl) >> gbase) & glm;
+        const uint64_t cb = ((clm | ((clm & 0x7f7f7f7f7f7f7f7full)+0x7f7f7f7f7f7f7f7full)) >> 7) & LEADS;   // bit 8j: slot j clashes
+        const uint64_t ub = (__ballot(lead && upd) >> gbase) & glm;                                         // bit 8j: slot j has an update
+        const uint64_t stop = (~ub & LEADS) | cb;
+        const int js = stop ? __ffsll((long long)stop)-1 : L;  // (in lanes: 8 x the slot)
+        const uint64_t hb = ((m_hd >> gbase) & glm) & (js < 64 ? (1ull << js)-1 : ~0ull);
+        const bool hstop = pass == 1 && hb != 0;               // positions behind it were skipped on bits this change may have set
+        const int jh = hstop ? __ffsll((long long)hb)-1 : 0;
+        const bool cstop = !hstop && js < L && ((ub >> js) & 1);       // computed from a state an earlier slot changed
+        const int spos = __shfl(mypos,gbase+(hstop ? jh : cstop ? js : 0));
+        const int newit = hstop ? spos+1 : cstop ? spos : cover;
+        const bool cm = lead && upd && ql < (hstop ? jh+1 : js);
+        unsigned long long *const need = reinterpret_cast<unsigned long long *>(S.need[g]);
+        // Every clear before any set: the clears are ONE LDS instruction of the wave, the sets later ones, and a wave's LDS
+        // instructions are issued and carried out in program order -- that order is what this relies on, no barrier.
+        if (cm) atomicAnd(&need[idx >> 6],~(1ull << (idx & 63)));      // evaluated on the state as it is now
+        if (cm && hd)                                          // the neighbours' "asgn == s" tests (a neighbour may be an earlier slot of the round)
+          { if (idx > 0)   atomicOr(&need[(idx-1) >> 6],1ull << ((idx-1) & 63));
+            if (idx+1 < N) atomicOr(&need[(idx+1) >> 6],1ull << ((idx+1) & 63));
+          }
+        if (cm && old != snew) S.asgn[g][idx] = (int8_t)snew;
+        if (cm && setc)                                        // (the last committed slot of its read: every later one clashes)
+          { const uint64_t bit = 1ull << (idx & 63);
+            for (int q = 0; q < 2; q++)                        // idx leaves / joins the reliable-H (q = 0) or the reliable-D set
+              { const int sq = q ? CP_DIPLO : CP_HAPLO;
+                if (old != sq && snew != sq) continue;
+                int lo = bits_left(S.rel[g][q],idx), hi = bits_right(S.rel[g][q],idx,nwords);   // (idx's own bit plays no part)
+                if (lo < 0) lo = 0;
+                if (hi < 0) hi = N-1;
+                for (int w = lo >> 6; w <= (hi >> 6); w++)
+                  { const uint64_t ml = (w == (lo >> 6)) ? (~0ull << (lo & 63)) : ~0ull;
+                    const uint64_t mh = (w == (hi >> 6)) ? (~0ull >> (63-(hi & 63))) : ~0ull;
+                    atomicOr(&need[w],ml & mh);
                   }
+                if (old == sq) S.rel[g][q][idx >> 6] &= ~bit; else S.rel[g][q][idx >> 6] |= bit;
               }
           }
-        newit = __shfl(newit,gbase);
+        UR_STAMP(ur_commit);
 #ifdef CP_PROF_WALK
         if (!done) prof_rounds[pass]++;
 #endif
@@ -3044,7 +3063,12 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   if (ql == 0 && N > 0 && MINN == 0)                       // rounds of the first / second sweep, non-fixed intervals, reads (main class)
     { atomicAdd(&g_phase_sum[9],(unsigned long long)prof_rounds[0]); atomicAdd(&g_phase_max[9],(unsigned long long)prof_rounds[1]);
       atomicAdd(&g_phase_sum[10],(unsigned long long)nnf); atomicAdd(&g_phase_sum[11],1ull); }
+  if (lane == 0 && MINN == 0)
+    { UR_STAMP(ur_rest);
+      atomicAdd(&g_unrel_prof[0],ur_commit); atomicAdd(&g_unrel_prof[1],ur_rest);
+      atomicAdd(&g_unrel_prof[2],wall_clock64()-ur_t0); atomicAdd(&g_unrel_prof[3],1ull); }
 #endif
+#undef UR_STAMP
   if (pcls_all)                                            // whole-path calls: 4 bytes per interval for k_paint_labels instead of a
     for (int k = ql; k < N; k += L)                        // one-byte store into every 48-byte record (CP_PCLS)
       pcls_all[io+k] = CP_PCLS((int)S.e[g][k],S.asgn[g][k]);
@@ -3058,13 +3082,31 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
 // ---------------------------------------------------------------------------------------------
 //  k_paint_labels: ClassPro.c:116-119 ('N' x (K-1)) and :265-271 (interval class per k-mer).
 //  One wave per read.  The read's label string is cut into 16-byte pieces of the output (aligned to the buffer), a lane
-//  each, 1 KB per step: the interval ends (in label coordinates, the 'N' prefix as interval 0) sit in LDS, a lane finds
-//  the interval of its piece's first label by binary search, splats that class over the piece and patches what follows
-//  an interval end inside it (one piece in ten holds one).  The form before -- interval by interval, every interval
-//  painted by the whole wave -- issued 57 instructions per interval, 0.4 G of the pipeline's 4.5 G per sub-batch
-//  (profiles/r03_sq_insts.txt), mostly scalar address arithmetic; this one about a quarter of that.
+//  each, 1 KB per step: the interval ends (in label coordinates, the 'N' prefix as interval 0) sit in LDS.  The interval
+//  of a piece's first label is the number of ends at or before that label, and consecutive pieces are monotone in it:
+//  every end adds one to a counter of the first piece that starts at or behind it (LDS atomics, once per read and tile of
+//  PAINT_TILE pieces), and a step's 64 counters, summed by a wave scan on top of the steps before, are the 64 indices.  A
+//  lane splats its interval's class over the piece and patches what follows an interval end inside it (one piece in
+//  ten holds one).  The patch is still the loop over the ends inside the piece, a wave-wide branch taken when any lane has
+//  one (with five ends per 1-KB step that is nearly every step), only its body is selects now; a select-only patch for the
+//  first end with the loop kept for pieces of two or more ends is not done.  The form before searched the ends for every piece (seven dependent LDS reads per lane and step):
+//  0.53 G vector + 0.23 G scalar instructions per 4-Gbase launch, this one 0.32 G + 0.09 G
+//  (profiles/unrel_commit_paint_ab.txt).  The first form of all -- interval by interval, every interval painted by the
+//  whole wave -- issued 57 instructions per interval, mostly scalar address arithmetic (profiles/r03_sq_insts.txt).
 // ---------------------------------------------------------------------------------------------
 #define PAINT_MAX 512
+#define PAINT_TILE 2048
+// inclusive prefix sum over the wave as DPP adds: inside the rows of 16 lanes, then lane 15 of rows 0 / 2 into rows 1 / 3,
+// then lane 31 into rows 2 and 3 (a lane without a source adds 0)
+__device__ __forceinline__ int wave_scan_add(int v)
+{ v += __builtin_amdgcn_update_dpp(0,v,0x111,0xf,0xf,false);
+  v += __builtin_amdgcn_update_dpp(0,v,0x112,0xf,0xf,false);
+  v += __builtin_amdgcn_update_dpp(0,v,0x114,0xf,0xf,false);
+  v += __builtin_amdgcn_update_dpp(0,v,0x118,0xf,0xf,false);
+  v += __builtin_amdgcn_update_dpp(0,v,0x142,0xa,0xf,false);
+  v += __builtin_amdgcn_update_dpp(0,v,0x143,0xc,0xf,false);
+  return v;
+}
 __device__ __forceinline__ unsigned cp_label_char(int a)
 { return (a == CP_ERROR) ? 'E' : (a == CP_REPEAT) ? 'R' : (a == CP_HAPLO) ? 'H' : (a == CP_DIPLO) ? 'D' : '?'; }
 
@@ -3083,7 +3125,8 @@ k_paint_labels(const cp_dev_params *__restrict__ P, const int64_t *__restrict__ 
   const int N = nintvl[r];
   __shared__ int s_end[PAINT_MAX];                       // end of interval k (k = 0: the 'N' prefix), label coordinates
   __shared__ uint8_t s_chr[PAINT_MAX];
-  if (N+1 <= PAINT_MAX)
+  __shared__ __attribute__((aligned(16))) uint32_t s_cnt[PAINT_TILE/2];   // 16-bit counters, one per piece of the tile: the interval ends that
+  if (N+1 <= PAINT_MAX)                                  // lie behind the piece before and not behind this one (at most PAINT_MAX)
     { if (lane == 0) { s_end[0] = K-1 < rlen ? K-1 : rlen; s_chr[0] = 'N'; }
       if (pcls)
         for (int k = lane; k < N; k += WAVE)
@@ -3103,32 +3146,51 @@ k_paint_labels(const cp_dev_params *__restrict__ P, const int64_t *__restrict__ 
       if (lane < h) lab[lane] = (char)s_chr[find(lane)];
       const int npiece = (rlen-h) >> 4;
       uint4 *dst = reinterpret_cast<uint4 *>(lab+h);
-      for (int pc = lane; pc < npiece; pc += WAVE)
-        { const int q0 = h+16*pc;
-          int k = find(q0);
-          unsigned c = s_chr[k]*0x01010101u;
-          uint32_t w[4] = { c, c, c, c };
-          int e = s_end[k];
-          while (e < q0+16 && k+1 < M)                   // an interval ends inside the piece: the rest of it is the next one's
-            { k++;
-              const unsigned c2 = s_chr[k]*0x01010101u;
-              const int o = e-q0;                        // first byte of the piece that belongs to interval k
-#pragma unroll
-              for (int d = 0; d < 4; d++)
-                { const int lo = o-4*d;                  // first byte of dword d to replace
-                  if (lo <= 0) w[d] = c2;
-                  else if (lo < 4) { const uint32_t m = 0xffffffffu << (8*lo); w[d] = (w[d] & ~m) | (c2 & m); }
-                }
-              e = s_end[k];
+      int carry = 0;                                     // interval ends at or before the first label of the step's first piece
+      for (int p0 = 0; p0 < npiece; p0 += PAINT_TILE)    // PAINT_TILE pieces at a time: as many as there are counters
+        { const int np = npiece-p0 < PAINT_TILE ? npiece-p0 : PAINT_TILE;
+          for (int j = lane; 4*j < ((np+WAVE-1) & ~(WAVE-1)); j += WAVE)   // (whole steps: the last one reads a counter on every lane)
+            reinterpret_cast<uint2 *>(s_cnt)[j] = make_uint2(0u,0u);
+          wave_sync();
+          for (int k = lane; k < M; k += WAVE)           // an end counts for the first piece that starts at or behind it
+            { const int e = s_end[k];
+              const int p = (e <= h ? 0 : (e-h+15) >> 4)-p0;
+              if (p >= 0 && p < np) atomicAdd(&s_cnt[p >> 1],1u << (16*(p & 1)));
             }
+          wave_sync();
+          for (int base = 0; base < np; base += WAVE)
+            { const int pc = p0+base+lane;
+              const int inc = wave_scan_add((int)reinterpret_cast<const uint16_t *>(s_cnt)[base+lane]);
+              int k = carry+inc;                         // ends at or before this piece's first label = its interval
+              carry += wave_of_last(inc);
+              if (pc >= npiece) continue;
+              k = k < M-1 ? k : M-1;
+              const int q0 = h+16*pc;
+              unsigned c = s_chr[k]*0x01010101u;
+              uint32_t w[4] = { c, c, c, c };
+              int e = s_end[k];
+              while (e < q0+16 && k+1 < M)               // an interval ends inside the piece: the rest of it is the next one's
+                { k++;
+                  const unsigned c2 = s_chr[k]*0x01010101u;
+                  const int o = e-q0;                    // first byte of the piece that belongs to interval k
+#pragma unroll
+                  for (int d = 0; d < 4; d++)
+                    { const int lo = o-4*d;              // first byte of dword d to replace
+                      const uint32_t m = lo <= 0 ? 0xffffffffu : lo < 4 ? 0xffffffffu << (8*lo) : 0u;
+                      w[d] = (w[d] & ~m) | (c2 & m);
+                    }
+                  e = s_end[k];
+                }
 #ifdef PAINT_NT                                          // (A/B knob: non-temporal label stores, measured and dropped -- this kernel 1.18 -> 1.51 ms
                                                          //  per 4 Gbases in the pipeline, the step 0.4-0.9 % slower: profiles/r05_paint_nt_fw5_ab.txt)
-          { const cp_u4v v = { w[0], w[1], w[2], w[3] };
-            __builtin_nontemporal_store(v,reinterpret_cast<cp_u4v *>(dst+pc));
-          }
+              { const cp_u4v v = { w[0], w[1], w[2], w[3] };
+                __builtin_nontemporal_store(v,reinterpret_cast<cp_u4v *>(dst+pc));
+              }
 #else
-          dst[pc] = make_uint4(w[0],w[1],w[2],w[3]);
+              dst[pc] = make_uint4(w[0],w[1],w[2],w[3]);
 #endif
+            }
+          wave_sync();                                   // the counters are zeroed again for the next tile
         }
       const int t0 = h+16*npiece;                        // the bytes behind the last aligned piece
       if (t0+lane < rlen) lab[t0+lane] = (char)s_chr[find(t0+lane)];

@@ -27,7 +27,9 @@ clf = Classifier(40, 20000, hc, dc)
 ph = (C.c_ulonglong * 36)()
 lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
+ur = (C.c_ulonglong * 4)()
 clf.classify(b)
+lib().cp_debug_unrel_prof(ur)
 lib().cp_debug_phase_prof(ph)
 lib().cp_debug_live_prof(lv)
 lib().cp_debug_emit_prof(em)
@@ -35,6 +37,7 @@ clf.classify(b)
 lib().cp_debug_phase_prof(ph)
 lib().cp_debug_live_prof(lv)
 lib().cp_debug_emit_prof(em)
+lib().cp_debug_unrel_prof(ur)
 pn = {0: "k_wall_tasks: candidate list", 7: "k_wall_tasks: prelude + filters", 6: "k_wall_tasks: live tasks",
       1: "k_find_wall: replay", 2: "unwall/sort/olist", 3: "multi-error search", 4: "merge + sorts",
       8: "components + boundaries", 5: "records + find_rel"}
@@ -47,6 +50,8 @@ print("E-interval lists of at most 64 (the wave-parallel forms): before the un-w
       % (em[0], em[1] / b.nreads, em[2], em[3] / b.nreads, em[4], em[5] / b.nreads))
 print("classify_unrel (main class): %.1f non-fixed intervals per read, %.1f speculation rounds in the first sweep (four slots per round), %.1f in the second"
       % (ph[12 + 10] / max(1, ph[12 + 11]), ph[12 + 9] / max(1, ph[12 + 11]), ph[9] / max(1, ph[12 + 11])))
+print("classify_unrel (main class): %d waves, %.1f ticks per wave: committing the slots %.1f (%.1f %% of the wave time), the rest of the rounds %.1f, before and behind the rounds %.1f"
+      % (ur[3], ur[2] / max(1, ur[3]), ur[0] / max(1, ur[3]), 100.0 * ur[0] / max(1, ur[2]), ur[1] / max(1, ur[3]), (ur[2] - ur[0] - ur[1]) / max(1, ur[3])))
 print("classify_rel: %d of %d (read, direction) passes are repeated with adjusted coverages (class_rel.c:629-650); %d of %d waves run the DP a second time"
       % (em[6] & 0xffffffff, em[6] >> 32, em[7] & 0xffffffff, em[7] >> 32))
 print("reads %d: memo on chip %d, flags on chip to the end %d, sent their flags to the arrays after the replay (more off-list SELF walls than slots) %d, flags on chip after the walk %d" %
