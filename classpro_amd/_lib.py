@@ -22,6 +22,8 @@ SYMBOLS = [
     "cp_kmer_counts_create", "cp_kmer_counts_destroy", "cp_kmer_counts_add", "cp_kmer_counts_profiles",
     "cp_kmer_counts_hist", "cp_kmer_counts_stats", "cp_kmer_counts_rel_labels",
     "cp_kmer_counts_create_filtered", "cp_kmer_counts_mark", "cp_kmer_counts_filter_stats",
+    "cp_kmer_counts_sort", "cp_kmer_sorted_destroy", "cp_kmer_sorted_size", "cp_kmer_sorted_bytes",
+    "cp_kmer_sorted_arrays", "cp_kmer_sorted_ktab", "cp_ktab_ibyte", "cp_ktab_tile",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -141,6 +143,17 @@ def lib():
     L.cp_kmer_counts_create_filtered.argtypes = [i32, i64, i64, C.POINTER(vp)]
     L.cp_kmer_counts_mark.argtypes = [vp, vp, vp, i32, i64, vp]
     L.cp_kmer_counts_filter_stats.argtypes = [vp, C.POINTER(KmerFilterStats)]
+    L.cp_kmer_counts_sort.argtypes = [vp, i64, vp, C.POINTER(vp)]
+    L.cp_kmer_sorted_destroy.argtypes = [vp]
+    L.cp_kmer_sorted_destroy.restype = None
+    L.cp_kmer_sorted_size.argtypes = [vp]
+    L.cp_kmer_sorted_size.restype = i64
+    L.cp_kmer_sorted_bytes.argtypes = [vp]
+    L.cp_kmer_sorted_bytes.restype = i64
+    L.cp_kmer_sorted_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.cp_kmer_sorted_ktab.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.cp_ktab_ibyte.argtypes = [i32]
+    L.cp_ktab_tile.argtypes = []
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -572,6 +572,81 @@ class KmerCounts:
         check(self.L.cp_kmer_counts_stats(self.t, C.byref(s)))
         return {f: getattr(s, f) for f, _ in s._fields_}
 
+    def sorted(self, min_count=1):
+        """A `SortedKmers` snapshot of the table: every key with count >= min_count (in [1, 32767]; at least 2 on a
+        filtered table), ascending by key.  The table is only read and the snapshot does not follow later adds."""
+        s = C.c_void_p()
+        check(self.L.cp_kmer_counts_sort(self.t, int(min_count), self._stream(), C.byref(s)))
+        return SortedKmers(self, s)
+
+
+class SortedKmers:
+    """A sorted snapshot of a `KmerCounts` table (cp_kmer_sorted_*; semantics in include/classpro_amd.h, "Sorted
+    k-mers").  len() is the number of entries; `.hi`, `.lo` (key = hi << 63 | lo) and `.counts` (exact) are int64 device
+    tensors that VIEW the snapshot's memory; `.nbytes` is the device memory held.  A tensor taken from them keeps the
+    snapshot alive, so the memory is freed when the object and all such tensors are gone -- or at once by `close()`,
+    after which any tensor still held points at freed memory: clone what has to outlive an explicit `close()`."""
+
+    def __init__(self, table, handle):
+        self.L, self.device, self.K = table.L, table.device, table.K
+        self.s = handle
+        self.n = check(self.L.cp_kmer_sorted_size(self.s))
+        self.nbytes = check(self.L.cp_kmer_sorted_bytes(self.s))
+        p = [C.c_void_p() for _ in range(3)]
+        check(self.L.cp_kmer_sorted_arrays(self.s, *[C.byref(x) for x in p]))
+        self._ptr = [x.value for x in p]
+
+    hi = property(lambda self: self._view(0))
+    lo = property(lambda self: self._view(1))
+    counts = property(lambda self: self._view(2))
+
+    def _view(self, which):
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if self.n == 0:
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        ptr = self._ptr[which]
+        iface = {"shape": (self.n,), "typestr": "<i8", "data": (ptr, False), "version": 2, "strides": None}
+        # torch keeps `holder` for the life of the tensor and of every view of it; the holder keeps this object, so a
+        # tensor that outlives the last name of the SortedKmers (`T.sorted().hi`) still points at live memory.  The
+        # object itself holds no tensor (a new one per access), so there is no cycle through torch to keep it alive.
+        holder = type("_KsView", (), {"__cuda_array_interface__": iface, "owner": self})()
+        return torch.as_tensor(holder, device=self.device)
+
+    def __len__(self):
+        return self.n
+
+    def ktab(self, first=0, n=None):
+        """(records, index): the FASTK .ktab records of the entries [first, first+n) (n = None: to the end) as a uint8
+        device tensor, and the prefix index of the WHOLE snapshot as an int64 device tensor of 1 << 8*ibyte."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        n = self.n - first if n is None else n
+        ibyte = self.L.cp_ktab_ibyte(self.K)
+        pbyte = ((self.K + 3) >> 2) - ibyte + 2
+        rec = torch.empty(max(n, 0) * pbyte, dtype=torch.uint8, device=self.device)
+        idx = torch.empty((1 << (8 * ibyte)) if ibyte else 0, dtype=torch.int64, device=self.device)
+        check(self.L.cp_kmer_sorted_ktab(self.s, int(first), int(n), rec.data_ptr() if rec.numel() else None,
+                                         idx.data_ptr() if idx.numel() else None,
+                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return rec, idx
+
+    def close(self):
+        if getattr(self, "s", None):
+            self.L.cp_kmer_sorted_destroy(self.s)
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ktab_tile():
+    """cp_ktab_tile: the entries one block sorts on chip (a build constant; tests place sizes around it)."""
+    return lib().cp_ktab_tile()
+
 
 def _stream_of(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

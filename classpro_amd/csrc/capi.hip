@@ -1165,5 +1165,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // k-mer count table, count profiles and histogram (kprof): kmer_counts.hip
 #include "kmer_counts.hip"
 
+// sorted snapshot of a count table and its FASTK .ktab payload (kprof -t): kmer_sort.hip
+#include "kmer_sort.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

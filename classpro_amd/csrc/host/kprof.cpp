@@ -1,7 +1,7 @@
 // kprof.cpp -- k-mer count profiles and histogram from reads alone: what `FastK -k<K> -t1 -p` leaves for ClassPro,
 // counted on the GPU.
 //
-//   kprof [-v] [-k<int(40)>] [-T<int(4)>] [-f<int>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]
+//   kprof [-v] [-k<int(40)>] [-T<int(4)>] [-f<int>] [-t<int>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]
 //
 // Writes <root>.hist, <root>.prof, .<root>.pidx.1..n and .<root>.prof.1..n (layout: classpro_amd/fastk.py), <root> being
 // the source's path without its extension, or -N.  The source is found as ClassPro finds it: the first of .db .dam
@@ -15,6 +15,14 @@
 // ("Filtered count table" in include/classpro_amd.h): the k-mers seen once then take no slot, at the price of a third
 // pass over the reads -- mark, count, profile.  The files written are byte for byte those written without -f; absent or
 // 0 means no filter and the two passes above.
+// -t<m> also writes the k-mer table of `FastK -t<m>`, <root>.ktab and .<root>.ktab.1..n: the distinct canonical k-mers
+// that occur at least m times (m in [1, 32767]; with -f at least 2, the k-mers seen once hold no slot), in ascending
+// order, with a prefix index -- what libfastk.c's Open_Kmer_Stream, Load_Kmer_Table and Find_Kmer read (layout:
+// classpro_amd/fastk.py).  Between the count and the profile pass the table is sorted on the device
+// (cp_kmer_counts_sort, "Sorted k-mers" in include/classpro_amd.h) and its records, encoded there, come down in ranges
+// of TAB_RANGE entries through one buffer; the host only writes them.  Part p of nparts = max(1, min(T, entries)) holds
+// the entries [entries*p/nparts, entries*(p+1)/nparts).  The snapshot is destroyed before the profile pass starts.
+// Without -t every file is what it was.  K < 5 has no .ktab (the reader decodes one to three prefix bytes).
 // A k-mer with a byte other than upper-case A C G T is not counted and gets count 0; how many there were is always said
 // on stderr.  FastK's own treatment of such bases is not reproduced.
 #include <cerrno>
@@ -27,6 +35,7 @@ static const char *USAGE = "[-v] [-k<int(40)>] [-T<int(4)>] [-N<out_root>] <sour
 
 static const long long MAX_FILTER_MIB = 1ll << 17;           // 2^40 bits, the library's limit
 static const int64_t BATCH_BASES = (int64_t)64 << 20;        // bases per device batch
+static const int64_t TAB_RANGE = (int64_t)4 << 20;           // -t: table entries per transfer (records of at most 15 bytes: 60 MiB)
 
 struct Batch
   { std::vector<char> seq;
@@ -40,6 +49,7 @@ int main(int argc, char **argv)
   bool verbose = false;
   int K = 40, nthreads = 4;
   int64_t filter_mib = 0;
+  int tab_min = 0;                                                  // -t: 0 = no k-mer table
   std::string out_root;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; i++)
@@ -55,6 +65,17 @@ int main(int argc, char **argv)
           case 'k': K = arg_int(a,"K-mer length",true); break;
           case 'T': nthreads = arg_int(a,"Number of threads",true); break;
           case 'N': out_root = a+2; break;
+          case 't':
+            { char *end;
+              errno = 0;
+              const long long v = strtoll(a+2,&end,10);
+              if (*end != '\0' || a[2] == '\0')
+                die("%s: -t '%s' argument is not an integer\n",PROG,a+2);
+              if (errno != 0 || v < 1 || v > CP_MAX_KMER_CNT)
+                die("%s: Table cutoff must lie in [1, %d] (%s)\n",PROG,CP_MAX_KMER_CNT,a+2);
+              tab_min = (int)v;
+              break;
+            }
           case 'f':
             { char *end;
               errno = 0;
@@ -74,6 +95,10 @@ int main(int argc, char **argv)
     die("Usage: %s %s\n",PROG,USAGE);
   if (K < 2 || K > 63)
     die("%s: K-mer length must lie in [2, 63] (%d)\n",PROG,K);
+  if (tab_min == 1 && filter_mib)
+    die("%s: -t1 needs the k-mers seen once, which -f keeps out of the table: give -t2 or more, or drop -f\n",PROG);
+  if (tab_min && cp_ktab_ibyte(K) == 0)
+    die("%s: -t needs a K-mer length of at least 5 (%d): a k-mer table has one to three prefix bytes\n",PROG,K);
 
   Source S;
   std::string path, root;
@@ -86,6 +111,10 @@ int main(int argc, char **argv)
   if (!fh) die("%s: Cannot open %s for 'w'\n",PROG,hist_path.c_str());
   FILE *fs = fopen(stub_path.c_str(),"wb");
   if (!fs) die("%s: Cannot open %s for 'w'\n",PROG,stub_path.c_str());
+  const std::string tab_path = odir+"/"+oname+".ktab";
+  FILE *ft = nullptr;
+  if (tab_min && !(ft = fopen(tab_path.c_str(),"wb")))
+    die("%s: Cannot open %s for 'w'\n",PROG,tab_path.c_str());
   S.open();
   if (verbose)
     fprintf(stderr,"Input = %s, K = %d, outputs = %s.hist, %s.prof, %s/.%s.{pidx,prof}.*\n",S.path.c_str(),K,
@@ -163,6 +192,52 @@ int main(int argc, char **argv)
     if (fclose(fh) != 0 || !ok) die("%s: Cannot write %s\n",PROG,hist_path.c_str());
   }
 
+  // ---- -t: the sorted table, between the passes ----
+  std::string tabled;                                               // what -t adds to the -v line
+  if (tab_min)
+    { cp_kmer_sorted *sorted = nullptr;
+      rc = cp_kmer_counts_sort(T,tab_min,nullptr,&sorted);
+      if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_sort");
+      const int64_t entries = cp_kmer_sorted_size(sorted);
+      const int ibyte = cp_ktab_ibyte(K), pbyte = ((K+3) >> 2)-ibyte+2;
+      const int tparts = (int)std::max<int64_t>(1,std::min<int64_t>(nthreads,entries));
+      { std::vector<int64_t> index((size_t)1 << (8*ibyte));
+        DevBuf<int64_t> d_index;
+        d_index.need(index.size());
+        rc = cp_kmer_sorted_ktab(sorted,0,0,nullptr,d_index.p,nullptr);
+        if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_ktab");
+        HCHK(hipMemcpy(index.data(),d_index.p,index.size()*8,hipMemcpyDeviceToHost));
+        HCHK(hipFree(d_index.p));
+        const bool ok = fwrite(&K,4,1,ft) == 1 && fwrite(&tparts,4,1,ft) == 1 && fwrite(&tab_min,4,1,ft) == 1
+                        && fwrite(&ibyte,4,1,ft) == 1 && fwrite(index.data(),8,index.size(),ft) == index.size();
+        if (fclose(ft) != 0 || !ok) die("%s: Cannot write %s\n",PROG,tab_path.c_str());
+      }
+      DevBuf<uint8_t> d_rec;
+      std::vector<uint8_t> h_rec;
+      for (int p = 0; p < tparts; p++)
+        { const int64_t e0 = entries*p/tparts, e1 = entries*(p+1)/tparts, nels = e1-e0;
+          const std::string part = odir+"/."+oname+".ktab."+std::to_string(p+1);
+          FILE *fp = fopen(part.c_str(),"wb");
+          if (!fp) die("%s: Cannot open %s for 'w'\n",PROG,part.c_str());
+          bool ok = fwrite(&K,4,1,fp) == 1 && fwrite(&nels,8,1,fp) == 1;
+          for (int64_t e = e0; e < e1 && ok; e += TAB_RANGE)
+            { const int64_t m = std::min(TAB_RANGE,e1-e);
+              d_rec.need((size_t)(m*pbyte));
+              h_rec.resize((size_t)(m*pbyte));
+              rc = cp_kmer_sorted_ktab(sorted,e,m,d_rec.p,nullptr,nullptr);
+              if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_ktab");
+              HCHK(hipMemcpy(h_rec.data(),d_rec.p,h_rec.size(),hipMemcpyDeviceToHost));
+              ok = fwrite(h_rec.data(),1,h_rec.size(),fp) == h_rec.size();
+            }
+          if (fclose(fp) != 0 || !ok) die("%s: Cannot write %s\n",PROG,part.c_str());
+        }
+      if (d_rec.p) HCHK(hipFree(d_rec.p));
+      cp_kmer_sorted_destroy(sorted);
+      char m[160];
+      snprintf(m,sizeof(m),", %lld table entries, minval %d, ibyte %d, %d table parts",(long long)entries,tab_min,ibyte,tparts);
+      tabled = m;
+    }
+
   // ---- pass 2: profiles ----
   const int nparts = (int)std::min<int64_t>(nthreads,nreads);
   ProfWriter W;
@@ -226,8 +301,8 @@ int main(int argc, char **argv)
     }
   if (verbose)
     fprintf(stderr,"%lld reads, %lld bases, %lld k-mers counted, %lld distinct, %lld skipped, %lld slots, %lld growth steps, "
-                   "%d profile parts%s\n",(long long)nreads,(long long)nbases,(long long)st.n_kmers,(long long)st.n_distinct,
-            (long long)st.n_skipped,(long long)st.slots,(long long)st.growths,nparts,filtered.c_str());
+                   "%d profile parts%s%s\n",(long long)nreads,(long long)nbases,(long long)st.n_kmers,(long long)st.n_distinct,
+            (long long)st.n_skipped,(long long)st.slots,(long long)st.growths,nparts,filtered.c_str(),tabled.c_str());
   if (st.n_skipped)
     fprintf(stderr,"%s: %lld k-mer positions skipped (a byte other than upper-case A C G T): their count is 0\n",PROG,
             (long long)st.n_skipped);

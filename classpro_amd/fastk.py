@@ -8,6 +8,10 @@ Format as read by the reference (all little-endian):
   .prof.N  per read: first count 1 byte (<128) or 2 bytes (0x80|hi, lo); then
            00rrrrrr run of r equal counts, 01sxxxxx 6-bit signed delta, 1sxxxxxx yyyyyyyy 15-bit delta
                                                                                              (libfastk.c:1467-1534)
+  .ktab    int kmer, int nparts, int minval, int ibyte, int64 index[1 << 8*ibyte]: index[p] = entries whose first
+           ibyte key bytes, read big-endian, are <= p                          (libfastk.c:816-841, 994)
+  .ktab.N  int kmer, int64 nels, nels records of (kmer+3)/4 - ibyte key bytes and a uint16 count
+                                                                                             (libfastk.c:854-855, 1037-1047)
 The production host path (C++ CLI, classpro_amd/csrc/host) has its own readers; this module is tooling.
 """
 import gzip
@@ -134,6 +138,75 @@ def read_fastk_codes(dirpath, root):
             codes.append(blob[o:int(e)])
             o = int(e)
     return K, codes
+
+
+def ktab_ibyte(K):
+    """Prefix bytes of a .ktab for this K (cp_ktab_ibyte): 3, 2, 1, or 0 for "no .ktab for this K"."""
+    return 3 if K >= 13 else 2 if K >= 9 else 1 if K >= 5 else 0
+
+
+def write_fastk_ktab(dirpath, root, K, min_count, keys, counts, nparts=1):
+    """Writes `<root>.ktab` and `.<root>.ktab.1..nparts`.  keys: Python ints, the 2K-bit k-mers (first base most
+    significant, A C G T = 0 1 2 3), distinct and ascending; counts: their counts, clamped to 32767 in the records.
+    Part p holds the entries [n*p/nparts, n*(p+1)/nparts)."""
+    ibyte = ktab_ibyte(K)
+    if ibyte == 0:
+        raise ValueError("there is no .ktab for K < 5")
+    keys = [int(k) for k in keys]
+    if any(a >= b for a, b in zip(keys, keys[1:])):
+        raise ValueError("keys must be distinct and ascending")
+    if len(counts) != len(keys) or nparts < 1:
+        raise ValueError("bad counts or nparts")
+    kbyte = (K + 3) >> 2
+    hbyte = kbyte - ibyte
+    n = len(keys)
+    index = np.zeros(1 << (8 * ibyte), np.int64)
+    recs = []
+    for k, c in zip(keys, counts):
+        b = (k << (8 * kbyte - 2 * K)).to_bytes(kbyte, "big")
+        index[int.from_bytes(b[:ibyte], "big")] += 1
+        recs.append(b[ibyte:] + struct.pack("<H", min(int(c), 32767)))
+    os.makedirs(dirpath, exist_ok=True)
+    with open(os.path.join(dirpath, root + ".ktab"), "wb") as f:
+        f.write(struct.pack("<iiii", K, nparts, min_count, ibyte))
+        f.write(np.cumsum(index).astype("<i8").tobytes())
+    for p in range(nparts):
+        lo, hi = n * p // nparts, n * (p + 1) // nparts
+        with open(os.path.join(dirpath, ".%s.ktab.%d" % (root, p + 1)), "wb") as f:
+            f.write(struct.pack("<iq", K, hi - lo))
+            f.write(b"".join(recs[lo:hi]))
+
+
+def read_fastk_ktab(dirpath, root):
+    """Returns (K, min_count, ibyte, keys, counts): keys as Python ints in file order (see write_fastk_ktab), counts a
+    uint16 array.  The prefix of an entry comes from the index, as in libfastk.c."""
+    with open(os.path.join(dirpath, root + ".ktab"), "rb") as f:
+        K, nparts, min_count, ibyte = struct.unpack("<iiii", f.read(16))
+        index = np.frombuffer(f.read(8 << (8 * ibyte)), dtype="<i8")
+    kbyte = (K + 3) >> 2
+    hbyte = kbyte - ibyte
+    pbyte = hbyte + 2
+    blob = b""
+    for p in range(nparts):
+        with open(os.path.join(dirpath, ".%s.ktab.%d" % (root, p + 1)), "rb") as f:
+            pk, n = struct.unpack("<iq", f.read(12))
+            if pk != K:
+                raise ValueError("part %d has another K than the stub" % (p + 1))
+            part = f.read()
+            if len(part) != n * pbyte:
+                raise ValueError("part %d does not hold %d records" % (p + 1, n))
+            blob += part
+    n = len(blob) // pbyte
+    if len(index) and int(index[-1]) != n:
+        raise ValueError("the index ends at %d, the parts hold %d entries" % (int(index[-1]), n))
+    prefix = np.searchsorted(index, np.arange(n), side="right")
+    keys, counts = [], np.zeros(n, np.uint16)
+    for i in range(n):
+        r = blob[i * pbyte:(i + 1) * pbyte]
+        b = int(prefix[i]).to_bytes(ibyte, "big") + r[:hbyte]
+        keys.append(int.from_bytes(b, "big") >> (8 * kbyte - 2 * K))
+        counts[i] = r[hbyte] | (r[hbyte + 1] << 8)
+    return K, min_count, ibyte, keys, counts
 
 
 def write_fasta(path, names, seqs, gz=None, comments=None):

@@ -438,6 +438,48 @@ int  cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, const int64
                                uint8_t *d_packed, const int64_t *d_pack_off, int64_t *d_counts, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sorted k-mers (kprof -t): a snapshot of a count table in key order, and the payload of the FASTK k-mer table
+ * (`<root>.ktab`, `.<root>.ktab.N`) that libfastk.c's Open_Kmer_Stream / Load_Kmer_Table / Find_Kmer read, encoded on
+ * the device.
+ *
+ *   Snapshot   every key of the table with count >= min_count, ascending by the 2K-bit key read as the integer
+ *              hi << 63 | lo: the first base is the most significant, A < C < G < T, FastK's order.  Keys are distinct,
+ *              so the result does not depend on the slot order or on scheduling.  d_cnt holds the exact 64-bit count.
+ *              The table is only read (cp_kmer_counts_hist and cp_kmer_counts_stats give the same before and after); a
+ *              snapshot does not follow later adds, a second sort after more adds does.  An empty result is no error:
+ *              the size is 0 and the array pointers are null.
+ *   min_count  must lie in [1, 32767], otherwise CP_EINVAL.  On a filtered table min_count = 1 is CP_EINVAL (the keys
+ *              seen once hold no slot), and so is a table whose marked and added batches differ (the check of
+ *              cp_kmer_counts_stats, made first); with min_count >= 2 the result is that of the unfiltered table.
+ *   Record     kbyte = (K+3)>>2 bytes hold the key left-aligned: the first base in bits 7..6 of byte 0, unused low
+ *              bits of the last byte 0.  The first ibyte = cp_ktab_ibyte(K) bytes are the prefix: 3 for K >= 13, 2 for
+ *              K in 9..12, 1 for K in 5..8; 0 for K < 5, for which there is no .ktab (cp_kmer_sorted_ktab is
+ *              CP_EINVAL).  A record is the other hbyte = kbyte - ibyte bytes, then min(count, CP_MAX_KMER_CNT) as a
+ *              little-endian uint16: pbyte = hbyte + 2 bytes.
+ *   ktab       d_records receives the records of the entries [first, first+n), n * pbyte bytes (any alignment; a range
+ *              outside the snapshot is CP_EINVAL, n = 0 is legal).  d_index, when not NULL, receives 1 << (8*ibyte)
+ *              int64: index[p] = the number of entries of the WHOLE snapshot whose prefix is <= p.  Asynchronous on
+ *              `stream`.
+ *   Memory     24 bytes per entry and 8 bytes per prefix ((1 << 8*ibyte) + 1 of them; 4^K + 1 for K < 5) on top of
+ *              the table: cp_kmer_sorted_bytes.  An allocation that fails is CP_ENOMEM with the byte count in the
+ *              message; the table is untouched.  cp_kmer_counts_sort synchronises `stream`.
+ *   Tile       cp_ktab_tile: the number of entries one block sorts on chip.  A prefix with more entries than that is
+ *              sorted by a path of its own; the constant is exported so that tests can place sizes around it.
+ */
+typedef struct cp_kmer_sorted cp_kmer_sorted;
+int     cp_kmer_counts_sort(cp_kmer_counts *t, int64_t min_count, void *stream, cp_kmer_sorted **out);
+void    cp_kmer_sorted_destroy(cp_kmer_sorted *s);
+int64_t cp_kmer_sorted_size(const cp_kmer_sorted *s);
+int64_t cp_kmer_sorted_bytes(const cp_kmer_sorted *s);
+/* Device pointers to size() words each, valid until destroy. */
+int     cp_kmer_sorted_arrays(const cp_kmer_sorted *s, const uint64_t **d_hi, const uint64_t **d_lo,
+                              const uint64_t **d_cnt);
+int     cp_kmer_sorted_ktab(cp_kmer_sorted *s, int64_t first, int64_t n, uint8_t *d_records, int64_t *d_index,
+                            void *stream);
+int     cp_ktab_ibyte(int K);
+int     cp_ktab_tile(void);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
