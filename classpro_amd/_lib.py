@@ -24,6 +24,7 @@ SYMBOLS = [
     "cp_kmer_counts_create_filtered", "cp_kmer_counts_mark", "cp_kmer_counts_filter_stats",
     "cp_kmer_counts_sort", "cp_kmer_sorted_destroy", "cp_kmer_sorted_size", "cp_kmer_sorted_bytes",
     "cp_kmer_sorted_arrays", "cp_kmer_sorted_ktab", "cp_ktab_ibyte", "cp_ktab_tile",
+    "cp_kmer_table_sort", "cp_kmer_table_class_hist",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -154,6 +155,8 @@ def lib():
     L.cp_kmer_sorted_ktab.argtypes = [vp, i64, i64, vp, vp, vp]
     L.cp_ktab_ibyte.argtypes = [i32]
     L.cp_ktab_tile.argtypes = []
+    L.cp_kmer_table_sort.argtypes = [vp, i32, i64, i32, vp, C.POINTER(vp)]
+    L.cp_kmer_table_class_hist.argtypes = [vp, vp, vp, vp]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

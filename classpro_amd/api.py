@@ -425,6 +425,26 @@ class KmerTable:
         assert m == n
         return hi[:n], lo[:n], cnt[:n]
 
+    def sorted(self, label=None, min_total=1, min_pct=0):
+        """A `SortedKmers` snapshot of the table (cp_kmer_table_sort; "Sorted k-mers of a label table" in
+        include/classpro_amd.h): the keys whose consensus label is `label` (one of "E" "H" "D" "R"; None: every key),
+        whose four counts sum to at least min_total (in [1, 32767]) and whose largest count c has 100 * c >= min_pct *
+        total (min_pct in [0, 100]), ascending by key; `.counts` holds the totals.  The table is only read and the
+        snapshot does not follow later adds."""
+        if label is not None and not (isinstance(label, str) and len(label) == 1 and label in self.LABELS):
+            raise ValueError('label must be None or one of "E" "H" "D" "R"')
+        s = C.c_void_p()
+        check(self.L.cp_kmer_table_sort(self.t, -1 if label is None else self.LABELS.index(label), int(min_total),
+                                        int(min_pct), self._stream(), C.byref(s)))
+        return SortedKmers(self, s)
+
+    def class_hist(self):
+        """cp_kmer_table_class_hist: (hist int64 [4, 32767], ilowcnt int64 [4], ihighcnt int64 [4]) as numpy, the FASTK
+        histogram of the keys of each consensus class in the order E, H, D, R, a key's total standing for its count."""
+        h, il, ih = np.zeros((4, 32767), np.int64), np.zeros(4, np.int64), np.zeros(4, np.int64)
+        check(self.L.cp_kmer_table_class_hist(self.t, h.ctypes.data, il.ctypes.data, ih.ctypes.data))
+        return h, il, ih
+
 
 class KmerCounts:
     """K-mer count table on the device (cp_kmer_counts_*; semantics in include/classpro_amd.h): counts every canonical
@@ -581,8 +601,8 @@ class KmerCounts:
 
 
 class SortedKmers:
-    """A sorted snapshot of a `KmerCounts` table (cp_kmer_sorted_*; semantics in include/classpro_amd.h, "Sorted
-    k-mers").  len() is the number of entries; `.hi`, `.lo` (key = hi << 63 | lo) and `.counts` (exact) are int64 device
+    """A sorted snapshot of a `KmerCounts` or a `KmerTable` (cp_kmer_sorted_*; semantics in include/classpro_amd.h,
+    "Sorted k-mers").  len() is the number of entries; `.hi`, `.lo` (key = hi << 63 | lo) and `.counts` (exact) are int64 device
     tensors that VIEW the snapshot's memory; `.nbytes` is the device memory held.  A tensor taken from them keeps the
     snapshot alive, so the memory is freed when the object and all such tensors are gone -- or at once by `close()`,
     after which any tensor still held points at freed memory: clone what has to outlive an explicit `close()`."""

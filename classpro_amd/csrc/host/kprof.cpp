@@ -20,8 +20,9 @@
 // order, with a prefix index -- what libfastk.c's Open_Kmer_Stream, Load_Kmer_Table and Find_Kmer read (layout:
 // classpro_amd/fastk.py).  Between the count and the profile pass the table is sorted on the device
 // (cp_kmer_counts_sort, "Sorted k-mers" in include/classpro_amd.h) and its records, encoded there, come down in ranges
-// of TAB_RANGE entries through one buffer; the host only writes them.  Part p of nparts = max(1, min(T, entries)) holds
-// the entries [entries*p/nparts, entries*(p+1)/nparts).  The snapshot is destroyed before the profile pass starts.
+// of TAB_RANGE entries through one buffer; the host only writes them (ktab_writer.h).  Part p of nparts =
+// max(1, min(T, entries)) holds the entries [entries*p/nparts, entries*(p+1)/nparts).  The snapshot is destroyed before
+// the profile pass starts.
 // Without -t every file is what it was.  K < 5 has no .ktab (the reader decodes one to three prefix bytes).
 // A k-mer with a byte other than upper-case A C G T is not counted and gets count 0; how many there were is always said
 // on stderr.  FastK's own treatment of such bases is not reproduced.
@@ -29,13 +30,13 @@
 #include "gpu_tool.h"
 #include "read_source.h"
 #include "prof_writer.h"
+#include "ktab_writer.h"
 #include "thread_pool.h"
 
 static const char *USAGE = "[-v] [-k<int(40)>] [-T<int(4)>] [-N<out_root>] <source>[.db|.dam|.f[ast][aq][.gz]]";
 
 static const long long MAX_FILTER_MIB = 1ll << 17;           // 2^40 bits, the library's limit
 static const int64_t BATCH_BASES = (int64_t)64 << 20;        // bases per device batch
-static const int64_t TAB_RANGE = (int64_t)4 << 20;           // -t: table entries per transfer (records of at most 15 bytes: 60 MiB)
 
 struct Batch
   { std::vector<char> seq;
@@ -198,40 +199,11 @@ int main(int argc, char **argv)
     { cp_kmer_sorted *sorted = nullptr;
       rc = cp_kmer_counts_sort(T,tab_min,nullptr,&sorted);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_sort");
-      const int64_t entries = cp_kmer_sorted_size(sorted);
-      const int ibyte = cp_ktab_ibyte(K), pbyte = ((K+3) >> 2)-ibyte+2;
-      const int tparts = (int)std::max<int64_t>(1,std::min<int64_t>(nthreads,entries));
-      { std::vector<int64_t> index((size_t)1 << (8*ibyte));
-        DevBuf<int64_t> d_index;
-        d_index.need(index.size());
-        rc = cp_kmer_sorted_ktab(sorted,0,0,nullptr,d_index.p,nullptr);
-        if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_ktab");
-        HCHK(hipMemcpy(index.data(),d_index.p,index.size()*8,hipMemcpyDeviceToHost));
-        HCHK(hipFree(d_index.p));
-        const bool ok = fwrite(&K,4,1,ft) == 1 && fwrite(&tparts,4,1,ft) == 1 && fwrite(&tab_min,4,1,ft) == 1
-                        && fwrite(&ibyte,4,1,ft) == 1 && fwrite(index.data(),8,index.size(),ft) == index.size();
-        if (fclose(ft) != 0 || !ok) die("%s: Cannot write %s\n",PROG,tab_path.c_str());
-      }
-      DevBuf<uint8_t> d_rec;
-      std::vector<uint8_t> h_rec;
-      for (int p = 0; p < tparts; p++)
-        { const int64_t e0 = entries*p/tparts, e1 = entries*(p+1)/tparts, nels = e1-e0;
-          const std::string part = odir+"/."+oname+".ktab."+std::to_string(p+1);
-          FILE *fp = fopen(part.c_str(),"wb");
-          if (!fp) die("%s: Cannot open %s for 'w'\n",PROG,part.c_str());
-          bool ok = fwrite(&K,4,1,fp) == 1 && fwrite(&nels,8,1,fp) == 1;
-          for (int64_t e = e0; e < e1 && ok; e += TAB_RANGE)
-            { const int64_t m = std::min(TAB_RANGE,e1-e);
-              d_rec.need((size_t)(m*pbyte));
-              h_rec.resize((size_t)(m*pbyte));
-              rc = cp_kmer_sorted_ktab(sorted,e,m,d_rec.p,nullptr,nullptr);
-              if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_ktab");
-              HCHK(hipMemcpy(h_rec.data(),d_rec.p,h_rec.size(),hipMemcpyDeviceToHost));
-              ok = fwrite(h_rec.data(),1,h_rec.size(),fp) == h_rec.size();
-            }
-          if (fclose(fp) != 0 || !ok) die("%s: Cannot write %s\n",PROG,part.c_str());
-        }
-      if (d_rec.p) HCHK(hipFree(d_rec.p));
+      KtabWriter TW;
+      TW.write(sorted,K,tab_min,nthreads,ft,tab_path,odir,oname);
+      TW.release();
+      const int64_t entries = TW.entries;
+      const int ibyte = TW.ibyte, tparts = TW.nparts;
       cp_kmer_sorted_destroy(sorted);
       char m[160];
       snprintf(m,sizeof(m),", %lld table entries, minval %d, ibyte %d, %d table parts",(long long)entries,tab_min,ibyte,tparts);

@@ -2,6 +2,9 @@
 // and its FASTK .ktab payload (prefix index and fixed-width records) encoded on the device.  Semantics:
 // include/classpro_amd.h, "Sorted k-mers"; design: DESIGN.md 9.11.  Included by capi.hip after kmer_counts.hip (the table,
 // set_err, HIPCHK and the library's error contract are in scope).  The table is only read.
+// The same snapshot of a LABEL table (class2ktab), one consensus class per call, and that table's per-class histogram:
+// "Sorted k-mers of a label table" in the header, DESIGN.md 9.12.  The two sweeps over the slots are templates over the
+// slot type and a selector (slot -> keep?, 64-bit payload); everything behind the scatter sees keys and payloads only.
 //
 // The file format names the partition: a bucket is the top pbits = 8*ibyte bits of the key (2K bits where K < 5 and
 // there is no .ktab), and the prefix sum over the bucket sizes is the .ktab index.
@@ -35,30 +38,83 @@ struct cp_kmer_sorted
 __device__ static inline unsigned long long ks_bucket(unsigned long long hi, unsigned long long lo, int shift)
 { return (unsigned long long)(((((kt_u128)hi) << 63) | (kt_u128)lo) >> shift); }
 
-__global__ void __launch_bounds__(KT_BLOCK) ks_count_kernel(const kc_slot *tab, unsigned long long nslots,
-                                                            unsigned long long min_count, int shift, int64_t *start)
+// A selector says which slots a snapshot keeps and what it carries for them: keep(slot, &payload).
+struct ks_sel_count                        // the count table: the keys seen at least min_count times, with their count
+  { unsigned long long min_count;
+    __device__ bool keep(const kc_slot &e, unsigned long long *pay) const
+    { *pay = e.cnt;
+      return e.cnt >= min_count;
+    }
+  };
+
+struct ks_sel_class                        // the label table: the rule of "Sorted k-mers of a label table", with the total
+  { int label;                             // -1: every class
+    unsigned long long min_total, min_pct;
+    __device__ bool keep(const kt_slot &e, unsigned long long *pay) const
+    { unsigned long long tot = 0, mx = 0;
+      for (int l = 0; l < 4; l++)
+        { tot += e.cnt[l];
+          mx = max(mx,(unsigned long long)e.cnt[l]);
+        }
+      *pay = tot;                          // tot < 2^34, so 100*mx and min_pct*tot stay far below 2^64
+      return (label < 0 || kt_consensus(e.cnt) == label) && tot >= min_total && 100*mx >= min_pct*tot;
+    }
+  };
+
+template <class Slot, class Sel>
+__global__ void __launch_bounds__(KT_BLOCK) ks_count_kernel(const Slot *tab, unsigned long long nslots, Sel sel, int shift,
+                                                            int64_t *start)
 { for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < nslots;
        s += (unsigned long long)gridDim.x*blockDim.x)
-    { const kc_slot e = tab[s];
-      if (e.lo == KT_EMPTY || e.cnt < min_count) continue;
+    { const Slot e = tab[s];
+      unsigned long long pay;
+      if (e.lo == KT_EMPTY || !sel.keep(e,&pay)) continue;
       atomicAdd((unsigned long long *)&start[ks_bucket(e.hi,e.lo,shift)],1ull);
     }
 }
 
-__global__ void __launch_bounds__(KT_BLOCK) ks_scatter_kernel(const kc_slot *tab, unsigned long long nslots,
-                                                              unsigned long long min_count, int shift, int64_t *start,
-                                                              unsigned long long *hi, unsigned long long *lo,
-                                                              unsigned long long *cnt, int64_t n)
+template <class Slot, class Sel>
+__global__ void __launch_bounds__(KT_BLOCK) ks_scatter_kernel(const Slot *tab, unsigned long long nslots, Sel sel, int shift,
+                                                              int64_t *start, unsigned long long *hi,
+                                                              unsigned long long *lo, unsigned long long *cnt, int64_t n)
 { for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < nslots;
        s += (unsigned long long)gridDim.x*blockDim.x)
-    { const kc_slot e = tab[s];
-      if (e.lo == KT_EMPTY || e.cnt < min_count) continue;
+    { const Slot e = tab[s];
+      unsigned long long pay;
+      if (e.lo == KT_EMPTY || !sel.keep(e,&pay)) continue;
       const int64_t i = (int64_t)atomicAdd((unsigned long long *)&start[ks_bucket(e.hi,e.lo,shift)],~0ull)-1;
       if ((unsigned long long)i >= (unsigned long long)n) continue;        // cannot happen while the table is only read
       hi[i] = e.hi;
       lo[i] = e.lo;
-      cnt[i] = e.cnt;
+      cnt[i] = pay;
     }
+}
+
+// The per-class histogram of a label table: hist[l*(CP_MAX_KMER_CNT+1) + ...] is the layout of kc_hist_kernel for the
+// keys of consensus class l, the total of a key's four counts standing for the count.  4 x KC_LOW_BINS bins in LDS.
+__global__ void __launch_bounds__(KT_BLOCK) ks_class_hist_kernel(const kt_slot *tab, unsigned long long n,
+                                                                 unsigned long long *hist)
+{ __shared__ unsigned int low[4*KC_LOW_BINS];
+  for (int i = threadIdx.x; i < 4*KC_LOW_BINS; i += KT_BLOCK) low[i] = 0;
+  __syncthreads();
+  for (unsigned long long s = (unsigned long long)blockIdx.x*blockDim.x+threadIdx.x; s < n;
+       s += (unsigned long long)gridDim.x*blockDim.x)
+    { const kt_slot e = tab[s];
+      if (e.lo == KT_EMPTY) continue;
+      const unsigned long long tot = (unsigned long long)e.cnt[0]+e.cnt[1]+e.cnt[2]+e.cnt[3];
+      if (tot == 0) continue;
+      const int l = kt_consensus(e.cnt);
+      unsigned long long *h = hist+(size_t)l*(CP_MAX_KMER_CNT+1);
+      if (tot <= KC_LOW_BINS) atomicAdd(&low[l*KC_LOW_BINS+(int)tot-1],1u);
+      else if (tot < CP_MAX_KMER_CNT) atomicAdd(&h[tot-1],1ull);
+      else
+        { atomicAdd(&h[CP_MAX_KMER_CNT-1],1ull);
+          atomicAdd(&h[CP_MAX_KMER_CNT],tot);
+        }
+    }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 4*KC_LOW_BINS; i += KT_BLOCK)
+    if (low[i]) atomicAdd(&hist[(size_t)(i/KC_LOW_BINS)*(CP_MAX_KMER_CNT+1)+(i%KC_LOW_BINS)],(unsigned long long)low[i]);
 }
 
 // the block's inclusive scan of one value per lane (KS_BLOCK lanes); `part` is KS_BLOCK words of LDS
@@ -275,22 +331,21 @@ extern "C" void cp_kmer_sorted_destroy(cp_kmer_sorted *s)
   delete s;
 }
 
-static int ks_alloc(void **p, size_t bytes, const char *what)
+static int ks_alloc(const char *who, void **p, size_t bytes, const char *what)
 { const hipError_t e = hipMalloc(p,bytes);
   if (e == hipSuccess) return CP_OK;
   (void)hipGetLastError();
   *p = nullptr;
   char m[200];
-  snprintf(m,sizeof(m),"cp_kmer_counts_sort: hipMalloc(%s, %llu bytes): %s",what,(unsigned long long)bytes,
-           hipGetErrorString(e));
+  snprintf(m,sizeof(m),"%s: hipMalloc(%s, %llu bytes): %s",who,what,(unsigned long long)bytes,hipGetErrorString(e));
   return set_err(CP_ENOMEM,m);
 }
 
 // the sort of the buckets of more than KS_TILE entries (see the file comment); scratch is freed by the caller
-static int ks_sort_oversize(cp_kmer_sorted *s, hipStream_t st, void **scratch)
+static int ks_sort_oversize(const char *who, cp_kmer_sorted *s, hipStream_t st, void **scratch)
 { unsigned long long *hi = s->key, *lo = s->key+s->n, *cnt = s->key+2*s->n;
   const int64_t cap = s->n/(KS_TILE+1)+1;                  // no more buckets than that can be oversize
-  int rc = ks_alloc(scratch,16+(size_t)cap*sizeof(ks_run),"the oversize list");
+  int rc = ks_alloc(who,scratch,16+(size_t)cap*sizeof(ks_run),"the oversize list");
   if (rc != CP_OK) return rc;
   unsigned long long *ctl = (unsigned long long *)*scratch, h_ctl[2];
   ks_run *list = (ks_run *)(ctl+2);
@@ -301,7 +356,7 @@ static int ks_sort_oversize(cp_kmer_sorted *s, hipStream_t st, void **scratch)
   HIPCHK(hipStreamSynchronize(st));
   const int64_t nover = (int64_t)h_ctl[0], longest = (int64_t)h_ctl[1];
   if (nover == 0) return CP_OK;
-  if (nover > cap) return set_err(CP_EHIP,"cp_kmer_counts_sort: the oversize list overflowed");
+  if (nover > cap) return set_err(CP_EHIP,std::string(who)+": the oversize list overflowed");
   int64_t np = 2;
   while (np < longest) np <<= 1;
   const unsigned gx = (unsigned)std::min<int64_t>((np/2+KS_BLOCK-1)/KS_BLOCK,4096);
@@ -319,15 +374,17 @@ static int ks_sort_oversize(cp_kmer_sorted *s, hipStream_t st, void **scratch)
   return CP_OK;
 }
 
-static int ks_build(cp_kmer_counts *t, cp_kmer_sorted *s, unsigned long long min_count, hipStream_t st, void **scratch)
+// the snapshot of the slots that `sel` keeps, for either table; `who` names the entry point in the messages
+template <class Tab, class Sel>
+static int ks_build(const char *who, Tab *t, cp_kmer_sorted *s, Sel sel, hipStream_t st, void **scratch)
 { const int shift = 2*s->K-s->pbits;
-  int rc = ks_alloc((void **)&s->start,(size_t)(s->nb+1)*8,"the bucket counters");
+  int rc = ks_alloc(who,(void **)&s->start,(size_t)(s->nb+1)*8,"the bucket counters");
   if (rc != CP_OK) return rc;
   HIPCHK(hipMemsetAsync(s->start,0,(size_t)(s->nb+1)*8,st));
-  ks_count_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,min_count,shift,s->start);
+  ks_count_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,sel,shift,s->start);
   HIPCHK(hipGetLastError());
   const int nchunk = (int)((s->nb+KS_CHUNK-1)/KS_CHUNK);   // at most 2^24 / KS_CHUNK = KS_CHUNK
-  rc = ks_alloc(scratch,(size_t)nchunk*8,"the scan's sums");
+  rc = ks_alloc(who,scratch,(size_t)nchunk*8,"the scan's sums");
   if (rc != CP_OK) return rc;
   unsigned long long *sum = (unsigned long long *)*scratch;
   ks_chunk_sum_kernel<<<nchunk,KS_BLOCK,0,st>>>(s->start,s->nb,sum);
@@ -340,18 +397,39 @@ static int ks_build(cp_kmer_counts *t, cp_kmer_sorted *s, unsigned long long min
   (void)hipFree(*scratch);
   *scratch = nullptr;
   if (s->n == 0) return CP_OK;                             // the starts are all 0 already
-  rc = ks_alloc((void **)&s->key,(size_t)s->n*24,"the sorted entries");
+  rc = ks_alloc(who,(void **)&s->key,(size_t)s->n*24,"the sorted entries");
   if (rc != CP_OK) return rc;
   unsigned long long *hi = s->key, *lo = s->key+s->n, *cnt = s->key+2*s->n;
-  ks_scatter_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,min_count,shift,s->start,hi,lo,cnt,s->n);
+  ks_scatter_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,sel,shift,s->start,hi,lo,cnt,s->n);
   HIPCHK(hipGetLastError());
   const int64_t ntile = (s->n+KS_TILE-1)/KS_TILE;
-  if (ntile > 0x7fffffff) return set_err(CP_EINVAL,"cp_kmer_counts_sort: more than 2^31 tiles");
+  if (ntile > 0x7fffffff) return set_err(CP_EINVAL,std::string(who)+": more than 2^31 tiles");
   ks_tile_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(hi,lo,cnt,s->start,s->nb,s->n);
   HIPCHK(hipGetLastError());
-  rc = ks_sort_oversize(s,st,scratch);
+  rc = ks_sort_oversize(who,s,st,scratch);
   if (rc != CP_OK) return rc;
   HIPCHK(hipStreamSynchronize(st));
+  return CP_OK;
+}
+
+// what both sorts do once their arguments are checked and the table's stream is in order
+template <class Tab, class Sel>
+static int ks_snapshot(const char *who, Tab *t, Sel sel, hipStream_t st, cp_kmer_sorted **out)
+{ cp_kmer_sorted *s = new (std::nothrow) cp_kmer_sorted();
+  if (!s) return set_err(CP_ENOMEM,std::string(who)+": out of memory");
+  s->K = t->K;
+  s->ibyte = cp_ktab_ibyte(t->K);
+  s->pbits = s->ibyte ? 8*s->ibyte : 2*t->K;
+  s->nb = (int64_t)1 << s->pbits;
+  void *scratch = nullptr;
+  const int rc = ks_build(who,t,s,sel,st,&scratch);
+  if (rc != CP_OK) (void)hipStreamSynchronize(st);
+  if (scratch) (void)hipFree(scratch);
+  if (rc != CP_OK)
+    { cp_kmer_sorted_destroy(s);
+      return rc;
+    }
+  *out = s;
   return CP_OK;
 }
 
@@ -368,21 +446,46 @@ extern "C" int cp_kmer_counts_sort(cp_kmer_counts *t, int64_t min_count, void *s
       if (rc != CP_OK) return rc;
     }
   else if (t->stream != st) HIPCHK(hipStreamSynchronize(t->stream));
-  cp_kmer_sorted *s = new (std::nothrow) cp_kmer_sorted();
-  if (!s) return set_err(CP_ENOMEM,"cp_kmer_counts_sort: out of memory");
-  s->K = t->K;
-  s->ibyte = cp_ktab_ibyte(t->K);
-  s->pbits = s->ibyte ? 8*s->ibyte : 2*t->K;
-  s->nb = (int64_t)1 << s->pbits;
-  void *scratch = nullptr;
-  const int rc = ks_build(t,s,(unsigned long long)min_count,st,&scratch);
-  if (rc != CP_OK) (void)hipStreamSynchronize(st);
-  if (scratch) (void)hipFree(scratch);
-  if (rc != CP_OK)
-    { cp_kmer_sorted_destroy(s);
-      return rc;
+  return ks_snapshot("cp_kmer_counts_sort",t,ks_sel_count{(unsigned long long)min_count},st,out);
+}
+
+extern "C" int cp_kmer_table_sort(cp_kmer_table *t, int label, int64_t min_total, int min_pct, void *stream,
+                                  cp_kmer_sorted **out)
+{ if (out) *out = nullptr;
+  if (!t || !out) return set_err(CP_EINVAL,"cp_kmer_table_sort: bad argument");
+  if (label < -1 || label > 3) return set_err(CP_EINVAL,"cp_kmer_table_sort: label must lie in [-1, 3]");
+  if (min_total < 1 || min_total > CP_MAX_KMER_CNT)
+    return set_err(CP_EINVAL,"cp_kmer_table_sort: min_total must lie in [1, 32767]");
+  if (min_pct < 0 || min_pct > 100) return set_err(CP_EINVAL,"cp_kmer_table_sort: min_pct must lie in [0, 100]");
+  hipStream_t st = (hipStream_t)stream;
+  if (t->stream != st) HIPCHK(hipStreamSynchronize(t->stream));
+  return ks_snapshot("cp_kmer_table_sort",t,
+                     ks_sel_class{label,(unsigned long long)min_total,(unsigned long long)min_pct},st,out);
+}
+
+extern "C" int cp_kmer_table_class_hist(cp_kmer_table *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt)
+{ if (!t || !hist || !ilowcnt || !ihighcnt) return set_err(CP_EINVAL,"cp_kmer_table_class_hist: bad argument");
+  hipStream_t st = t->stream;
+  const size_t cells = 4*((size_t)CP_MAX_KMER_CNT+1), bytes = cells*sizeof(unsigned long long);
+  unsigned long long *d_hist = nullptr;
+  int rc = ks_alloc("cp_kmer_table_class_hist",(void **)&d_hist,bytes,"the device histogram");
+  if (rc != CP_OK) return rc;
+  std::vector<unsigned long long> h(cells);
+  hipError_t e = hipMemsetAsync(d_hist,0,bytes,st);
+  if (e == hipSuccess)
+    { ks_class_hist_kernel<<<kt_grid(t->slots),KT_BLOCK,0,st>>>(t->tab,t->slots,d_hist);
+      e = hipGetLastError();
     }
-  *out = s;
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(),d_hist,bytes,hipMemcpyDeviceToHost,st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_hist);
+  if (e != hipSuccess) return set_err(CP_EHIP,std::string("cp_kmer_table_class_hist: ")+hipGetErrorString(e));
+  for (int l = 0; l < 4; l++)
+    { const unsigned long long *hl = h.data()+(size_t)l*(CP_MAX_KMER_CNT+1);
+      for (int c = 0; c < CP_MAX_KMER_CNT; c++) hist[(size_t)l*CP_MAX_KMER_CNT+c] = (int64_t)hl[c];
+      ilowcnt[l] = (int64_t)hl[0];
+      ihighcnt[l] = (int64_t)hl[CP_MAX_KMER_CNT];
+    }
   return CP_OK;
 }
 

@@ -480,6 +480,42 @@ int     cp_ktab_ibyte(int K);
 int     cp_ktab_tile(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Sorted k-mers of a label table (class2ktab): the same snapshot taken of a cp_kmer_table, one consensus class per
+ * call, so that the classes of the k-mers themselves become FASTK k-mer tables (the haploid k-mers as hap-mers, the
+ * repeat k-mers as a mask), and the FASTK histogram of each class.
+ *
+ *   Per key    total = the sum of the four label counts, in 64 bits (below 2^34); max = the largest of the four;
+ *              cls = the consensus label of "Per-k-mer label table": the largest count, a tie R > D > H > E.
+ *   Selected   a key for which all three hold: label == -1 or cls == label (label 0..3 is E, H, D, R; -1 is every
+ *              key); total >= min_total; 100 * max >= min_pct * total, in integers.  So min_pct = 100 keeps exactly
+ *              the unanimous keys, counts (2, 1, 0, 0) pass 66 and fail 67, and (1, 1, 0, 0) is class H, passes 50
+ *              and fails 51.
+ *   Result     an ordinary cp_kmer_sorted: the selected keys ascending by hi << 63 | lo, d_cnt the exact total;
+ *              cp_kmer_sorted_size, _bytes, _arrays, _ktab and _destroy work on it unchanged, a record carries
+ *              min(total, CP_MAX_KMER_CNT), and cp_kmer_sorted_ktab stays CP_EINVAL for K < 5.  An empty selection is
+ *              size 0 with null arrays and is no error.
+ *   Arguments  label in [-1, 3], min_total in [1, 32767], min_pct in [0, 100]; anything else is CP_EINVAL, and so is a
+ *              NULL t or out.  The table is untouched.
+ *   Table      only read: cp_kmer_table_stats and cp_kmer_table_export give the same before and after, and a snapshot
+ *              does not follow later adds.  Forward and canonical tables are both legal; the key order is the same.
+ *              Neither call reports or clears the table's deferred error (a caller that wants it asks
+ *              cp_kmer_table_stats first).  cp_kmer_table_sort synchronises `stream`, and the stream of the table's
+ *              last add first when the two differ.  An allocation that fails is CP_ENOMEM with the byte count in the
+ *              message, nothing leaked.
+ *   Histogram  cp_kmer_table_class_hist, for each class l in the order E, H, D, R: hist[l][c-1] = distinct keys with
+ *              cls == l and total == c for c < 32767, hist[l][32766] = those with total >= 32767, ilowcnt[l] =
+ *              hist[l][0], ihighcnt[l] = the sum of total over the keys with total >= 32767: the contract of
+ *              cp_kmer_counts_hist, four times.  No min_total and no min_pct.  Synchronises.
+ * On a canonical table the four class snapshots at min_total = 1, min_pct = 0 partition the label = -1 snapshot, which
+ * is cp_kmer_counts_sort(min_count 1) of a count table fed the same reads (keys, counts, records, index), and the
+ * four class histograms sum cell for cell to that table's cp_kmer_counts_hist.
+ */
+int     cp_kmer_table_sort(cp_kmer_table *t, int label, int64_t min_total, int min_pct, void *stream,
+                           cp_kmer_sorted **out);
+int     cp_kmer_table_class_hist(cp_kmer_table *t, int64_t *hist /* [4][32767] */, int64_t *ilowcnt /* [4] */,
+                                 int64_t *ihighcnt /* [4] */);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
