@@ -15,73 +15,13 @@
 //   -c  canonical k-mers (a k-mer and its reverse complement share one entry) for -u, -x and -C; under -u each line
 //       then carries the canonical k-mer's text.
 //   -v  a summary on stderr: distinct, unanimous and skipped k-mers, table size.
+// The batches of records and the table's fill are class_batch.h's, shared with class2ktab; -C walks the file a second
+// time through the same buffers.
 #include <charconv>
 #include <cmath>
-#include "gpu_tool.h"
-#include "class_record.h"
+#include "class_batch.h"
 
 static const char *USAGE = "[-v] [-c] [-u] [-x] [-C<out.class>] <estimate>.class <fastk_root>[.prof]";
-
-static const int64_t BATCH_BASES = (int64_t)256 << 20;        // bases per device batch
-
-// host and device buffers of one batch of records (pinned host memory)
-struct Batch
-  { char *h_seq = nullptr, *h_lab = nullptr, *d_seq = nullptr, *d_lab = nullptr;
-    int64_t *h_off = nullptr, *d_off = nullptr;
-    int64_t cap_bases = 0, cap_reads = 0, nbases = 0;
-    int nreads = 0;
-
-    void reserve(int64_t bases, int64_t reads)
-    { if (bases > cap_bases)
-        { if (h_seq) { HCHK(hipHostFree(h_seq)); HCHK(hipHostFree(h_lab)); HCHK(hipFree(d_seq)); HCHK(hipFree(d_lab)); }
-          HCHK(hipHostMalloc((void **)&h_seq,bases,hipHostMallocDefault));
-          HCHK(hipHostMalloc((void **)&h_lab,bases,hipHostMallocDefault));
-          HCHK(hipMalloc((void **)&d_seq,bases));
-          HCHK(hipMalloc((void **)&d_lab,bases));
-          cap_bases = bases;
-        }
-      if (reads+1 > cap_reads)
-        { if (h_off) { HCHK(hipHostFree(h_off)); HCHK(hipFree(d_off)); }
-          HCHK(hipHostMalloc((void **)&h_off,(reads+1)*8,hipHostMallocDefault));
-          HCHK(hipMalloc((void **)&d_off,(reads+1)*8));
-          cap_reads = reads+1;
-        }
-    }
-    void upload(bool labels)
-    { HCHK(hipMemcpy(d_seq,h_seq,nbases,hipMemcpyHostToDevice));
-      if (labels) HCHK(hipMemcpy(d_lab,h_lab,nbases,hipMemcpyHostToDevice));
-      HCHK(hipMemcpy(d_off,h_off,(nreads+1)*8,hipMemcpyHostToDevice));
-    }
-  };
-
-// Reads the records of `path` in batches of about BATCH_BASES bases; calls f(batch, headers) for each.
-template <class F>
-static void for_batches(const char *path, Batch &B, bool keep_headers, F f)
-{ FastxReader in(path);
-  if (!in.f) die("%s: Cannot open %s [errno=%d]\n",PROG,path,errno);
-  std::vector<std::string> headers;
-  B.reserve(BATCH_BASES,1 << 16);
-  B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
-  auto flush = [&]()
-    { if (B.nreads) f(B,headers);
-      B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
-      headers.clear();
-    };
-  while (in.next() >= 0)
-    { const int64_t n = (int64_t)in.seq.size();
-      if (in.qual.size() != in.seq.size())
-        die("%s: record %s of %s carries no labels\n",PROG,in.name.c_str(),path);
-      if (B.nbases+n > B.cap_bases || B.nreads+1 >= B.cap_reads) flush();
-      if (n > B.cap_bases) B.reserve(n,B.cap_reads);
-      memcpy(B.h_seq+B.nbases,in.seq.data(),n);
-      memcpy(B.h_lab+B.nbases,in.qual.data(),n);
-      B.nbases += n;
-      B.h_off[++B.nreads] = B.nbases;
-      if (keep_headers)
-        headers.push_back("@"+in.name+(in.rec_comment ? " "+in.comment : std::string()));
-    }
-  flush();
-}
 
 static std::string kmer_text(uint64_t hi, uint64_t lo, int K)
 { std::string s((size_t)K,'A');
@@ -158,25 +98,9 @@ int main(int argc, char **argv)
       return 0;
     }
 
-  HCHK(hipSetDevice(0));
-  cp_kmer_table *T = nullptr;
-  int rc = cp_kmer_table_create(K,canon ? 1 : 0,0,&T);
-  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_create");
-  Batch B;
-  for_batches(cls,B,false,[&](Batch &b, std::vector<std::string> &)
-    { b.upload(true);
-      int r = cp_kmer_table_add(T,b.d_seq,b.d_off,b.d_lab,b.nreads,b.nbases,nullptr);
-      if (r != CP_OK) cp_die(r,"cp_kmer_table_add");
-      HCHK(hipStreamSynchronize(nullptr));                        // the host buffers are refilled next
-    });
+  ClassBatch B;
   cp_kmer_stats st;
-  rc = cp_kmer_table_stats(T,&st);
-  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_stats");
-  if (verbose)
-    fprintf(stderr,"%s: K = %d%s: %lld k-mer positions, %lld distinct k-mers, %lld unanimous, %lld skipped "
-                   "(a base other than A C G T); table %lld slots, %.3f GB, %lld growth steps\n",
-            PROG,K,canon ? " canonical" : "",(long long)st.n_kmers,(long long)st.n_distinct,(long long)st.n_unanimous,
-            (long long)st.n_skipped,(long long)st.slots,st.bytes/1e9,(long long)st.growths);
+  cp_kmer_table *T = fill_label_table(cls,K,canon,verbose,B,&st);
 
   if (table)
     { const int64_t n = cp_kmer_table_export(T,nullptr,nullptr,nullptr,0);
@@ -210,8 +134,9 @@ int main(int argc, char **argv)
       if (!out) die("%s: Cannot open %s for 'w'\n",PROG,cns_out);
       std::vector<char> wbuf(1 << 22);
       setvbuf(out,wbuf.data(),_IOFBF,wbuf.size());
-      for_batches(cls,B,true,[&](Batch &b, std::vector<std::string> &headers)
-        { b.upload(true);
+      for_class_batches(cls,B,CLASS_BATCH_BASES,CLASS_BATCH_READS,true,
+                        [&](ClassBatch &b, std::vector<std::string> &headers)
+        { b.upload();
           int r = cp_kmer_table_consensus(T,b.d_seq,b.d_off,b.nreads,b.nbases,b.d_lab,nullptr);
           if (r != CP_OK) cp_die(r,"cp_kmer_table_consensus");
           HCHK(hipMemcpy(b.h_lab,b.d_lab,b.nbases,hipMemcpyDeviceToHost));
@@ -220,7 +145,7 @@ int main(int argc, char **argv)
               write_class_record(out,headers[(size_t)i],b.h_seq+s,(size_t)n,b.h_lab+s,(size_t)n);
             }
         });
-      rc = cp_kmer_table_stats(T,&st);                              // a k-mer missing from the table would show here
+      const int rc = cp_kmer_table_stats(T,&st);                    // a k-mer missing from the table would show here
       if (rc != CP_OK) cp_die(rc,"cp_kmer_table_consensus");
       if (fclose(out) != 0) die("%s: Cannot write %s\n",PROG,cns_out);
     }

@@ -6,8 +6,9 @@
 // <out_root>.<L>.hist (layouts: classpro_amd/fastk.py), <out_root> being the estimate's path without .class or
 // .class.gz, or -N.  libfastk's Root() strips only the .ktab suffix, so Open_Kmer_Stream("reads.H") finds the haploid
 // k-mers.  K comes from the .prof stub, as in class2cns; the key is always canonical, which is FASTK's key.
-// One pass over the .class in device batches on GPU 0 into a label table (cp_kmer_table_*, include/classpro_amd.h);
-// cp_kmer_table_stats then ends the run on a label other than E/H/D/R.  Then the per-class histograms
+// One pass over the .class in device batches on GPU 0 into a label table (class_batch.h fill_label_table, shared with
+// class2cns; cp_kmer_table_*, include/classpro_amd.h); cp_kmer_table_stats then ends the run on a label other than
+// E/H/D/R, and the batch buffers are given back before the first sort.  Then the per-class histograms
 // (cp_kmer_table_class_hist) and, class by class, a sorted snapshot (cp_kmer_table_sort, "Sorted k-mers of a label
 // table"), written by ktab_writer.h and destroyed before the next class is sorted.
 //   -t  a table holds the k-mers with at least that many occurrences over all labels (1..32767); it is the stub's minval.
@@ -19,88 +20,10 @@
 // A .hist covers every k-mer of its class, whatever -t and -a say.  A record carries min(occurrences, 32767).  Usage
 // errors, inputs that cannot be opened and outputs that cannot be created are reported before the GPU is touched, and
 // then nothing is created.
-#include <cerrno>
-#include "gpu_tool.h"
-#include "class_record.h"
+#include "class_batch.h"
 #include "ktab_writer.h"
 
 static const char *USAGE = "[-v] [-T<int(4)>] [-t<int(1)>] [-a<int(0)>] [-N<out_root>] <estimate>.class[.gz] <fastk_root>[.prof]";
-
-static const int64_t BATCH_BASES = (int64_t)256 << 20;        // bases per device batch
-
-// host and device buffers of one batch of records (pinned host memory)
-struct Batch
-  { char *h_seq = nullptr, *h_lab = nullptr, *d_seq = nullptr, *d_lab = nullptr;
-    int64_t *h_off = nullptr, *d_off = nullptr;
-    int64_t cap_bases = 0, cap_reads = 0, nbases = 0;
-    int nreads = 0;
-
-    void reserve(int64_t bases, int64_t reads)
-    { if (bases > cap_bases)
-        { if (h_seq) { HCHK(hipHostFree(h_seq)); HCHK(hipHostFree(h_lab)); HCHK(hipFree(d_seq)); HCHK(hipFree(d_lab)); }
-          HCHK(hipHostMalloc((void **)&h_seq,bases,hipHostMallocDefault));
-          HCHK(hipHostMalloc((void **)&h_lab,bases,hipHostMallocDefault));
-          HCHK(hipMalloc((void **)&d_seq,bases));
-          HCHK(hipMalloc((void **)&d_lab,bases));
-          cap_bases = bases;
-        }
-      if (reads+1 > cap_reads)
-        { if (h_off) { HCHK(hipHostFree(h_off)); HCHK(hipFree(d_off)); }
-          HCHK(hipHostMalloc((void **)&h_off,(reads+1)*8,hipHostMallocDefault));
-          HCHK(hipMalloc((void **)&d_off,(reads+1)*8));
-          cap_reads = reads+1;
-        }
-    }
-    void upload()
-    { HCHK(hipMemcpy(d_seq,h_seq,nbases,hipMemcpyHostToDevice));
-      HCHK(hipMemcpy(d_lab,h_lab,nbases,hipMemcpyHostToDevice));
-      HCHK(hipMemcpy(d_off,h_off,(nreads+1)*8,hipMemcpyHostToDevice));
-    }
-    void release()
-    { if (h_seq) { HCHK(hipHostFree(h_seq)); HCHK(hipHostFree(h_lab)); HCHK(hipFree(d_seq)); HCHK(hipFree(d_lab)); }
-      if (h_off) { HCHK(hipHostFree(h_off)); HCHK(hipFree(d_off)); }
-      h_seq = h_lab = d_seq = d_lab = nullptr;
-      h_off = d_off = nullptr;
-      cap_bases = cap_reads = 0;
-    }
-  };
-
-// Reads the records of `path` in batches of about BATCH_BASES bases; calls f(batch) for each.
-template <class F>
-static void for_batches(const char *path, Batch &B, F f)
-{ FastxReader in(path);
-  if (!in.f) die("%s: Cannot open %s [errno=%d]\n",PROG,path,errno);
-  B.reserve(BATCH_BASES,1 << 16);
-  B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
-  auto flush = [&]()
-    { if (B.nreads) f(B);
-      B.nreads = 0; B.nbases = 0; B.h_off[0] = 0;
-    };
-  while (in.next() >= 0)
-    { const int64_t n = (int64_t)in.seq.size();
-      if (in.qual.size() != in.seq.size())
-        die("%s: record %s of %s carries no labels\n",PROG,in.name.c_str(),path);
-      if (B.nbases+n > B.cap_bases || B.nreads+1 >= B.cap_reads) flush();
-      if (n > B.cap_bases) B.reserve(n,B.cap_reads);
-      memcpy(B.h_seq+B.nbases,in.seq.data(),n);
-      memcpy(B.h_lab+B.nbases,in.qual.data(),n);
-      B.nbases += n;
-      B.h_off[++B.nreads] = B.nbases;
-    }
-  flush();
-}
-
-// -t and -a: an integer in [lo, hi]
-static int arg_range(const char *a, const char *what, long long lo, long long hi)
-{ char *end;
-  errno = 0;
-  const long long v = strtoll(a+2,&end,10);
-  if (*end != '\0' || a[2] == '\0')
-    die("%s: -%c '%s' argument is not an integer\n",PROG,a[1],a+2);
-  if (errno != 0 || v < lo || v > hi)
-    die("%s: %s must lie in [%lld, %lld] (%s)\n",PROG,what,lo,hi,a+2);
-  return (int)v;
-}
 
 int main(int argc, char **argv)
 { PROG = "class2ktab";
@@ -120,8 +43,8 @@ int main(int argc, char **argv)
             break;
           case 'T': nthreads = arg_int(a,"Number of threads",true); break;
           case 'N': out_root = a+2; break;
-          case 't': min_total = arg_range(a,"Table cutoff",1,CP_MAX_KMER_CNT); break;
-          case 'a': min_pct = arg_range(a,"Agreement",0,100); break;
+          case 't': min_total = (int)arg_range(a,"Table cutoff",1,CP_MAX_KMER_CNT); break;
+          case 'a': min_pct = (int)arg_range(a,"Agreement",0,100); break;
         }
       else
         pos.push_back(a);
@@ -174,43 +97,24 @@ int main(int argc, char **argv)
   }
 
   // ---- the label table ----
-  HCHK(hipSetDevice(0));
-  cp_kmer_table *T = nullptr;
-  int rc = cp_kmer_table_create(K,1,0,&T);
-  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_create");
-  { Batch B;
-    for_batches(cls,B,[&](Batch &b)
-      { b.upload();
-        const int r = cp_kmer_table_add(T,b.d_seq,b.d_off,b.d_lab,b.nreads,b.nbases,nullptr);
-        if (r != CP_OK) cp_die(r,"cp_kmer_table_add");
-        HCHK(hipStreamSynchronize(nullptr));                        // the host buffers are refilled next
-      });
+  cp_kmer_stats st;
+  cp_kmer_table *T;
+  { ClassBatch B;
+    T = fill_label_table(cls,K,true,verbose,B,&st);
     B.release();                                                    // the snapshots want the room
   }
-  cp_kmer_stats st;
-  rc = cp_kmer_table_stats(T,&st);
-  if (rc != CP_OK) cp_die(rc,"cp_kmer_table_stats");
-  if (verbose)
-    fprintf(stderr,"%s: K = %d canonical: %lld k-mer positions, %lld distinct k-mers, %lld unanimous, %lld skipped "
-                   "(a base other than A C G T); table %lld slots, %.3f GB, %lld growth steps\n",
-            PROG,K,(long long)st.n_kmers,(long long)st.n_distinct,(long long)st.n_unanimous,(long long)st.n_skipped,
-            (long long)st.slots,st.bytes/1e9,(long long)st.growths);
 
   // ---- the histograms: every key of a class ----
   int64_t nkeys[4];
   { std::vector<int64_t> hist((size_t)4*CP_MAX_KMER_CNT);
     int64_t ilow[4], ihigh[4];
-    rc = cp_kmer_table_class_hist(T,hist.data(),ilow,ihigh);
+    const int rc = cp_kmer_table_class_hist(T,hist.data(),ilow,ihigh);
     if (rc != CP_OK) cp_die(rc,"cp_kmer_table_class_hist");
-    const int low = 1, high = CP_MAX_KMER_CNT;
     for (int l = 0; l < 4; l++)
       { const int64_t *h = hist.data()+(size_t)l*CP_MAX_KMER_CNT;
         nkeys[l] = 0;
         for (int c = 0; c < CP_MAX_KMER_CNT; c++) nkeys[l] += h[c];
-        const bool ok = fwrite(&K,4,1,fh[l]) == 1 && fwrite(&low,4,1,fh[l]) == 1 && fwrite(&high,4,1,fh[l]) == 1
-                        && fwrite(&ilow[l],8,1,fh[l]) == 1 && fwrite(&ihigh[l],8,1,fh[l]) == 1
-                        && fwrite(h,8,(size_t)CP_MAX_KMER_CNT,fh[l]) == (size_t)CP_MAX_KMER_CNT;
-        if (fclose(fh[l]) != 0 || !ok) die("%s: Cannot write %s\n",PROG,hist_path[l].c_str());
+        write_hist(fh[l],hist_path[l],K,ilow[l],ihigh[l],h);
       }
   }
 
@@ -218,7 +122,7 @@ int main(int argc, char **argv)
   KtabWriter W;
   for (int l = 0; l < 4; l++)
     { cp_kmer_sorted *sorted = nullptr;
-      rc = cp_kmer_table_sort(T,l,min_total,min_pct,nullptr,&sorted);
+      const int rc = cp_kmer_table_sort(T,l,min_total,min_pct,nullptr,&sorted);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_table_sort");
       W.write(sorted,K,min_total,nthreads,ft[l],tab_path[l],odir,oname+"."+LABELS[l]);
       cp_kmer_sorted_destroy(sorted);

@@ -163,8 +163,7 @@ int main(int argc, char **argv)
           die("rlen (%d) > rlen_max (%d)\n",rlen,rlen_max);
         }
       if (truth_path)                                              // class2acc.c:141-160
-        { const size_t sp = header.find(' ');
-          const std::string name = header.substr(1,sp == std::string::npos ? std::string::npos : sp-1);
+        { const std::string name = class_header_name(header);
           if (tru.next() < 0)
             die("# seqs in %s > # seqs in %s\n",out_path.c_str(),truth_path);
           if (name != tru.name)

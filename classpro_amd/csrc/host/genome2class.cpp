@@ -272,8 +272,7 @@ int main(int argc, char **argv)
         }
       if (est_path)                                                  // class2acc.c:141-160, this file being the truth
         { const int id = (int)nreads+1;
-          const size_t sp = S.header.find(' ');
-          const std::string name = S.header.substr(1,sp == std::string::npos ? std::string::npos : sp-1);
+          const std::string name = class_header_name(S.header);
           if (est.next() < 0)
             die("# seqs in %s < # seqs in %s\n",est_path,class_path.c_str());
           if (est.name != name)

@@ -1,6 +1,7 @@
-// gpu_tool.h -- what the command-line tools that use the GPU share (ClassGS, class2cns, kprof, genome2class): how a
-// failed library or HIP call ends the tool, a device buffer that only grows, and the accuracy totals read from the
-// device.  Needs the HIP runtime, so the host-only tools (prof2class, class2acc) do not include it.
+// gpu_tool.h -- what the command-line tools that use the GPU share (ClassGS, class2cns, class2ktab, kprof,
+// genome2class): how a failed library or HIP call ends the tool, a device buffer that only grows until it is given
+// back, and the accuracy totals read from the device.  Needs the HIP runtime, so the host-only tools (prof2class,
+// class2acc) do not include it.  class_batch.h builds the .class batches of class2cns and class2ktab on it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "host_io.h"
@@ -15,7 +16,7 @@ static void hip_die(hipError_t e, const char *what)
 
 #define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) hip_die(e_,#call); } while (0)
 
-// a device buffer that only grows
+// a device buffer that only grows, until release() gives it back
 template <class T>
 struct DevBuf
   { T *p = nullptr;
@@ -27,6 +28,11 @@ struct DevBuf
           HCHK(hipMalloc((void **)&p,cap*sizeof(T)));
         }
       return p;
+    }
+    void release()
+    { if (p) HCHK(hipFree(p));
+      p = nullptr;
+      cap = 0;
     }
     void up(const std::vector<T> &h) { need(h.size()+1); if (!h.empty()) HCHK(hipMemcpy(p,h.data(),h.size()*sizeof(T),hipMemcpyHostToDevice)); }
   };

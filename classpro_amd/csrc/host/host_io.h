@@ -1,11 +1,12 @@
 // host_io.h -- host-side readers shared by the command-line tools: the forms of a <source> argument,
-// FASTX with kseq.h semantics, the FASTK profile index / histogram files, gene_core-style option
-// parsing.  Plain C++; no device code.
+// FASTX with kseq.h semantics, the FASTK profile index, the histogram file (read and written),
+// gene_core-style option parsing.  Plain C++; no device code.
 #pragma once
 #include <zlib.h>
 #include <fcntl.h>
 #include <strings.h>
 #include <unistd.h>
+#include <cerrno>
 #include <cstdio>
 #include <cstdarg>
 #include <cstdlib>
@@ -68,6 +69,17 @@ static int arg_int(const char *arg, const char *what, bool positive)
   if (positive ? v <= 0 : v < 0)
     die("%s: %s must be %s (%ld)\n",PROG,what,positive ? "positive" : "non-negative",v);
   return (int)v;
+}
+// an integer in [lo, hi]; `unit` follows the range in the message (" MiB")
+static long long arg_range(const char *arg, const char *what, long long lo, long long hi, const char *unit = "")
+{ char *end;
+  errno = 0;
+  const long long v = strtoll(arg+2,&end,10);
+  if (*end != '\0' || arg[2] == '\0')
+    die("%s: -%c '%s' argument is not an integer\n",PROG,arg[1],arg+2);
+  if (errno != 0 || v < lo || v > hi)
+    die("%s: %s must lie in [%lld, %lld]%s (%s)\n",PROG,what,lo,hi,unit,arg+2);
+  return v;
 }
 
 // ---- FASTX reader with kseq.h semantics (name up to the first space, comment = rest of the header
@@ -236,3 +248,11 @@ static bool load_hist(const std::string &fk_root, int *low, int *high, int64_t *
   return ok;
 }
 
+// The FASTK histogram a tool opened as `path`: K, the counts 1 .. 32767 in `bins`, the k-mers below and above.  Closes f.
+static void write_hist(FILE *f, const std::string &path, int K, int64_t ilow, int64_t ihigh, const int64_t *bins)
+{ const int low = 1, high = 32767;
+  const bool ok = fwrite(&K,4,1,f) == 1 && fwrite(&low,4,1,f) == 1 && fwrite(&high,4,1,f) == 1
+                  && fwrite(&ilow,8,1,f) == 1 && fwrite(&ihigh,8,1,f) == 1
+                  && fwrite(bins,8,(size_t)high,f) == (size_t)high;
+  if (fclose(f) != 0 || !ok) die("%s: Cannot write %s\n",PROG,path.c_str());
+}

@@ -26,7 +26,6 @@
 // Without -t every file is what it was.  K < 5 has no .ktab (the reader decodes one to three prefix bytes).
 // A k-mer with a byte other than upper-case A C G T is not counted and gets count 0; how many there were is always said
 // on stderr.  FastK's own treatment of such bases is not reproduced.
-#include <cerrno>
 #include "gpu_tool.h"
 #include "read_source.h"
 #include "prof_writer.h"
@@ -66,28 +65,8 @@ int main(int argc, char **argv)
           case 'k': K = arg_int(a,"K-mer length",true); break;
           case 'T': nthreads = arg_int(a,"Number of threads",true); break;
           case 'N': out_root = a+2; break;
-          case 't':
-            { char *end;
-              errno = 0;
-              const long long v = strtoll(a+2,&end,10);
-              if (*end != '\0' || a[2] == '\0')
-                die("%s: -t '%s' argument is not an integer\n",PROG,a+2);
-              if (errno != 0 || v < 1 || v > CP_MAX_KMER_CNT)
-                die("%s: Table cutoff must lie in [1, %d] (%s)\n",PROG,CP_MAX_KMER_CNT,a+2);
-              tab_min = (int)v;
-              break;
-            }
-          case 'f':
-            { char *end;
-              errno = 0;
-              const long long v = strtoll(a+2,&end,10);
-              if (*end != '\0' || a[2] == '\0')
-                die("%s: -f '%s' argument is not an integer\n",PROG,a+2);
-              if (errno != 0 || v < 0 || v > MAX_FILTER_MIB)
-                die("%s: Filter size must lie in [0, %lld] MiB (%s)\n",PROG,MAX_FILTER_MIB,a+2);
-              filter_mib = v;
-              break;
-            }
+          case 't': tab_min = (int)arg_range(a,"Table cutoff",1,CP_MAX_KMER_CNT); break;
+          case 'f': filter_mib = arg_range(a,"Filter size",0,MAX_FILTER_MIB," MiB"); break;
         }
       else
         pos.push_back(a);
@@ -157,26 +136,27 @@ int main(int argc, char **argv)
       if (rc != CP_OK) cp_die(rc,marking ? "cp_kmer_counts_mark" : "cp_kmer_counts_add");
       B.clear();
     };
-  while (S.next())
-    { push();
-      nreads++;
-      nbases += (int64_t)S.seq.size();
-      if (B.soff.back() >= BATCH_BASES) add();
-    }
-  add();
+  // One pass over the reads: each is pushed, and `batch` takes what has gathered at BATCH_BASES and at the end.  The
+  // first pass counts the reads and bases; a later one starts the source again and has to meet the same reads.
+  auto pass = [&](bool first, const auto &batch)
+    { if (!first) S.rewind();
+      int64_t seen = 0;
+      while (S.next())
+        { if (!first && seen >= nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+          push();
+          seen++;
+          if (first) nbases += (int64_t)S.seq.size();
+          if (B.soff.back() >= BATCH_BASES) batch();
+        }
+      batch();
+      if (first) nreads = seen;
+      else if (seen != nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+    };
+  pass(true,add);
   device_up();
   if (marking)                                                      // the same reads again, counted
     { marking = false;
-      S.rewind();
-      int64_t again = 0;
-      while (S.next())
-        { if (again >= nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
-          push();
-          again++;
-          if (B.soff.back() >= BATCH_BASES) add();
-        }
-      add();
-      if (again != nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+      pass(false,add);
     }
 
   cp_kmer_count_stats st;
@@ -186,11 +166,7 @@ int main(int argc, char **argv)
     int64_t ilow = 0, ihigh = 0;
     rc = cp_kmer_counts_hist(T,hist.data(),&ilow,&ihigh);
     if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_hist");
-    const int low = 1, high = CP_MAX_KMER_CNT;
-    bool ok = fwrite(&K,4,1,fh) == 1 && fwrite(&low,4,1,fh) == 1 && fwrite(&high,4,1,fh) == 1
-              && fwrite(&ilow,8,1,fh) == 1 && fwrite(&ihigh,8,1,fh) == 1
-              && fwrite(hist.data(),8,hist.size(),fh) == hist.size();
-    if (fclose(fh) != 0 || !ok) die("%s: Cannot write %s\n",PROG,hist_path.c_str());
+    write_hist(fh,hist_path,K,ilow,ihigh,hist.data());
   }
 
   // ---- -t: the sorted table, between the passes ----
@@ -248,16 +224,7 @@ int main(int argc, char **argv)
         W.append((int)((int64_t)n*t/nt),(int)((int64_t)n*(t+1)/nt),code[(size_t)t].data());
       B.clear();
     };
-  S.rewind();
-  int64_t again = 0;
-  while (S.next())
-    { if (again >= nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
-      push();
-      again++;
-      if (B.soff.back() >= BATCH_BASES) profile();
-    }
-  profile();
-  if (again != nreads) die("%s: %s changed while it was read\n",PROG,S.path.c_str());
+  pass(false,profile);
   rc = cp_kmer_counts_stats(T,&st);
   if (rc != CP_OK) cp_die(rc,"cp_kmer_counts_stats");
   W.close();

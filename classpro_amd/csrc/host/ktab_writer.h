@@ -28,7 +28,7 @@ struct KtabWriter
         rc = cp_kmer_sorted_ktab(sorted,0,0,nullptr,d_index.p,nullptr);
         if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_ktab");
         HCHK(hipMemcpy(index.data(),d_index.p,index.size()*8,hipMemcpyDeviceToHost));
-        HCHK(hipFree(d_index.p));
+        d_index.release();
         const bool ok = fwrite(&K,4,1,ft) == 1 && fwrite(&nparts,4,1,ft) == 1 && fwrite(&minval,4,1,ft) == 1
                         && fwrite(&ibyte,4,1,ft) == 1 && fwrite(index.data(),8,index.size(),ft) == index.size();
         if (fclose(ft) != 0 || !ok) die("%s: Cannot write %s\n",PROG,tab_path.c_str());
@@ -52,9 +52,5 @@ struct KtabWriter
         }
     }
     // gives the transfer buffer back
-    void release()
-    { if (d_rec.p) HCHK(hipFree(d_rec.p));
-      d_rec.p = nullptr;
-      d_rec.cap = 0;
-    }
+    void release() { d_rec.release(); }
   };
