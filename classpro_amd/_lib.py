@@ -25,6 +25,8 @@ SYMBOLS = [
     "cp_kmer_counts_sort", "cp_kmer_sorted_destroy", "cp_kmer_sorted_size", "cp_kmer_sorted_bytes",
     "cp_kmer_sorted_arrays", "cp_kmer_sorted_ktab", "cp_ktab_ibyte", "cp_ktab_tile",
     "cp_kmer_table_sort", "cp_kmer_table_class_hist",
+    "cp_kmer_sorted_load_begin", "cp_kmer_sorted_load_records", "cp_kmer_sorted_load_end", "cp_kmer_sorted_find",
+    "cp_kmer_sorted_profiles",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -157,6 +159,11 @@ def lib():
     L.cp_ktab_tile.argtypes = []
     L.cp_kmer_table_sort.argtypes = [vp, i32, i64, i32, vp, C.POINTER(vp)]
     L.cp_kmer_table_class_hist.argtypes = [vp, vp, vp, vp]
+    L.cp_kmer_sorted_load_begin.argtypes = [i32, vp, C.POINTER(vp)]
+    L.cp_kmer_sorted_load_records.argtypes = [vp, i64, vp, vp]
+    L.cp_kmer_sorted_load_end.argtypes = [vp, vp]
+    L.cp_kmer_sorted_find.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.cp_kmer_sorted_profiles.argtypes = [vp, i32, vp, vp, vp, i32, i64, vp, vp, vp]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -601,14 +601,18 @@ class KmerCounts:
 
 
 class SortedKmers:
-    """A sorted snapshot of a `KmerCounts` or a `KmerTable` (cp_kmer_sorted_*; semantics in include/classpro_amd.h,
-    "Sorted k-mers").  len() is the number of entries; `.hi`, `.lo` (key = hi << 63 | lo) and `.counts` (exact) are int64 device
+    """A sorted snapshot of a `KmerCounts` or a `KmerTable`, or one loaded from a FASTK k-mer table (`from_records`,
+    `from_ktab`), which `find` and `profiles` query (cp_kmer_sorted_*; semantics in include/classpro_amd.h, "Sorted k-mers"
+    and "Sorted k-mers as input").  len() is the number of entries; `.hi`, `.lo` (key = hi << 63 | lo) and `.counts` (exact) are int64 device
     tensors that VIEW the snapshot's memory; `.nbytes` is the device memory held.  A tensor taken from them keeps the
     snapshot alive, so the memory is freed when the object and all such tensors are gone -- or at once by `close()`,
     after which any tensor still held points at freed memory: clone what has to outlive an explicit `close()`."""
 
     def __init__(self, table, handle):
         self.L, self.device, self.K = table.L, table.device, table.K
+        self._adopt(handle)
+
+    def _adopt(self, handle):
         self.s = handle
         self.n = check(self.L.cp_kmer_sorted_size(self.s))
         self.nbytes = check(self.L.cp_kmer_sorted_bytes(self.s))
@@ -635,6 +639,92 @@ class SortedKmers:
 
     def __len__(self):
         return self.n
+
+    @classmethod
+    def from_records(cls, K, index, records, device="cuda:0", piece=None):
+        """A snapshot loaded from the payload of a FASTK k-mer table (cp_kmer_sorted_load_*; "Sorted k-mers as input" in
+        include/classpro_amd.h): `index` the stub's int64 prefix index (numpy or tensor), `records` the records of all
+        parts in file order as uint8 (numpy, or a tensor on the host or the device, any alignment), loaded in pieces of
+        `piece` entries (None: one piece).  Raises ClassProError (CP_EINVAL) for an index that decreases, records that
+        do not match it, or keys that are not strictly ascending."""
+        self = cls.__new__(cls)
+        self.L, self.device, self.K, self.s = lib(), torch.device(device), K, None
+        if self.device.type != "cuda":
+            raise ValueError("classpro_amd runs on a HIP device only")
+        torch.cuda.set_device(self.device)
+        idx = np.ascontiguousarray(index.cpu().numpy() if isinstance(index, torch.Tensor) else index, np.int64)
+        ibyte = self.L.cp_ktab_ibyte(K)
+        if ibyte and len(idx) != 1 << (8 * ibyte):
+            raise ValueError("the index of a table of %d-mers has %d cells" % (K, 1 << (8 * ibyte)))
+        pbyte = ((K + 3) >> 2) - ibyte + 2
+        rec = records if isinstance(records, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(records, np.uint8))
+        if rec.dtype != torch.uint8 or rec.dim() != 1 or rec.numel() % pbyte:
+            raise ValueError("records must be a flat uint8 array of whole %d-byte records" % pbyte)
+        n = rec.numel() // pbyte
+        piece = max(n, 1) if piece is None else int(piece)
+        if piece < 1:
+            raise ValueError("piece must be positive")
+        h = C.c_void_p()
+        check(self.L.cp_kmer_sorted_load_begin(K, idx.ctypes.data, C.byref(h)))
+        try:
+            for e in range(0, n, piece):
+                m = min(piece, n - e)
+                part = rec[e * pbyte:(e + m) * pbyte]
+                part = part if part.device == self.device else part.to(self.device)
+                check(self.L.cp_kmer_sorted_load_records(h, m, part.data_ptr(), _stream_of(self.device)))
+            check(self.L.cp_kmer_sorted_load_end(h, _stream_of(self.device)))
+        except Exception:
+            self.L.cp_kmer_sorted_destroy(h)
+            raise
+        self._adopt(h)
+        return self
+
+    @classmethod
+    def from_ktab(cls, dirpath, root, device="cuda:0", piece=1 << 22):
+        """`from_records` of the table `<dirpath>/<root>.ktab` and its parts (fastk.read_fastk_ktab_raw)."""
+        from .fastk import read_fastk_ktab_raw
+        K, _minval, _ibyte, index, records = read_fastk_ktab_raw(dirpath, root)
+        return cls.from_records(K, index, records, device=device, piece=piece)
+
+    def find(self, hi, lo):
+        """cp_kmer_sorted_find: for keys hi << 63 | lo given as int64 device tensors of equal length, an int64 device
+        tensor of their ordinals in the snapshot, -1 for a key that is absent."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if hi.shape != lo.shape or hi.dim() != 1 or hi.dtype != torch.int64 or lo.dtype != torch.int64:
+            raise ValueError("hi and lo must be flat int64 tensors of equal length")
+        hi, lo = hi.to(self.device).contiguous(), lo.to(self.device).contiguous()
+        pos = torch.empty(hi.numel(), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_find(self.s, hi.data_ptr() if hi.numel() else None, lo.data_ptr() if hi.numel() else None,
+                                             hi.numel(), pos.data_ptr() if hi.numel() else None, _stream_of(self.device)))
+        return pos
+
+    def profiles(self, batch, canonical=True, tally=None):
+        """cp_kmer_sorted_profiles: the profiles of a `Batch` (its `prof` tensor is filled in place, ready for
+        `threshold_labels` and `Classifier.classify`) or of a tuple of device tensors (seq uint8, seq_off int64 [n+1])
+        RELATIVE to this snapshot: per k-mer min(count, 32767) of its key, 0 for a key that is absent and for a k-mer
+        with a byte other than upper-case A C G T.  canonical=False looks the forward k-mer up (the snapshots of a
+        forward `KmerTable`).  `tally`, an int64 device tensor [3], is added to: cells present, absent, with other
+        bytes.  Returns a uint16 device tensor in the `prof` layout, as `KmerCounts.profiles` does."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if isinstance(batch, Batch):
+            seq, seq_off, prof_off, n, total = batch.seq, batch.seq_off, batch.prof_off, batch.nreads, batch.total_bases
+            nk, out = batch.total_kmers, batch.prof
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+            prof_off = torch.zeros(n + 1, dtype=torch.int64, device=seq_off.device)
+            torch.cumsum((seq_off[1:] - seq_off[:-1] - (self.K - 1)).clamp(min=0), 0, out=prof_off[1:])
+            nk = int(prof_off[-1].item())
+            out = torch.empty(max(nk, 8), dtype=torch.int16, device=seq_off.device)
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_profiles(self.s, 1 if canonical else 0, seq.data_ptr(), seq_off.data_ptr(),
+                                                 prof_off.data_ptr(), n, total, out.data_ptr(),
+                                                 tally.data_ptr() if tally is not None else None, _stream_of(self.device)))
+        return out.view(torch.uint16)[:nk]
 
     def ktab(self, first=0, n=None):
         """(records, index): the FASTK .ktab records of the entries [first, first+n) (n = None: to the end) as a uint8

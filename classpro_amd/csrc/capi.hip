@@ -1168,5 +1168,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // sorted snapshot of a count table and its FASTK .ktab payload (kprof -t): kmer_sort.hip
 #include "kmer_sort.hip"
 
+// sorted snapshots as input: loaded from a .ktab payload, key lookup and relative profiles (tab2prof): kmer_lookup.hip
+#include "kmer_lookup.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

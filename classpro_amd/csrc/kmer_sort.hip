@@ -33,6 +33,8 @@ struct cp_kmer_sorted
     int64_t nb;                            // buckets = 1 << pbits
     unsigned long long *key;               // hi[n], lo[n], cnt[n] in one allocation (null when n = 0)
     int64_t *start;                        // nb+1 bucket starts; start[nb] = n
+    bool ready;                            // sorted here, or loaded and checked (kmer_lookup.hip): the queries take it
+    int64_t filled;                        // a snapshot being loaded: the entries appended so far
   };
 
 __device__ static inline unsigned long long ks_bucket(unsigned long long hi, unsigned long long lo, int shift)
@@ -429,6 +431,8 @@ static int ks_snapshot(const char *who, Tab *t, Sel sel, hipStream_t st, cp_kmer
     { cp_kmer_sorted_destroy(s);
       return rc;
     }
+  s->ready = true;
+  s->filled = s->n;
   *out = s;
   return CP_OK;
 }
@@ -502,6 +506,7 @@ extern "C" int64_t cp_kmer_sorted_bytes(const cp_kmer_sorted *s)
 extern "C" int cp_kmer_sorted_arrays(const cp_kmer_sorted *s, const uint64_t **d_hi, const uint64_t **d_lo,
                                      const uint64_t **d_cnt)
 { if (!s || !d_hi || !d_lo || !d_cnt) return set_err(CP_EINVAL,"cp_kmer_sorted_arrays: bad argument");
+  if (!s->ready) return set_err(CP_EINVAL,"cp_kmer_sorted_arrays: the snapshot is still being loaded");
   *d_hi = s->n ? (const uint64_t *)s->key : nullptr;
   *d_lo = s->n ? (const uint64_t *)(s->key+s->n) : nullptr;
   *d_cnt = s->n ? (const uint64_t *)(s->key+2*s->n) : nullptr;
@@ -511,6 +516,7 @@ extern "C" int cp_kmer_sorted_arrays(const cp_kmer_sorted *s, const uint64_t **d
 extern "C" int cp_kmer_sorted_ktab(cp_kmer_sorted *s, int64_t first, int64_t n, uint8_t *d_records, int64_t *d_index,
                                    void *stream)
 { if (!s) return set_err(CP_EINVAL,"cp_kmer_sorted_ktab: bad argument");
+  if (!s->ready) return set_err(CP_EINVAL,"cp_kmer_sorted_ktab: the snapshot is still being loaded");
   if (s->ibyte == 0) return set_err(CP_EINVAL,"cp_kmer_sorted_ktab: there is no .ktab for K < 5");
   if (first < 0 || n < 0 || first > s->n || n > s->n-first)
     return set_err(CP_EINVAL,"cp_kmer_sorted_ktab: the range does not lie in the snapshot");

@@ -209,6 +209,32 @@ def read_fastk_ktab(dirpath, root):
     return K, min_count, ibyte, keys, counts
 
 
+def read_fastk_ktab_raw(dirpath, root):
+    """Returns (K, min_count, ibyte, index, records): the stub's prefix index as an int64 array of 1 << 8*ibyte and the
+    records of all parts, in file order, as one uint8 array -- the payload as it is on disk, no key decoded (what
+    `SortedKmers.from_records` takes).  The checks are those of read_fastk_ktab."""
+    with open(os.path.join(dirpath, root + ".ktab"), "rb") as f:
+        K, nparts, min_count, ibyte = struct.unpack("<iiii", f.read(16))
+        index = np.frombuffer(f.read(8 << (8 * ibyte)), dtype="<i8").astype(np.int64)
+    if len(index) != 1 << (8 * ibyte):
+        raise ValueError("the stub is truncated")
+    pbyte = ((K + 3) >> 2) - ibyte + 2
+    parts = []
+    for p in range(nparts):
+        with open(os.path.join(dirpath, ".%s.ktab.%d" % (root, p + 1)), "rb") as f:
+            pk, n = struct.unpack("<iq", f.read(12))
+            if pk != K:
+                raise ValueError("part %d has another K than the stub" % (p + 1))
+            part = np.frombuffer(f.read(), np.uint8)
+            if len(part) != n * pbyte:
+                raise ValueError("part %d does not hold %d records" % (p + 1, n))
+            parts.append(part)
+    records = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    if int(index[-1]) * pbyte != len(records):
+        raise ValueError("the index ends at %d, the parts hold %d entries" % (int(index[-1]), len(records) // pbyte))
+    return K, min_count, ibyte, index, records
+
+
 def write_fasta(path, names, seqs, gz=None, comments=None):
     gz = path.endswith(".gz") if gz is None else gz
     op = gzip.open if gz else open

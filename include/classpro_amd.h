@@ -516,6 +516,55 @@ int     cp_kmer_table_class_hist(cp_kmer_table *t, int64_t *hist /* [4][32767] *
                                  int64_t *ihighcnt /* [4] */);
 
 /* ------------------------------------------------------------------------------------------
+ * Sorted k-mers as input (tab2prof): a snapshot loaded from the payload of a FASTK k-mer table, and the two queries that
+ * every snapshot answers -- what libfastk.c's Load_Kmer_Table, Find_Kmer and `FastK -p:<table>` do with a .ktab.
+ *
+ *   Load       the exact inverse of cp_kmer_sorted_ktab, in three steps.
+ *              load_begin    `index` is the stub's HOST array of 1 << 8*ibyte int64, ibyte = cp_ktab_ibyte(K).  K must lie
+ *                            in [5, 63] and the index must be non-negative and non-decreasing, otherwise CP_EINVAL.  n =
+ *                            the last index cell.  Allocates the 24 n bytes and the bucket starts (start[0] = 0,
+ *                            start[p+1] = index[p]); an allocation that fails is CP_ENOMEM with the byte count in the
+ *                            message, nothing leaked.  Synchronous (one copy of the starts).
+ *              load_records  appends the next n entries from device bytes of any alignment, n * pbyte of them, in file
+ *                            order (so there is no `first`); n = 0 is legal, an append past the end is CP_EINVAL and
+ *                            appends nothing.  An entry's prefix is the bucket whose range of the index holds its
+ *                            ordinal; the key is prefix and the record's hbyte bytes with the pad bits of the last byte
+ *                            dropped; the count is the little-endian uint16.  Asynchronous on `stream`; the bytes may be
+ *                            reused once the stream has passed the call.
+ *              load_end      CP_EINVAL unless all n entries were appended.  Then checks key[i-1] < key[i] for every i:
+ *                            a key that repeats or steps back is CP_EINVAL with the first offending ordinal i in the
+ *                            message (the snapshot stays unready).  Synchronises `stream`.
+ *   Ready      only after a successful load_end is a loaded snapshot ready; the snapshots of cp_kmer_counts_sort and
+ *              cp_kmer_table_sort are born ready.  On a snapshot that is not ready cp_kmer_sorted_find, _profiles,
+ *              _ktab and _arrays are CP_EINVAL; _size, _bytes and _destroy are always legal.  load_records and load_end
+ *              on a ready snapshot are CP_EINVAL.  A loaded snapshot is an ordinary cp_kmer_sorted: its _ktab gives back
+ *              the bytes it was loaded from (records whose pad bits were 0) and the index.
+ *   Find       d_pos[i] = the ordinal of the key d_hi[i] << 63 | d_lo[i] in the snapshot, or -1 when it is absent (so is a
+ *              key that no k-mer of this K can have): Find_Kmer's return value (libfastk.c:662-709) for a key that is
+ *              canonical already.  Works for every K a snapshot can have, K < 5 included (a bucket is the whole key).
+ *   Profiles   the cell layout of cp_kmer_counts_profiles: d_prof[d_prof_off[r] + i] = min(cnt, 32767) of the key of the
+ *              k-mer at positions [i, i+K) of read r, or 0 when that key is absent.  With `canonical` non-zero the key is
+ *              min(forward, reverse complement), the key of a count table; with 0 it is the forward k-mer, for the
+ *              snapshots of a forward cp_kmer_table.  A k-mer that holds a byte other than upper-case A C G T gives 0.
+ *              An absent key is never an error.  d_tally, when not NULL, is int64 [3] on the device and is ADDED TO:
+ *              cells present, cells absent, cells with other bytes.  Reads shorter than K and empty reads are legal.
+ *   Lookup     bucket = the key's top 8*ibyte bits (the whole key for K < 5), then a binary search over
+ *              [start[bucket], start[bucket+1]) clamped to [0, n], at most 64 probes: no content of a snapshot can make
+ *              a lookup run on or read outside the arrays (the first two probes may be placed by interpolation on the
+ *              key's suffix instead of at the middle; the result is the same).  When 2K-63 <= 8*ibyte (K <= 43 with three prefix bytes, every
+ *              K <= 31) the bucket fixes hi: only lo is compared and hi[] is never read.
+ * The snapshot is only read by both queries; both are asynchronous on `stream`.
+ */
+int     cp_kmer_sorted_load_begin(int K, const int64_t *index, cp_kmer_sorted **out);
+int     cp_kmer_sorted_load_records(cp_kmer_sorted *s, int64_t n, const uint8_t *d_records, void *stream);
+int     cp_kmer_sorted_load_end(cp_kmer_sorted *s, void *stream);
+int     cp_kmer_sorted_find(const cp_kmer_sorted *s, const uint64_t *d_hi, const uint64_t *d_lo, int64_t m,
+                            int64_t *d_pos, void *stream);
+int     cp_kmer_sorted_profiles(const cp_kmer_sorted *s, int canonical, const char *d_seq, const int64_t *d_seq_off,
+                                const int64_t *d_prof_off, int nreads, int64_t total_bases, uint16_t *d_prof,
+                                int64_t *d_tally, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
