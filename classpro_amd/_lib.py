@@ -27,6 +27,7 @@ SYMBOLS = [
     "cp_kmer_table_sort", "cp_kmer_table_class_hist",
     "cp_kmer_sorted_load_begin", "cp_kmer_sorted_load_records", "cp_kmer_sorted_load_end", "cp_kmer_sorted_find",
     "cp_kmer_sorted_profiles",
+    "cp_kmer_sorted_combine", "cp_kmer_sorted_hist",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -164,6 +165,8 @@ def lib():
     L.cp_kmer_sorted_load_end.argtypes = [vp, vp]
     L.cp_kmer_sorted_find.argtypes = [vp, vp, vp, i64, vp, vp]
     L.cp_kmer_sorted_profiles.argtypes = [vp, i32, vp, vp, vp, i32, i64, vp, vp, vp]
+    L.cp_kmer_sorted_combine.argtypes = [vp, vp, i32, i32, vp, vp, vp, C.POINTER(vp)]
+    L.cp_kmer_sorted_hist.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -741,6 +741,62 @@ class SortedKmers:
                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return rec, idx
 
+    _SET_OPS = {"and": 0, "or": 1, "sub": 2, "xor": 3}
+    _CNT_OPS = {"left": 0, "sum": 1, "min": 2, "max": 3}
+
+    def _combine(self, other, op, count, a_range, b_range, build):
+        if op not in self._SET_OPS:
+            raise ValueError("op must be one of 'and', 'or', 'sub', 'xor'")
+        if count not in self._CNT_OPS:
+            raise ValueError("count must be one of 'left', 'sum', 'min', 'max'")
+        if not isinstance(other, SortedKmers):
+            raise ValueError("the other operand must be a SortedKmers")
+        if self.s is None or other.s is None:
+            raise ValueError("SortedKmers is closed")
+        if other.K != self.K or other.device != self.device:
+            raise ValueError("the operands must hold k-mers of the same length on the same device")
+        rng = None
+        if a_range is not None or b_range is not None:
+            ends = []
+            for r in (a_range, b_range):
+                lo, hi = (None, None) if r is None else r
+                ends += [1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi)]
+            rng = (C.c_int64 * 4)(*ends)
+        tally = (C.c_int64 * 4)()
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_combine(self.s, other.s, self._SET_OPS[op], self._CNT_OPS[count], rng, tally,
+                                                _stream_of(self.device), C.byref(h) if build else None))
+        return h, tuple(tally)
+
+    def combine(self, other, op, count="left", a_range=None, b_range=None):
+        """cp_kmer_sorted_combine ("Set algebra on sorted k-mers" in include/classpro_amd.h): this snapshot (A) and
+        `other` (B) of the same K as a new `SortedKmers`.  `op` is "and", "or", "sub" or "xor"; `count` is "left", "sum",
+        "min" or "max"; a range is (lo, hi) on the operand's counts, either end None for open, and an entry outside its
+        range counts as absent.  The result has `.tally == (only_a, only_b, both, out)`, holds memory of its own and keeps
+        no reference to either operand.  Both operands are only read; `other` may be `self`."""
+        h, tally = self._combine(other, op, count, a_range, b_range, True)
+        out = SortedKmers.__new__(SortedKmers)
+        out.L, out.device, out.K = self.L, self.device, self.K
+        out._adopt(h)
+        out.tally = tally
+        return out
+
+    def compare(self, other, a_range=None, b_range=None):
+        """(only_a, only_b, both): the tally of `combine` with nothing built (cp_kmer_sorted_combine with out == NULL)."""
+        return self._combine(other, "and", "left", a_range, b_range, False)[1][:3]
+
+    def hist(self):
+        """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
+        (1, 32767, ilowcnt, ihighcnt, int64[32767])."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        h = np.zeros(32767, np.int64)
+        il, ih = C.c_int64(), C.c_int64()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_hist(self.s, h.ctypes.data, C.byref(il), C.byref(ih)))
+        return 1, 32767, il.value, ih.value, h
+
     def close(self):
         if getattr(self, "s", None):
             self.L.cp_kmer_sorted_destroy(self.s)

@@ -1171,5 +1171,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // sorted snapshots as input: loaded from a .ktab payload, key lookup and relative profiles (tab2prof): kmer_lookup.hip
 #include "kmer_lookup.hip"
 
+// set algebra on sorted snapshots and the histogram of one (tabop): kmer_setops.hip
+#include "kmer_setops.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

@@ -8,8 +8,8 @@
 // plus ".rel".  K comes from the table's stub.  The table may be FastK's own, a Logex product, `kprof -t` or a class
 // table of class2ktab; the source is found as kprof finds it.
 // The table goes up in pieces of TAB_RANGE entries through one device buffer into cp_kmer_sorted_load_records and is
-// checked there (cp_kmer_sorted_load_end: strictly ascending keys); the reads then go through in batches of -b bases,
-// one cp_kmer_sorted_profiles each ("Sorted k-mers as input" in include/classpro_amd.h): a cell is min(count, 32767) of
+// checked there (cp_kmer_sorted_load_end: strictly ascending keys; ktab_upload.h); the reads then go through in
+// batches of -b bases, one cp_kmer_sorted_profiles each ("Sorted k-mers as input" in include/classpro_amd.h): a cell is min(count, 32767) of
 // the canonical k-mer in the table, 0 when it is absent or holds a byte other than upper-case A C G T.  The -T host
 // threads encode the cells with cp_encode_profile.
 //   -C  also writes <out_root>.class with the labels of prof2class's rule (0 -> E, 1 -> H, 2 -> D, >= 3 -> R after K-1
@@ -32,8 +32,7 @@
 #include "gpu_tool.h"
 #include "read_source.h"
 #include "prof_writer.h"
-#include "ktab_reader.h"
-#include "ktab_writer.h"
+#include "ktab_upload.h"
 #include "thread_pool.h"
 
 static const char *USAGE = "[-v] [-C] [-T<int(4)>] [-b<int(67108864)>] [-N<out_root>]\n"
@@ -105,20 +104,10 @@ int main(int argc, char **argv)
 
   // ---- the table, up in pieces and checked ----
   HCHK(hipSetDevice(0));
-  cp_kmer_sorted *T = nullptr;
-  int rc = cp_kmer_sorted_load_begin(K,tab.index.data(),&T);
-  if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_load_begin");
+  int rc;
+  cp_kmer_sorted *T;
   { DevBuf<uint8_t> d_rec;
-    std::vector<uint8_t> h_rec((size_t)(std::min(TAB_RANGE,std::max<int64_t>(tab.entries,1))*tab.pbyte));
-    int64_t m;
-    while ((m = tab.read(h_rec.data(),TAB_RANGE)) > 0)
-      { d_rec.need((size_t)(m*tab.pbyte));
-        HCHK(hipMemcpy(d_rec.p,h_rec.data(),(size_t)(m*tab.pbyte),hipMemcpyHostToDevice));
-        rc = cp_kmer_sorted_load_records(T,m,d_rec.p,nullptr);       // the next copy waits for it: one stream
-        if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_load_records");
-      }
-    rc = cp_kmer_sorted_load_end(T,nullptr);
-    if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_load_end");
+    T = upload_ktab(tab,d_rec);
     d_rec.release();
   }
 

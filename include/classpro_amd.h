@@ -565,6 +565,46 @@ int     cp_kmer_sorted_profiles(const cp_kmer_sorted *s, int canonical, const ch
                                 int64_t *d_tally, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Set algebra on sorted k-mers (tabop): two snapshots combined into a third by a streaming merge on the device -- what
+ * FASTK's Logex does with two k-mer tables -- and the FASTK histogram of a snapshot.  Everything is in integers and
+ * independent of tile size and scheduling.
+ *
+ *   Presence   a key is IN A when A holds it and a_min <= cntA <= a_max, cntA being the snapshot's own d_cnt (the exact
+ *              64-bit count of a snapshot sorted here, at most 32767 for a loaded one); IN B likewise.  `range` is a
+ *              HOST array a_min a_max b_min b_max; NULL means [1, INT64_MAX] for both.  An entry outside its range is
+ *              treated exactly as if it were absent.
+ *   Kept       CP_SET_AND a key in A and in B; CP_SET_OR in either; CP_SET_SUB in A and not in B; CP_SET_XOR in exactly
+ *              one.
+ *   Count      of a kept key: CP_CNT_LEFT is cntA when in A, otherwise cntB; CP_CNT_SUM the sum over the sides it is in;
+ *              CP_CNT_MIN and CP_CNT_MAX over the sides it is in.  Under SUB and XOR one side is in, so all four give
+ *              that side's count.  Sums are exact in 64 bits; a record clamps at CP_MAX_KMER_CNT, as everywhere.
+ *   Result     an ordinary cp_kmer_sorted, born ready, keys ascending, with memory of its own (it survives destroying a
+ *              and b) and its bucket starts rebuilt: cp_kmer_sorted_size, _bytes, _arrays, _ktab, _find, _profiles and
+ *              _destroy work on it unchanged.  An empty result is size 0 with null arrays and is no error.
+ *   Tally      a HOST array: keys in A only, in B only, in both (each after the ranges), and the result's size.  With
+ *              out == NULL only the tally is computed and nothing of result size is allocated.
+ *   Operands   both ready and of the same K; a == b is legal; K < 5 is legal.  Both are only read: their _ktab gives
+ *              the same bytes before and after.
+ *   Errors     CP_EINVAL for a NULL a or b, for out and tally both NULL, an unready operand, differing K, a set_op or
+ *              cnt_op outside the enums, a range with min < 1 or max < min.  An allocation that fails is CP_ENOMEM with
+ *              the byte count in the message, nothing leaked.  Synchronises `stream`: the result's size must be known
+ *              to allocate it.
+ *   Memory     on top of the result (24 bytes per entry and the bucket starts) 24 bytes per tile of cp_ktab_tile()
+ *              entries of the two operands together, never 24 bytes per operand entry.
+ *   Histogram  cp_kmer_sorted_hist, the contract of cp_kmer_counts_hist over a snapshot's d_cnt: hist[c-1] = entries with
+ *              count c for c < 32767, hist[32766] = those with count >= 32767, ilowcnt = hist[0], ihighcnt = the sum of
+ *              the counts >= 32767.  CP_EINVAL on an unready snapshot; synchronises.  For cp_kmer_counts_sort(t, 1) it
+ *              equals cp_kmer_counts_hist(t) cell for cell.
+ */
+enum { CP_SET_AND = 0, CP_SET_OR = 1, CP_SET_SUB = 2, CP_SET_XOR = 3 };
+enum { CP_CNT_LEFT = 0, CP_CNT_SUM = 1, CP_CNT_MIN = 2, CP_CNT_MAX = 3 };
+int     cp_kmer_sorted_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b, int set_op, int cnt_op,
+                               const int64_t *range /* host [4]: a_min a_max b_min b_max, or NULL */,
+                               int64_t *tally /* host [4], or NULL */, void *stream,
+                               cp_kmer_sorted **out /* or NULL: tally only */);
+int     cp_kmer_sorted_hist(const cp_kmer_sorted *s, int64_t *hist /* host [32767] */, int64_t *ilowcnt, int64_t *ihighcnt);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
