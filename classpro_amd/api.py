@@ -755,13 +755,7 @@ class SortedKmers:
             raise ValueError("SortedKmers is closed")
         if other.K != self.K or other.device != self.device:
             raise ValueError("the operands must hold k-mers of the same length on the same device")
-        rng = None
-        if a_range is not None or b_range is not None:
-            ends = []
-            for r in (a_range, b_range):
-                lo, hi = (None, None) if r is None else r
-                ends += [1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi)]
-            rng = (C.c_int64 * 4)(*ends)
+        rng = self._range4(a_range, b_range)
         tally = (C.c_int64 * 4)()
         h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -781,6 +775,41 @@ class SortedKmers:
         out._adopt(h)
         out.tally = tally
         return out
+
+    @staticmethod
+    def _range4(a_range, b_range):
+        if a_range is None and b_range is None:
+            return None
+        ends = []
+        for r in (a_range, b_range):
+            lo, hi = (None, None) if r is None else r
+            ends += [1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi)]
+        return (C.c_int64 * 4)(*ends)
+
+    def read_hits(self, other, batch, canonical=True, a_range=None, b_range=None):
+        """cp_kmer_sorted_read_hits ("Read hits in two sorted k-mer sets" in include/classpro_amd.h): this snapshot (A)
+        and `other` (B) of the same K looked up together for every k-mer of a `Batch` or of a tuple of device tensors (seq
+        uint8, seq_off int64 [n+1]).  Returns an int64 device tensor [n, 5]: per read the positions whose key is only in
+        A, only in B, in both, the positions with a byte other than upper-case A C G T, and the number of times the A/B
+        markers switch sides along the read.  Ranges are those of `combine`; `other` may be `self`."""
+        if not isinstance(other, SortedKmers):
+            raise ValueError("the other operand must be a SortedKmers")
+        if self.s is None or other.s is None:
+            raise ValueError("SortedKmers is closed")
+        if other.K != self.K or other.device != self.device:
+            raise ValueError("the operands must hold k-mers of the same length on the same device")
+        if isinstance(batch, Batch):
+            seq, seq_off, n, total = batch.seq, batch.seq_off, batch.nreads, batch.total_bases
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+        hits = torch.empty((max(n, 0), 5), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_read_hits(self.s, other.s, 1 if canonical else 0, self._range4(a_range, b_range),
+                                                  seq.data_ptr(), seq_off.data_ptr(), n, total,
+                                                  hits.data_ptr() if n > 0 else None, _stream_of(self.device)))
+        return hits
 
     def compare(self, other, a_range=None, b_range=None):
         """(only_a, only_b, both): the tally of `combine` with nothing built (cp_kmer_sorted_combine with out == NULL)."""
@@ -807,6 +836,19 @@ class SortedKmers:
             self.close()
         except Exception:
             pass
+
+
+def bin_calls(hits, only_a, only_b, min_markers=1, normalise=True):
+    """cp_bin_call for every row of `hits` (the tensor of `SortedKmers.read_hits`, or any int64 [n, 5] array): a `bytes` of
+    'A', 'B' or 'U' per read.  `only_a` and `only_b` are the sizes of the two marker sets, `A.compare(B)[:2]` with the
+    ranges of the hits; they weigh the counts when `normalise` is set.  A read with nA + nB < min_markers is 'U'."""
+    h = hits.cpu().numpy() if isinstance(hits, torch.Tensor) else hits
+    h = np.ascontiguousarray(h, np.int64).reshape(-1, 5)
+    L = lib()
+    out = bytearray(len(h))
+    for i in range(len(h)):
+        out[i] = check(L.cp_bin_call(h[i].ctypes.data, int(only_a), int(only_b), int(min_markers), 1 if normalise else 0))
+    return bytes(out)
 
 
 def ktab_tile():

@@ -1171,6 +1171,9 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // sorted snapshots as input: loaded from a .ktab payload, key lookup and relative profiles (tab2prof): kmer_lookup.hip
 #include "kmer_lookup.hip"
 
+// read hits in two sorted snapshots and the bin call of a read (tabbin): kmer_hits.hip
+#include "kmer_hits.hip"
+
 // set algebra on sorted snapshots and the histogram of one (tabop): kmer_setops.hip
 #include "kmer_setops.hip"
 

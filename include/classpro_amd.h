@@ -605,6 +605,50 @@ int     cp_kmer_sorted_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b,
 int     cp_kmer_sorted_hist(const cp_kmer_sorted *s, int64_t *hist /* host [32767] */, int64_t *ilowcnt, int64_t *ihighcnt);
 
 /* ------------------------------------------------------------------------------------------
+ * Read hits in two sorted k-mer sets (tabbin): per read of a batch in the flat layout above, how many of its k-mer
+ * positions carry a key that only A holds, that only B holds, that both hold, and how often the A and B markers switch
+ * sides along the read -- what trio binning asks of two parental marker sets, and what a switch error or a chimeric read
+ * looks like.  One pass over the bases; every key is rolled once and looked up in both snapshots.  Everything is in
+ * integers.
+ *
+ *   Presence   exactly as in cp_kmer_sorted_combine: a key is IN A when A holds it and a_min <= cntA <= a_max with the
+ *              snapshot's own d_cnt; IN B likewise.  `range` is a HOST array a_min a_max b_min b_max; NULL means
+ *              [1, INT64_MAX] for both.
+ *   Marker     of a k-mer position.  The key is chosen as in cp_kmer_sorted_profiles: min(forward, reverse complement)
+ *              with `canonical` non-zero, the forward k-mer with 0.  The marker is A for a key in A and not in B, B for a
+ *              key in B and not in A, BOTH for a key in both, and none otherwise.  A k-mer that holds a byte other than
+ *              upper-case A C G T is OTHER.  The snapshots need not be disjoint: two raw parental tables give the A and B
+ *              markers that their two differences (CP_SET_SUB either way) would give.
+ *   Row        d_hits[r*CP_HIT_WIDTH + ...] of read r: CP_HIT_A, CP_HIT_B, CP_HIT_BOTH and CP_HIT_OTHER are the numbers of
+ *              its positions with that marker.  CP_HIT_SWITCHES: take the positions marked A or B in read order, ignoring
+ *              every other position; it is the number of adjacent pairs of that subsequence whose markers differ.  Reads
+ *              shorter than K and empty reads give a row of zeros.  Every row is written, never added to.
+ *   Fixed      a row is a function of the read and the two snapshots alone: not of what else is in the batch, of the order
+ *              of the reads, or of the block and chunk sizes of the kernels.
+ *   Operands   both ready and of the same K; a == b is legal (every hit is BOTH), so is a snapshot of size 0.  Both are
+ *              only read.  Lookups are those of "Sorted k-mers as input": clamped ranges, at most 64 probes.
+ *   Errors     all before any launch: CP_EINVAL for a NULL a or b, an unready snapshot, differing K, a range with
+ *              min < 1 or max < min, a negative nreads or total_bases, a null device pointer when there is work
+ *              (nreads == 0 is no work and no error).  Scratch, 32 bytes per 16384 bases of the batch, is allocated and
+ *              freed in stream order per call; when that fails it is CP_ENOMEM with the byte count in the message.
+ * Asynchronous on `stream`.
+ *
+ * cp_bin_call is the one rule by which a row becomes a call; host only, no device involved.  It returns 'U' when
+ * nA + nB < min_markers; otherwise 'A' when nA * wB > nB * wA, 'B' when nB * wA > nA * wB, and 'U' for a tie, the products
+ * taken in 128 bits.  wA = only_a and wB = only_b when `normalise` is non-zero and both are positive, otherwise both are
+ * 1: only_a and only_b are the numbers of distinct keys only in A and only in B (tally[0] and tally[1] of
+ * cp_kmer_sorted_combine with out == NULL and the same ranges), and dividing a read's hits by the sizes of the two marker
+ * sets is how trio binning scores it.  CP_EINVAL for a NULL hit.
+ */
+enum { CP_HIT_A = 0, CP_HIT_B = 1, CP_HIT_BOTH = 2, CP_HIT_OTHER = 3, CP_HIT_SWITCHES = 4, CP_HIT_WIDTH = 5 };
+int     cp_kmer_sorted_read_hits(const cp_kmer_sorted *a, const cp_kmer_sorted *b, int canonical,
+                                 const int64_t *range /* host [4]: a_min a_max b_min b_max, or NULL */,
+                                 const char *d_seq, const int64_t *d_seq_off, int nreads, int64_t total_bases,
+                                 int64_t *d_hits /* device [nreads][CP_HIT_WIDTH], overwritten */, void *stream);
+int     cp_bin_call(const int64_t *hit /* [CP_HIT_WIDTH] */, int64_t only_a, int64_t only_b, int64_t min_markers,
+                    int normalise);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
