@@ -628,7 +628,7 @@ static int stage_classify_rel(cp_workspace *ws, run_ctx &c)
   // (the fw / bw assignments are only read back through the stage API: the whole-path call leaves the array as it is --
   //  a 37-MB fill that sat 0.7 ms in the serial path of every 1-Gbase sub-batch)
   if (c.last_stage < CP_STAGE_LABELS) HIPCHK(hipMemsetAsync(ws->b.asgn.p,0xff,(size_t)totalI*2,c.st));
-  // size classes (kernels.hip: REL_SMALL_*): M <= 128 four reads per wave, up to 1024 one read per wave, larger (or a
+  // size classes (kernels.hip: REL_SMALL_*): M <= 112 eight reads per wave, up to 1024 one read per wave, larger (or a
   // read beyond 65535 k-mers): the sequential kernel
   CHK(launch_order_by_work(ws,as<int32_t>(ws->b.nrel),nreads,0,as<int32_t>(ws->b.perm),c.st,c.d_prof_off));
   // (the classes touch disjoint reads; the rare classes are a handful of latency-bound waves -- on most batches none at

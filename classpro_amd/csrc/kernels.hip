@@ -16,7 +16,7 @@
 //   k_wall_tasks        one wave per read: the read-only part of the candidate walk, wall.c:590-707 (lists + task results to HBM)
 //   k_find_wall         one wave per read: the walk's replay (dependency rounds, flags in LDS) and everything after it, wall.c:639-958
 //   k_find_rel          one wave per read, one lane per interval: wall.c:960-1051
-//   k_classify_rel_grp   4 reads per wave (1 for M > 128), 8 lanes per direction: class_rel.c:871-963
+//   k_classify_rel_grp   8 reads per wave (1 for M > 112), 4 lanes per direction: class_rel.c:871-963
 //   k_classify_unrel_grp 2 reads per wave, speculative update slots committed in order: class_unrel.c:248-300
 //   k_classify_rel / k_classify_unrel   sequential forms for reads with > 1024 intervals or > 65535 k-mers
 //   k_skellam_table     the table of logp_trans values (cp_types.h), filled once per cp_params
@@ -40,7 +40,7 @@ __device__ unsigned long long g_bounds[4];               // cp_bounds.h
 #define REL_MAXM 1024           // reads with more reliable intervals use the sequential kernel
 #define UNREL_MAXN 1024         // reads with more intervals use the sequential kernel
 #ifndef REL_SMALL_MAXM
-#define REL_SMALL_MAXM 112      // the main size class of k_classify_rel_grp (four reads per wave): M <= this
+#define REL_SMALL_MAXM 112      // the main size class of k_classify_rel_grp (eight reads per wave): M <= this
 #endif
 #ifndef UNREL_SMALL_MAXN
 #define UNREL_SMALL_MAXN 256    // the main size class of k_classify_unrel_grp (two reads per wave): N <= this
@@ -2186,18 +2186,21 @@ k_classify_unrel(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *__re
 }
 
 // ---------------------------------------------------------------------------------------------
-//  k_classify_rel_grp<MAXM,G>: class_rel.c:871-963, lane-parallel, G reads per wave (64/G >= 32 lanes
-//  per read) for reads with MINM < M <= MAXM.
+//  k_classify_rel_grp<MINM,MAXM,G,WPB>: class_rel.c:871-963, lane-parallel, G reads per wave (64/G lanes per
+//  read) for reads with MINM < M <= MAXM.
 //
-//  Per read, the forward pass runs on lanes 0-15 of its lane group and the backward pass on lanes
-//  16-31 at the same time; inside a pass lane (s,t) evaluates the transition s@pred -> t@i.  The 8
-//  H/D transitions of every read and direction meet at ONE convergent Bessel call (class_rel.c:213-270
-//  are all `logp_trans` with different arguments), so a DP step of the whole wave costs one
-//  recurrence.  Interval fields (16-bit), DP cells, back-pointers and both assignments live in LDS;
-//  HBM is touched for pe (once per step) and for the results.
+//  Per read, the forward pass runs on the first LD lanes of its lane group and the backward pass on the next LD
+//  at the same time.  Main class (G = 8, LD = 4): the four lanes of a direction are an aligned quad; in the
+//  transition phase lane s evaluates the four transitions s@pred -> E, R, H, D @i in straight code, its seven
+//  table loads in flight together, and the sum of the quad's sixteen terms is taken from the lanes' registers
+//  (DPP); in the state phase lane t owns target state t.  No lane of the wave idles in either phase.  Rare
+//  class (G = 1, LD = 16): lane (s,t) evaluates the one transition s@pred -> t@i, the state phase runs on four
+//  lanes.  Every H/D transition is one `logp_trans` (class_rel.c:213-270), a look-up in the table of its
+//  exponentials (the recurrence only outside the table).  Interval fields (16-bit), DP cells, back-pointers and
+//  both assignments live in LDS; HBM is touched for pe (once per step), the tables and the results.
 // ---------------------------------------------------------------------------------------------
-// LDS record of a wave (G reads).  Sized for waves: with MAXM = 112, G = 4 and the compact cells it is 9.2 KB, and four
-// four-wave blocks (with their 4 KB of libm tables each) fit a CU:
+// LDS record of a wave (G reads).  Sized for waves: with MAXM = 112, G = 8 and the compact cells it is 18 304 bytes, and
+// four two-wave blocks (with their 4 KB of libm tables each: 40 704 bytes) fit a CU's 160 KB:
 //   * `eff` (index of the interval whose data stands in for path index k) and the "absolutely repeat" flag rpos share
 //     one element: the index in the low bits, the flag in the top bit (one byte while MAXM <= 128);
 //   * the traceback overwrites a back-pointer byte with the assignment of the same interval once it has read it, so
@@ -2211,13 +2214,12 @@ template <int MAXM, int G>
 struct rel_grp_lds
   { typedef typename std::conditional<(MAXM <= 128),uint8_t,uint16_t>::type eff_t;
     static constexpr int RPOS = (MAXM <= 128) ? 0x80 : 0x8000;
-    // Bank layout (64 banks of 4 B; a 32-lane half holds 4 (read, direction) groups): rows and records are padded so
+    // Bank layout (64 banks of 4 B; a 32-lane half holds 8 (read, direction) quads with G = 8): rows and records are padded so
     // that the groups' copies of one field fall on different banks -- unpadded, the 64-byte cells of the 16 (group,
     // state) pairs of a half shared 2-4 banks and 58 % of the kernel's LDS cycles were conflict cycles
     // (profiles/r03_sq_counters.txt: SQ_LDS_BANK_CONFLICT 3.3e8 of SQ_LDS_IDX_ACTIVE 5.7e8 per sub-batch).
     // a DP cell as the wave keeps it: the E entries of pos / cnt are never read, counts are 16 bits, the four anchor
-    // indices are interval numbers (< MAXM): 40 bytes instead of cp_cell's 64 -- with the size class at 96 intervals the
-    // wave's record is 8.9 KB and four four-wave blocks (with their libm tables) fit a CU: 4 waves per SIMD
+    // indices are interval numbers (< MAXM): 40 bytes instead of cp_cell's 64
     typedef typename std::conditional<(MAXM <= 128),int8_t,int16_t>::type idx_t;
     struct alignas(8) cell_t
       { double dp, dhr; int32_t pos_[3]; uint16_t cnt_[3]; idx_t last_[4];
@@ -2275,24 +2277,42 @@ __device__ __forceinline__ void grp_sync()
   else { __builtin_amdgcn_fence(__ATOMIC_RELEASE,"wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE,"wavefront"); }
 }
 
+// lanes per direction of a read's 64/G lanes (rel_grp_pass)
+#define REL_LD(G) ((G) <= 2 ? 16 : 4)
+// x of lane S of the caller's aligned quad (a DPP move per half: no LDS, no wait)
+template <int S>
+__device__ __forceinline__ double quad_bcast(double x)
+{ const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x),S*0x55,0xf,0xf,true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x),S*0x55,0xf,0xf,true);
+  return __hiloint2double(hi,lo);
+}
+template <int S>
+__device__ __forceinline__ double quad_sum4(double acc, const double (&v)[4])         // acc + v[0..3] of lane S, in index order
+{ for (int x = 0; x < 4; x++) acc += quad_bcast<S>(v[x]);
+  return acc;
+}
+
 // pe of reliable interval i: a field of the 48-byte record copies (stage API, rare classes) or of the compact records
 #define REL_PE(i) (*reinterpret_cast<const double *>(pe0+(size_t)(i)*pe_stride))
 template <int MAXM, int G, int WPB>
 __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, const rel_libm_lds &T, const char *pe0, int pe_stride, int M, int plen,
                              bool active, const int *COV)
 { CP_LDS_PTR(const uint64_t) xt = (CP_LDS_PTR(const uint64_t))T.exp_tab;
-  CP_LDS_PTR(const double)   lt = (CP_LDS_PTR(const double))T.log_tab; // Lanes of a read: LD per direction (forward first).  With LD = 16 (G <= 2) lane (s,t) owns transition
-  // s -> t; with LD = 8 (G = 4) lane (s,h) owns two, s -> H|D (a Skellam term, the expensive kind) and
-  // s -> E|R (table look-ups), so that every lane of the wave has a Bessel evaluation to do.
-  constexpr int L = WAVE/G, LD = (L >= 32) ? 16 : 8;
+  CP_LDS_PTR(const double)   lt = (CP_LDS_PTR(const double))T.log_tab;
+  // Lanes of a read: LD per direction (forward first).  With LD = 16 (G <= 2) lane (s,t) owns transition s -> t.  With
+  // LD = 4 (G = 8) lane s owns the four transitions of source state s -- straight code, E, R, H, D -- and is the lane of
+  // target state s in the state phase: no lane of the wave idles in either phase, and everything that costs the same per
+  // wave-instruction whatever the lanes do (the state phase, the syncs, psum, the loop) serves eight reads.
+  static_assert(G <= 2 || G == 8,"lane layouts: 16 lanes per direction (G <= 2) or 4 (G = 8)");
+  constexpr int L = WAVE/G, LD = REL_LD(G);
   const int lane = lane_id();
   const int g = lane/L, ql = lane%L;
   const int d = (ql / LD) & 1, F = (d == 0);
   const int ld = ql % LD;
-  const int s = (LD == 16) ? (ld >> 2) : (ld >> 1);
+  const int s = (LD == 16) ? (ld >> 2) : ld;
   const int t1 = (LD == 16) ? (ld & 3) : -1;               // the single transition of a 16-lane direction
-  const int t_sk  = (LD == 16) ? ((t1 == CP_HAPLO || t1 == CP_DIPLO) ? t1 : -1) : ((ld & 1) ? CP_DIPLO : CP_HAPLO);
-  const int t_tab = (LD == 16) ? ((t1 == CP_ERROR || t1 == CP_REPEAT) ? t1 : -1) : ((ld & 1) ? CP_REPEAT : CP_ERROR);
+  const int t_sk  = (t1 == CP_HAPLO || t1 == CP_DIPLO) ? t1 : -1;
+  const int t_tab = (t1 == CP_ERROR || t1 == CP_REPEAT) ? t1 : -1;
   const bool in_grp = active && ql < 2*LD && M > 0;
   rel_grp_view<MAXM,G> view; view.S = &S; view.g = g; view.d = d;
   rel_grp_rv<MAXM,G> rv; rv.S = &S; rv.g = g;
@@ -2322,15 +2342,93 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
     }
   grp_sync<WPB>();
 
+  // (LD = 4) P's scalars of the step, read once: behind the fences of grp_sync the compiler reloads them step by step
+  const double *const eskel = P->eskel;
+  const int skel_kmax = P->skel_kmax;
+  const long long skel_cdmax = P->skel_cdmax;
+  const double r_lp = P->r_lp, r_l1mp = P->r_l1mp;
+  const double *const etab = eskel ? eskel : P->logfact;  // (a valid address for the lanes that take nothing from the table)
+  const int li_e = COV[CP_ERROR];                          // logp_e's lambda and its logarithm: the same at every step
+  const double D_e = (li_e >= 0 && li_e <= CP_MAX_KMER_CNT) ? P->logint[li_e] : cp_log((double)li_e);
   int cur = 0;
   double pe_next = 0.;                                     // pe of the next interval (E lanes), one step ahead
-  if (in_grp && t_tab == CP_ERROR && M > 1)
+  if (in_grp && (LD == 4 || t_tab == CP_ERROR) && M > 1)
     pe_next = REL_PE(F ? 1 : M-2);
   for (int k = 1; k < maxM; k++)                           // _update, class_rel.c:279-513
     { const bool on = in_grp && k < M;
       const int i_pred = i;
       if (on) i = F ? k : M-1-k;
       cp_riv I; I.b = I.e = I.ccb = I.cce = 0; I.pe = 0.;
+      if constexpr (LD == 4)
+      { // ---- :300-336 with a lane per source state: its four transitions in straight code.  The lane first works out the
+        //      table cells of the E and R terms and the arguments of the two Skellam terms, then all its loads go out
+        //      together; no branch depends on the target state.
+        double v[4] = { 0., 0., 0., 0. };                  // exp(logp) of s -> E, R, H, D (0 = exp(-inf) while not live)
+        bool live = false, r_tab = false, r_cap = false;
+        int e0 = 0, e1 = 0, rk = 0, rn = 0, r2 = 0;
+        int hb = 0, hcb = 0, hce = 0, db = 0, dcb = 0, te = 0, tce = 0;
+        const double pe_now = pe_next;                     // fetched one step ahead
+        if (on)
+          { I = rv(i);
+            if (k+1 < M)
+              pe_next = REL_PE(F ? k+1 : M-2-k);           // (one address per direction: its four lanes load it)
+            const auto &pr = S.cell[g][d][cur][s];
+            live = pr.dp != -INFINITY;
+            if (live)
+              { const int beg_pos = cp_beg_pos(I,F), beg_cnt = cp_beg_cnt(I,F), prc = pr.cnt_[CP_REPEAT-1];
+                I.pe = pe_now;                             // logp_e, class_rel.c:158-170
+                e0 = cp_check_cnt(I.ccb); e1 = cp_check_cnt(I.cce);
+                if (beg_cnt < prc)                         // logp_r, class_rel.c:172-211
+                  { r_tab = true;
+                    rk = cp_check_cnt(beg_cnt); rn = cp_check_cnt(prc); r2 = rn-rk;
+                  }
+                const int max_cc = I.ccb > I.cce ? I.ccb : I.cce;
+                r_cap = max_cc >= COV[CP_REPEAT] || max_cc >= prc;
+                te = beg_pos; tce = beg_cnt;               // logp_h / logp_d, class_rel.c:213-270
+                const bool h_own = pr.dhr == -INFINITY;    // H from the last H anchor; otherwise from the last D anchor, scaled
+                hb  = cp_pred(h_own ? pr.pos_[CP_HAPLO-1] : pr.pos_[CP_DIPLO-1],F);
+                hcb = h_own ? pr.cnt_[CP_HAPLO-1] : pr.cnt_[CP_DIPLO-1];
+                hce = h_own ? beg_cnt : (int)(pr.dhr*beg_cnt);
+                db  = cp_pred(pr.pos_[CP_DIPLO-1],F); dcb = pr.cnt_[CP_DIPLO-1];
+              }
+          }
+        // the look-up of cp_exp_logp_trans (cp_math.h) for H and D, index by index: what lies outside the table, or a
+        // classifier without the table of exponentials, goes through cp_exp_logp_trans itself below
+        const int hd = te-hb < 0 ? hb-te : te-hb, dd = te-db < 0 ? db-te : te-db;
+        const int hk = hce-hcb < 0 ? hcb-hce : hce-hcb, dk = tce-dcb < 0 ? dcb-tce : tce-dcb;
+        const long long hcd = (long long)(hcb & 0xffff)*hd, dcd = (long long)(dcb & 0xffff)*dd;
+        const bool h_in = live && eskel && hk <= skel_kmax && hcd <= skel_cdmax;
+        const bool d_in = live && eskel && dk <= skel_kmax && dcd <= skel_cdmax;
+        { const double A = P->logfact[e0], B = P->logfact[e1];                    // all seven loads of the lane together
+          const double RA = P->logfact[rn], RB = P->logfact[rk], RC = P->logfact[r2];
+          const double TH = etab[h_in ? hcd*(skel_kmax+1)+hk : 0], TD = etab[d_in ? dcd*(skel_kmax+1)+dk : 0];
+          if (live)
+            { const double po = (e0 * D_e - li_e - A)+(e1 * D_e - li_e - B)+CP_E_PO_BASE;       // prob.c:33-39 twice
+              const double lp_e = (po > I.pe) ? po : I.pe;
+              double lp_r = r_tab ? (RA - RB - RC + rk * r_lp + (rn-rk) * r_l1mp) : -INFINITY;   // prob.c:67-73
+              if (!(lp_r > CP_R_LOGP) && r_cap) lp_r = CP_R_LOGP;
+              v[CP_HAPLO] = TH; v[CP_DIPLO] = TD;
+              if (!h_in) v[CP_HAPLO] = cp_exp_logp_trans(P,hb,te,hcb,hce,hcb,xt);
+              if (!d_in) v[CP_DIPLO] = cp_exp_logp_trans(P,db,te,dcb,tce,dcb,xt);
+              v[CP_ERROR]  = cp_exp_t(lp_e,xt);
+              v[CP_REPEAT] = cp_exp_t(lp_r,xt);
+            }
+        }
+        // :320-336.  The sixteen terms sit in the four lanes of the quad, four each: the sum over tr[0..15] in index order
+        // takes them from the lanes' registers (a quad whose step is off holds zeros and its result is dropped)
+        double psum = quad_sum4<3>(quad_sum4<2>(quad_sum4<1>(quad_sum4<0>(0.,v),v),v),v);
+        if (on)
+          { if (psum == 0.)
+              { v[CP_ERROR] = 1.;
+                psum = 4.;
+              }
+            for (int x = 0; x < 4; x++) v[x] = cp_log_t(v[x]/psum,lt);
+            for (int x = 0; x < 4; x++) S.tr[g][d][s*4+x] = v[x];          // (tr's readers of the step before are behind its last sync)
+          }
+        grp_sync<WPB>();
+      }
+      else
+      {
       double v_sk = 0., v_tab = 0.;
       // ---- :300-319: the 16 transitions of a (read, direction).  Every lane first works out which table
       //      cells (log-factorials, log lambda) and which Skellam arguments its transition(s) need; the
@@ -2417,6 +2515,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
           if (t_tab >= 0) S.tr[g][d][s*4+t_tab] = nv_tab;
         }
       grp_sync<WPB>();
+      }
       // :348-499: one lane per state.  The four state lanes of a (read, direction) are an aligned quad; what the reference
       // computes once per step and all four need -- "only R reachable" (four row maxima, :348-380) and the H->H / D->D
       // equalisation (two column maxima, :382-386) -- is split over them, a row and a column each, and joined through a
@@ -2519,8 +2618,16 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
 // with a Bessel term): 5.00 ms at MAXM 256, 4.77 at 192, 5.39 at 128.
 // With the table of logp_trans values (cp_types.h) the Bessel term is a load and the balance moved again: whole step
 // 70.7 ms at MAXM 192, 68.7 at 128 or 96 (less LDS per wave: 3 waves per SIMD instead of 2); G = 2 74.8, G = 8 89.7.
+// (That G = 8 figure is from round 2: 64-byte cells, the exp/log tables and exp(logp_trans) not yet tabulated, a larger
+// record per read, and no fewer than 8 lanes per direction, so half the lanes of such a wave had no transition.)
+// Eight reads per wave with four lanes per direction (profiles/rel_grp_lanes_ab.txt): the state phase, the syncs, the sum
+// of the sixteen terms and the loop serve twice the reads per wave-instruction -- 1.66 G vector + 0.79 G scalar
+// instructions per 4-Gbase launch become 1.04 G + 0.44 G.  A wave's record doubles (18.3 KB) and the CU holds 8 waves
+// instead of 16: with the straight port of the step the kernel was latency-bound and slower (3.77 ms alone against 3.53,
+// the step 25.2 ms against 24.4); with the lane's table loads in flight together, P's scalars read once per pass and the
+// sum taken through DPP instead of an LDS round trip it runs in 3.25 ms alone, and the step takes 23.6 ms.
 #ifndef REL_SMALL_G
-#define REL_SMALL_G 4
+#define REL_SMALL_G 8
 #endif
 // (REL_SMALL_MAXM: defined at the top of the file, k_find_wall needs it)
 // (unrel, later, with K = 64/G/8 speculative update slots per read: G = 4 4.28 ms per step, G = 2 4.07, G = 1 4.04)
@@ -2536,16 +2643,20 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
 #ifndef REL_EXTRA_ATTR
 #define REL_EXTRA_ATTR
 #endif
-// waves per block of the main size class (they share the block's copy of the libm tables, 4 KB, and nothing else)
+// waves per block of the main size class (they share the block's copy of the libm tables, 4 KB, and nothing else).
+// Two: 40.7 KB per block, four blocks to a CU.  Four-wave blocks (77.3 KB, two to a CU) hold the same 8 waves and the
+// kernel alone runs as fast, but a CU that holds two of them has 6 KB of LDS left for the other stream's kernels: the step
+// takes 24.2 ms with four-wave blocks and 23.6 with two-wave ones.  One-wave blocks (7 to a CU): 4.11 ms alone.
 #ifndef REL_SMALL_WPB
-#define REL_SMALL_WPB 4
+#define REL_SMALL_WPB 2
 #endif
 // (round 3: 4 waves per SIMD = 128 VGPRs with 32 of them spilled to scratch, against 167 and none at 3: 192 against 186
 //  Gbases/s.  Round 4: four-wave blocks with the libm tables in LDS; with 64-byte cells and a size class of 128 a block was
 //  52 KB, three to a CU = 3 waves per SIMD (149 VGPRs, nothing spilled): 194.4 Gbases/s; with the 40-byte cell_t and a
-//  size class of 112 a block is 40.7 KB, four to a CU = 4 waves per SIMD at 128 VGPRs, 14 spilled: 198.6-199.7)
+//  size class of 112 a block is 40.7 KB, four to a CU = 4 waves per SIMD at 128 VGPRs, 14 spilled: 198.6-199.7.
+//  With eight reads per wave LDS allows 2 waves per SIMD, which leaves each up to 256 registers: 170, nothing spilled)
 #ifndef REL_WAVES_PER_EU
-#define REL_WAVES_PER_EU 4
+#define REL_WAVES_PER_EU 2
 #endif
 
 template <int MINM, int MAXM, int G, int WPB, int COMPACT = 0>
@@ -2599,7 +2710,7 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
       }
   grp_sync<WPB>();
 
-  constexpr int LD = (L >= 32) ? 16 : 8;                   // lanes per direction, see rel_grp_pass
+  constexpr int LD = REL_LD(G);                            // lanes per direction, see rel_grp_pass
   const int d = (ql / LD) & 1, F = (d == 0);
   const int leadlane = g*L+d*LD;
   const bool lead = (M > 0) && (ql < 2*LD) && ((ql % LD) == 0);
