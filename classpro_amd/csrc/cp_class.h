@@ -45,6 +45,36 @@ CP_HD int cp_beg_cnt(const cp_riv &I, int F) { return F ? I.ccb : I.cce; }
 CP_HD int cp_end_pos(const cp_riv &I, int F) { return F ? I.e-1 : I.b; }
 CP_HD int cp_end_cnt(const cp_riv &I, int F) { return F ? I.cce : I.ccb; }
 
+// Cell policy.  cp_dh_ratio takes from the anchors i2, i3 of a path only cp_end_pos / cp_end_cnt of the interval that
+// stands in for them.  A cp_cell holds the anchors as indices and the pair is looked up when needed (View: through `eff`).
+// A cp_cell_anc carries the pair of each of its four anchors beside the index, so no look-up is needed: the pair of an
+// anchor is known when the anchor is set -- the interval's own end on a normal step, and on an "only R reachable" step the
+// end of the interval that stands in for the predecessor (one value per pass, carried by the caller).  The pairs are
+// 16 + 16 bits: for reads of at most 65535 k-mers (the caller's business).
+enum { CP_A_H = 0, CP_A_D = 1, CP_A_HBD = 2, CP_A_DBH = 3 };       // lastH, lastD, lastHbD, lastDbH
+struct cp_cell_anc : cp_cell
+  { uint32_t anc[4]; };              // end_pos | end_cnt << 16 of the four anchors (meaningless while the index is CP_NONE)
+CP_HD uint32_t cp_anc_pair(const cp_riv &I, int F) { return (uint32_t)cp_end_pos(I,F) | ((uint32_t)cp_end_cnt(I,F) << 16); }
+CP_HD void cp_anc_reset(cp_cell &) { }
+CP_HD void cp_anc_reset(cp_cell_anc &c) { for (int k = 0; k < 4; k++) c.anc[k] = 0; }
+CP_HD void cp_anc_copy(cp_cell &, const cp_cell &) { }
+CP_HD void cp_anc_copy(cp_cell_anc &c, const cp_cell_anc &p) { for (int k = 0; k < 4; k++) c.anc[k] = p.anc[k]; }
+// state t (H or D) becomes the newest anchor of the cell's path: goes with "lastDbH = lastD; lastH = i" (or its mirror)
+CP_HD void cp_anc_push(cp_cell &, int, uint32_t) { }
+CP_HD void cp_anc_push(cp_cell_anc &c, int t, uint32_t pair)
+{ if (t == CP_HAPLO) { c.anc[CP_A_DBH] = c.anc[CP_A_D]; c.anc[CP_A_H] = pair; }
+  else               { c.anc[CP_A_HBD] = c.anc[CP_A_H]; c.anc[CP_A_D] = pair; }
+}
+// what cp_dh_ratio needs of the anchor in `slot` of pr (path index k)
+template <class View>
+CP_HD cp_riv cp_anc_riv(const cp_cell &, int, int k, const View &view) { return view(k); }
+template <class View>
+CP_HD cp_riv cp_anc_riv(const cp_cell_anc &pr, int slot, int, const View &)
+{ cp_riv r; r.b = (int)(pr.anc[slot] & 0xffff); r.e = r.b+1; r.ccb = r.cce = (int)(pr.anc[slot] >> 16); r.pe = 0.;
+  return r;
+}
+struct cp_no_view { };               // the View of cp_cell_anc cells: never asked
+
 // class_rel.c:158-170
 CP_HD double cp_logp_e(const cp_dev_params *P, const cp_riv &I, const int *COV)
 { double logp_po = cp_logp_poisson(P,I.ccb,COV[CP_ERROR])+cp_logp_poisson(P,I.cce,COV[CP_ERROR])+CP_E_PO_BASE;
@@ -116,8 +146,9 @@ CP_HD int cp_argmax_tr(const double *dp, const double *tr, int s, int t, double 
 }
 
 // First cell of a pass for state s (class_rel.c:544-580), before the normalisation of :582-586.
+template <class C>
 CP_HD void cp_rel_init_cell(const cp_dev_params *P, int s, const cp_riv &I, int i, int plen, int F,
-                            const int *COV, cp_cell *c)
+                            const int *COV, C *c)
 { const int POS_INIT = cp_offs(F ? 0 : plen,F);
   const int ep = cp_end_pos(I,F), ec = cp_end_cnt(I,F), bc = cp_beg_cnt(I,F);
   for (int t = 0; t < 4; t++)
@@ -126,6 +157,7 @@ CP_HD void cp_rel_init_cell(const cp_dev_params *P, int s, const cp_riv &I, int 
     }
   c->dhr = -INFINITY;
   c->lastH = c->lastD = c->lastHbD = c->lastDbH = CP_NONE;
+  cp_anc_reset(*c);
   if (s == CP_ERROR)
     c->dp = cp_logp_e(P,I,COV);
   else if (s == CP_REPEAT)
@@ -140,6 +172,7 @@ CP_HD void cp_rel_init_cell(const cp_dev_params *P, int s, const cp_riv &I, int 
       c->pos[CP_DIPLO] = cp_offs(ep,F);
       c->cnt[CP_DIPLO] = (ec+COV[CP_HAPLO]) & 0xffff;
       c->lastH = i;
+      cp_anc_push(*c,CP_HAPLO,cp_anc_pair(I,F));
     }
   else
     { c->dp = cp_logp_poisson(P,bc,COV[CP_DIPLO]);
@@ -148,37 +181,43 @@ CP_HD void cp_rel_init_cell(const cp_dev_params *P, int s, const cp_riv &I, int 
       c->pos[CP_DIPLO] = ep;
       c->cnt[CP_DIPLO] = ec;
       c->lastD = i;
+      cp_anc_push(*c,CP_DIPLO,cp_anc_pair(I,F));
     }
 }
 
 // "Only R reachable" step (class_rel.c:349-380) for state s: the cell is carried over and the path
-// gains one more interval of state s (whose data stands in for the predecessor's).
-CP_HD void cp_rel_only_r_cell(int s, int i, cp_cell *c)
+// gains one more interval of state s (whose data stands in for the predecessor's: `standin` is its cp_anc_pair, for
+// cells that carry the pairs).
+template <class C>
+CP_HD void cp_rel_only_r_cell(int s, int i, C *c, uint32_t standin = 0)
 { if (c->dp == -INFINITY)
     return;
-  if (s == CP_HAPLO)      { c->lastDbH = c->lastD; c->lastH = i; }
-  else if (s == CP_DIPLO) { c->lastHbD = c->lastH; c->lastD = i; }
+  if (s == CP_HAPLO)      { c->lastDbH = c->lastD; c->lastH = i; cp_anc_push(*c,s,standin); }
+  else if (s == CP_DIPLO) { c->lastHbD = c->lastH; c->lastD = i; cp_anc_push(*c,s,standin); }
   c->dhr = -INFINITY;                                    // dh_ratio[i][s] is left at its reset value (:520-522)
 }
 
 // New cell for target state t at interval i given its best predecessor (class_rel.c:390-499).
 // View gives the hot fields of the interval standing in for path index k: view(k) -> cp_riv.
-// `prev` = the four cells of the previous interval (cp_cell, or a padded record derived from it: Cell).
-template <class View, class Cell>
+// `prev` = the four cells of the previous interval (C, or a padded record derived from it: Cell).
+// C = cp_cell: the anchors of cp_dh_ratio are looked up through `view`; C = cp_cell_anc: they come with the cell.
+template <class View, class Cell, class C>
 CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv &I, int F, const int *COV,
-                              int max_s, double max_logp, const Cell *prev, const View &view, cp_cell *out)
-{ cp_cell c;
+                              int max_s, double max_logp, const Cell *prev, const View &view, C *out)
+{ C c;
   c.dp = max_logp;
   c.dhr = -INFINITY;
   if (max_s == CP_N_STATE)
     { for (int k = 0; k < 4; k++) { c.pos[k] = 0; c.cnt[k] = 0; }
       c.lastH = c.lastD = c.lastHbD = c.lastDbH = CP_NONE;
+      cp_anc_reset(c);
       *out = c;
       return;
     }
-  const cp_cell pr = prev[max_s];
+  const C pr = prev[max_s];
   const int end_pos = cp_end_pos(I,F), end_cnt = cp_end_cnt(I,F);
   c.lastH = pr.lastH; c.lastD = pr.lastD; c.lastHbD = pr.lastHbD; c.lastDbH = pr.lastDbH;
+  cp_anc_copy(c,pr);
   for (int k = 0; k < 4; k++) { c.pos[k] = pr.pos[k]; c.cnt[k] = pr.cnt[k]; }
 
   if (t == CP_ERROR)
@@ -205,7 +244,8 @@ CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv
             curr_o = (curr_t/2 > curr_t-COV[CP_HAPLO]) ? curr_t/2 : curr_t-COV[CP_HAPLO];
         }
       else
-        { double r = cp_dh_ratio(t,I,view(i2),view(i3),F);
+        { double r = cp_dh_ratio(t,I,cp_anc_riv(pr,(t == CP_HAPLO) ? CP_A_D : CP_A_H,i2,view),
+                                     cp_anc_riv(pr,(t == CP_HAPLO) ? CP_A_HBD : CP_A_DBH,i3,view),F);
           curr_o = (t == CP_HAPLO) ? (int)(r*curr_t) : (int)((double)curr_t/r);
           c.dhr = r;
         }
@@ -218,6 +258,7 @@ CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv
       c.cnt[CP_REPEAT] = curr_r & 0xffff;
       if (t == CP_HAPLO) { c.lastDbH = pr.lastD; c.lastH = i; }
       else               { c.lastHbD = pr.lastH; c.lastD = i; }
+      cp_anc_push(c,t,cp_anc_pair(I,F));
     }
   if (!((c.cnt[CP_HAPLO] < c.cnt[CP_DIPLO]) && (c.cnt[CP_DIPLO] < c.cnt[CP_REPEAT])))   // :496-498
     c.dp = -INFINITY;
@@ -234,11 +275,13 @@ struct cp_aos_view                   // path index -> hot fields, through the `e
 //   parent[M*4] back-pointers, eff[M] index of the interval whose data stands in for i (the
 //               reference overwrites arg->intvl[i] with its predecessor at "only R" steps, :351)
 //   rpos[M]     "absolutely repeat" flags (:350), asgn[M] out
-CP_HD void cp_rel_direction(const cp_dev_params *P, const cp_intvl *rintvl, int M, int plen, int F,
-                            const int *COV, int8_t *parent, int *eff, uint8_t *rpos, int8_t *asgn)
-{ cp_cell prev[4], cur[4];
+// C: the cell policy (cp_cell with a View through `eff`, or cp_cell_anc, which asks no view)
+template <class C, class View>
+CP_HD void cp_rel_direction_c(const cp_dev_params *P, const cp_intvl *rintvl, int M, int plen, int F,
+                              const int *COV, int8_t *parent, int *eff, uint8_t *rpos, int8_t *asgn, const View &view)
+{ C prev[4], cur[4];
   int i = F ? 0 : M-1;
-  cp_aos_view view; view.rintvl = rintvl; view.eff = eff;
+  uint32_t standin;                                      // cp_anc_pair of rintvl[eff[i]]
 
   { const cp_riv I = cp_riv_of(rintvl[i]);                // init, class_rel.c:544-586
     for (int s = 0; s < 4; s++)
@@ -252,6 +295,7 @@ CP_HD void cp_rel_direction(const cp_dev_params *P, const cp_intvl *rintvl, int 
       prev[s].dp = cp_log(cp_exp(prev[s].dp)/psum);
     rpos[i] = 0;
     eff[i] = i;
+    standin = cp_anc_pair(I,F);
   }
 
   while (true)                                           // class_rel.c:599-605 -> _update (:279-513)
@@ -298,10 +342,11 @@ CP_HD void cp_rel_direction(const cp_dev_params *P, const cp_intvl *rintvl, int 
           eff[i] = eff[i_pred];
           for (int s = 0; s < 4; s++)
             { parent[i*4+s] = (int8_t)s;
-              cp_rel_only_r_cell(s,i,&prev[s]);
+              cp_rel_only_r_cell(s,i,&prev[s],standin);
             }
           continue;
         }
+      standin = cp_anc_pair(I,F);
 
       { double dummy;                                    // :382-386
         int maxs_h = cp_argmax_tr(dp,tr,CP_N_STATE,CP_HAPLO,&dummy);
@@ -335,6 +380,12 @@ CP_HD void cp_rel_direction(const cp_dev_params *P, const cp_intvl *rintvl, int 
     { asgn[k] = rpos[k] ? (int8_t)CP_REPEAT : (int8_t)s;
       s = parent[k*4+s];
     }
+}
+
+CP_HD void cp_rel_direction(const cp_dev_params *P, const cp_intvl *rintvl, int M, int plen, int F,
+                            const int *COV, int8_t *parent, int *eff, uint8_t *rpos, int8_t *asgn)
+{ cp_aos_view view; view.rintvl = rintvl; view.eff = eff;
+  cp_rel_direction_c<cp_cell>(P,rintvl,M,plen,F,COV,parent,eff,rpos,asgn,view);
 }
 
 // Coverage heuristics after a pass (class_rel.c:629-735 / :743-845), split in two so that the

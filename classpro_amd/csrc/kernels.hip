@@ -2196,11 +2196,13 @@ k_classify_unrel(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *__re
 //  (DPP); in the state phase lane t owns target state t.  No lane of the wave idles in either phase.  Rare
 //  class (G = 1, LD = 16): lane (s,t) evaluates the one transition s@pred -> t@i, the state phase runs on four
 //  lanes.  Every H/D transition is one `logp_trans` (class_rel.c:213-270), a look-up in the table of its
-//  exponentials (the recurrence only outside the table).  Interval fields (16-bit), DP cells, back-pointers and
-//  both assignments live in LDS; HBM is touched for pe (once per step), the tables and the results.
+//  exponentials (the recurrence only outside the table).  Rare class: interval fields (16-bit), DP cells, back-pointers and
+//  both assignments live in LDS; HBM is touched for pe (once per step), the tables and the results.  Main class: DP cells,
+//  back-pointers and assignments live in LDS; the interval of a step is its record in global memory, fetched one step ahead
+//  (in the order of the pass), the cells carry what cp_dh_ratio needs of their anchors, and the transition matrix of a step
+//  stays in the registers of the quad: three waves per SIMD (profiles/rel_grp_occupancy_ab.txt).
 // ---------------------------------------------------------------------------------------------
-// LDS record of a wave (G reads).  Sized for waves: with MAXM = 112, G = 8 and the compact cells it is 18 304 bytes, and
-// four two-wave blocks (with their 4 KB of libm tables each: 40 704 bytes) fit a CU's 160 KB:
+// LDS record of a wave (G reads), general form (the rare class, G = 1; the main class has its own below):
 //   * `eff` (index of the interval whose data stands in for path index k) and the "absolutely repeat" flag rpos share
 //     one element: the index in the low bits, the flag in the top bit (one byte while MAXM <= 128);
 //   * the traceback overwrites a back-pointer byte with the assignment of the same interval once it has read it, so
@@ -2221,6 +2223,7 @@ struct rel_grp_lds
     // a DP cell as the wave keeps it: the E entries of pos / cnt are never read, counts are 16 bits, the four anchor
     // indices are interval numbers (< MAXM): 40 bytes instead of cp_cell's 64
     typedef typename std::conditional<(MAXM <= 128),int8_t,int16_t>::type idx_t;
+    typedef cp_cell dp_cell;             // the cell policy of cp_class.h: anchors looked up through `eff` (rel_grp_view)
     struct alignas(8) cell_t
       { double dp, dhr; int32_t pos_[3]; uint16_t cnt_[3]; idx_t last_[4];
         __device__ __forceinline__ operator cp_cell() const
@@ -2244,6 +2247,56 @@ struct rel_grp_lds
     __device__ __forceinline__ int8_t *asgn(int g, int d) { return reinterpret_cast<int8_t *>(parent[g][d]); }
   };
 
+// The record of the main class (eight reads per wave): cells, back-pointers and the "absolutely repeat" flags only, 9 216
+// bytes with MAXM = 112.  The interval rows are not here: the step's interval is streamed from the read's records in
+// global memory one step ahead (rel_rec), and the only random access to the rows -- the anchors of cp_dh_ratio -- is gone
+// because the cells carry the (end_pos, end_cnt) pair of their four anchors (cp_cell_anc: 56 bytes instead of 40).  The
+// transition matrix is not here either: it stays in the registers of the quad that computed it (rel_grp_pass).
+template <int MAXM>
+struct rel_grp_lds<MAXM,8>
+  { static_assert(MAXM <= 128,"one-byte anchor indices");
+    static_assert(GRP_MAX_PLEN <= 0xffff,"cp_cell_anc keeps interval ends as 16-bit values");
+    typedef int8_t idx_t;
+    typedef cp_cell_anc dp_cell;
+    struct alignas(8) cell_t
+      { double dp, dhr; int32_t pos_[3]; uint32_t anc_[4]; uint16_t cnt_[3]; idx_t last_[4];
+        __device__ __forceinline__ operator cp_cell_anc() const
+        { cp_cell_anc c; c.dp = dp; c.dhr = dhr;
+          c.pos[0] = 0; c.cnt[0] = 0;
+          for (int k = 0; k < 3; k++) { c.pos[k+1] = pos_[k]; c.cnt[k+1] = cnt_[k]; }
+          c.lastH = last_[0]; c.lastD = last_[1]; c.lastHbD = last_[2]; c.lastDbH = last_[3];
+          for (int k = 0; k < 4; k++) c.anc[k] = anc_[k];
+          return c;
+        }
+        __device__ __forceinline__ void set(const cp_cell_anc &c)
+        { dp = c.dp; dhr = c.dhr;
+          for (int k = 0; k < 3; k++) { pos_[k] = c.pos[k+1]; cnt_[k] = (uint16_t)c.cnt[k+1]; }
+          last_[0] = (idx_t)c.lastH; last_[1] = (idx_t)c.lastD; last_[2] = (idx_t)c.lastHbD; last_[3] = (idx_t)c.lastDbH;
+          for (int k = 0; k < 4; k++) anc_[k] = c.anc[k];
+        }
+      };
+    static constexpr int RW = (MAXM+31)/32;
+    uint8_t  parent[8][2][MAXM];         // back-pointers of the 4 cells of an interval, 2 bits each; then the assignment
+    uint32_t rpos[8][2][RW];             // "absolutely repeat" flags, a bit per interval
+    cell_t   cell[8][2][2][4];           // [read][direction][buffer][state]
+    __device__ __forceinline__ int8_t *asgn(int g, int d) { return reinterpret_cast<int8_t *>(parent[g][d]); }
+    __device__ __forceinline__ bool is_rpos(int g, int d, int k) const { return (rpos[g][d][k >> 5] >> (k & 31)) & 1; }
+  };
+
+// Reliable interval i of a read from its records in global memory: the 24-byte compact records of a whole-path call, or
+// the 48-byte record copies of the stage API
+template <int COMPACT>
+struct rel_rec
+  { const cp_rrec *rrec; const cp_intvl *rintvl;
+    __device__ __forceinline__ cp_riv operator()(int i) const
+    { cp_riv r;
+      if (COMPACT) { const cp_rrec q = rrec[i]; r.b = q.b; r.e = q.e; r.ccb = q.ccb; r.cce = q.cce; r.pe = q.pe; }
+      else         r = cp_riv_of(rintvl[i]);
+      return r;
+    }
+    __device__ __forceinline__ double pe(int i) const { return COMPACT ? rrec[i].pe : rintvl[i].pe; }
+  };
+
 template <int MAXM, int G>
 struct rel_grp_view                      // path index -> hot fields through `eff`
   { const rel_grp_lds<MAXM,G> *S; int g, d;
@@ -2263,6 +2316,12 @@ struct rel_grp_rv
     }
   };
 
+template <int MAXM, int G>
+__device__ __forceinline__ bool rel_is_rpos(const rel_grp_lds<MAXM,G> &S, int g, int d, int k)
+{ if constexpr (G == 8) return S.is_rpos(g,d,k);
+  else return (S.eff[g][d][k] & rel_grp_lds<MAXM,G>::RPOS) != 0;
+}
+
 // One DP pass (_classify_rel, class_rel.c:515-614) for every (read, direction) whose lanes have
 // active == true.  M differs per read group; the wave iterates to the largest.
 // libm tables of a block in LDS (cp_libm.h): the DP step's chain is exp -> sum -> log, and from global memory each of the
@@ -2277,6 +2336,22 @@ __device__ __forceinline__ void grp_sync()
   else { __builtin_amdgcn_fence(__ATOMIC_RELEASE,"wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE,"wavefront"); }
 }
 
+// -DCP_PROF_WALK (scripts/walk_profile.py): wave time of the main class of k_classify_rel_grp in 100 MHz ticks, lane 0 of every wave.
+//   [0] a step from its start to the return of its loads, [1] from there to the normalised tr values, [2] the state phase,
+//   [3] the syncs (with the stores in front of them), [4] the traceback, [5] cp_rel_post1, [6] cp_rel_post2, [7] the fw / bw
+//   compare, [8] a group of reads as a whole, [9] groups, [10] the init of a pass, [11] the final write.
+// Every stamp waits for the wave's outstanding memory operations first, so the phases do not overlap as they do unstamped.
+#ifdef CP_PROF_WALK
+__device__ unsigned long long g_rel_prof[12];
+#define RP_DECL(n) unsigned long long rp_acc[n] = { 0 }, rp_t = wall_clock64()
+#define RP_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = wall_clock64(); \
+                         rp_acc[k] += t_-rp_t; rp_t = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define RP_FLUSH(on,lo,hi,off) do { if ((on) && lane_id() == 0) for (int k_ = lo; k_ <= hi; k_++) atomicAdd(&g_rel_prof[k_],rp_acc[k_-(off)]); } while (0)
+#else
+#define RP_DECL(n) ((void)0)
+#define RP_STAMP(k) ((void)0)
+#define RP_FLUSH(on,lo,hi,off) ((void)0)
+#endif
 // lanes per direction of a read's 64/G lanes (rel_grp_pass)
 #define REL_LD(G) ((G) <= 2 ? 16 : 4)
 // x of lane S of the caller's aligned quad (a DPP move per half: no LDS, no wait)
@@ -2292,10 +2367,22 @@ __device__ __forceinline__ double quad_sum4(double acc, const double (&v)[4])   
   return acc;
 }
 
+__device__ __forceinline__ double quad_sum1(double x)                                 // x of lanes 0..3 of the quad, summed in that order
+{ double acc = 0.;
+  acc += quad_bcast<0>(x); acc += quad_bcast<1>(x); acc += quad_bcast<2>(x); acc += quad_bcast<3>(x);
+  return acc;
+}
+// lane x's v[t] for the caller's own t (its lane in the quad): column t of the matrix whose row s is lane s's v[0..3]
+template <int X>
+__device__ __forceinline__ double quad_col(const double (&v)[4], int t)
+{ const double a = quad_bcast<X>(v[0]), b = quad_bcast<X>(v[1]), c = quad_bcast<X>(v[2]), e = quad_bcast<X>(v[3]);
+  return t == 0 ? a : t == 1 ? b : t == 2 ? c : e;
+}
+
 // pe of reliable interval i: a field of the 48-byte record copies (stage API, rare classes) or of the compact records
-#define REL_PE(i) (*reinterpret_cast<const double *>(pe0+(size_t)(i)*pe_stride))
-template <int MAXM, int G, int WPB>
-__device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, const rel_libm_lds &T, const char *pe0, int pe_stride, int M, int plen,
+#define REL_PE(i) rec.pe(i)
+template <int MAXM, int G, int WPB, class Rec>
+__device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, const rel_libm_lds &T, const Rec &rec, int M, int plen,
                              bool active, const int *COV)
 { CP_LDS_PTR(const uint64_t) xt = (CP_LDS_PTR(const uint64_t))T.exp_tab;
   CP_LDS_PTR(const double)   lt = (CP_LDS_PTR(const double))T.log_tab;
@@ -2304,6 +2391,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   // target state s in the state phase: no lane of the wave idles in either phase, and everything that costs the same per
   // wave-instruction whatever the lanes do (the state phase, the syncs, psum, the loop) serves eight reads.
   static_assert(G <= 2 || G == 8,"lane layouts: 16 lanes per direction (G <= 2) or 4 (G = 8)");
+  RP_DECL(11);
   constexpr int L = WAVE/G, LD = REL_LD(G);
   const int lane = lane_id();
   const int g = lane/L, ql = lane%L;
@@ -2314,13 +2402,40 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   const int t_sk  = (t1 == CP_HAPLO || t1 == CP_DIPLO) ? t1 : -1;
   const int t_tab = (t1 == CP_ERROR || t1 == CP_REPEAT) ? t1 : -1;
   const bool in_grp = active && ql < 2*LD && M > 0;
-  rel_grp_view<MAXM,G> view; view.S = &S; view.g = g; view.d = d;
-  rel_grp_rv<MAXM,G> rv; rv.S = &S; rv.g = g;
+  typedef typename rel_grp_lds<MAXM,G>::dp_cell dp_cell;
+  // LD = 16: the rows in LDS, anchors through `eff`.  LD = 4: the records streamed from global memory, anchors in the cells
+  typename std::conditional<LD == 4,cp_no_view,rel_grp_view<MAXM,G>>::type view;
+  typename std::conditional<LD == 4,Rec,rel_grp_rv<MAXM,G>>::type rv;
+  if constexpr (LD == 4) rv = rec;
+  else { view.S = &S; view.g = g; view.d = d; rv.S = &S; rv.g = g; }
   int maxM = in_grp ? M : 0;
   for (int o = 32; o > 0; o >>= 1)
     { int x = __shfl_xor(maxM,o); maxM = x > maxM ? x : maxM; }
 
   int i = F ? 0 : M-1;
+  uint32_t standin = 0;                                    // (LD = 4) cp_anc_pair of the interval that stands in for i: i itself
+                                                           // unless the steps since were "only R reachable" ones
+  if constexpr (LD == 4)
+  { double e0 = 0.;                                        // init, class_rel.c:544-580: exp(dp) of the lane's state
+    dp_cell c;
+    if (in_grp)
+      { const cp_riv I = rv(i);                            // (with its pe)
+        cp_rel_init_cell(P,ld,I,i,plen,F,COV,&c);
+        e0 = cp_exp_t(c.dp,xt);
+        standin = cp_anc_pair(I,F);
+      }
+    const double psum = quad_sum1(e0);                     // :582-586, the four terms from the quad's registers
+    if (in_grp)
+      { c.dp = cp_log_t(e0/psum,lt);
+        S.cell[g][d][0][ld].set(c);
+        if (ld == 0)
+          { S.parent[g][d][i] = 0xe4;                      // each state its own parent: 3,2,1,0
+            for (int w = 0; w < rel_grp_lds<MAXM,G>::RW; w++) S.rpos[g][d][w] = 0;
+          }
+      }
+  }
+  else
+  {
   if (in_grp && ld < 4)                                    // init, class_rel.c:544-580
     { cp_riv I = rv(i);
       I.pe = REL_PE(i);
@@ -2340,8 +2455,10 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
         psum += S.tr[g][d][x];
       S.cell[g][d][0][ld].dp = cp_log_t(S.tr[g][d][ld]/psum,lt);
     }
+  }
   grp_sync<WPB>();
 
+  RP_STAMP(10);
   // (LD = 4) P's scalars of the step, read once: behind the fences of grp_sync the compiler reloads them step by step
   const double *const eskel = P->eskel;
   const int skel_kmax = P->skel_kmax;
@@ -2352,6 +2469,10 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   const double D_e = (li_e >= 0 && li_e <= CP_MAX_KMER_CNT) ? P->logint[li_e] : cp_log((double)li_e);
   int cur = 0;
   double pe_next = 0.;                                     // pe of the next interval (E lanes), one step ahead
+  cp_riv I_next; I_next.b = I_next.e = I_next.ccb = I_next.cce = 0; I_next.pe = 0.;    // (LD = 4) the whole record, one step ahead
+  if constexpr (LD == 4)
+    { if (in_grp && M > 1) I_next = rv(F ? 1 : M-2); }
+  else
   if (in_grp && (LD == 4 || t_tab == CP_ERROR) && M > 1)
     pe_next = REL_PE(F ? 1 : M-2);
   for (int k = 1; k < maxM; k++)                           // _update, class_rel.c:279-513
@@ -2359,24 +2480,25 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
       const int i_pred = i;
       if (on) i = F ? k : M-1-k;
       cp_riv I; I.b = I.e = I.ccb = I.cce = 0; I.pe = 0.;
+      double v[4] = { 0., 0., 0., 0. };                    // (LD = 4) the lane's row of the transition matrix
+      double dp_own = 0.;                                  // (LD = 4) dp of the predecessor's cell of the lane's state
       if constexpr (LD == 4)
       { // ---- :300-336 with a lane per source state: its four transitions in straight code.  The lane first works out the
         //      table cells of the E and R terms and the arguments of the two Skellam terms, then all its loads go out
         //      together; no branch depends on the target state.
-        double v[4] = { 0., 0., 0., 0. };                  // exp(logp) of s -> E, R, H, D (0 = exp(-inf) while not live)
+        // v: exp(logp) of s -> E, R, H, D (0 = exp(-inf) while not live)
         bool live = false, r_tab = false, r_cap = false;
         int e0 = 0, e1 = 0, rk = 0, rn = 0, r2 = 0;
         int hb = 0, hcb = 0, hce = 0, db = 0, dcb = 0, te = 0, tce = 0;
-        const double pe_now = pe_next;                     // fetched one step ahead
         if (on)
-          { I = rv(i);
+          { I = I_next;                                    // fetched one step ahead
             if (k+1 < M)
-              pe_next = REL_PE(F ? k+1 : M-2-k);           // (one address per direction: its four lanes load it)
+              I_next = rv(F ? k+1 : M-2-k);                // (one address per direction: its four lanes load it)
             const auto &pr = S.cell[g][d][cur][s];
-            live = pr.dp != -INFINITY;
+            dp_own = pr.dp;
+            live = dp_own != -INFINITY;
             if (live)
               { const int beg_pos = cp_beg_pos(I,F), beg_cnt = cp_beg_cnt(I,F), prc = pr.cnt_[CP_REPEAT-1];
-                I.pe = pe_now;                             // logp_e, class_rel.c:158-170
                 e0 = cp_check_cnt(I.ccb); e1 = cp_check_cnt(I.cce);
                 if (beg_cnt < prc)                         // logp_r, class_rel.c:172-211
                   { r_tab = true;
@@ -2402,6 +2524,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
         { const double A = P->logfact[e0], B = P->logfact[e1];                    // all seven loads of the lane together
           const double RA = P->logfact[rn], RB = P->logfact[rk], RC = P->logfact[r2];
           const double TH = etab[h_in ? hcd*(skel_kmax+1)+hk : 0], TD = etab[d_in ? dcd*(skel_kmax+1)+dk : 0];
+          RP_STAMP(0);
           if (live)
             { const double po = (e0 * D_e - li_e - A)+(e1 * D_e - li_e - B)+CP_E_PO_BASE;       // prob.c:33-39 twice
               const double lp_e = (po > I.pe) ? po : I.pe;
@@ -2422,10 +2545,9 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
               { v[CP_ERROR] = 1.;
                 psum = 4.;
               }
-            for (int x = 0; x < 4; x++) v[x] = cp_log_t(v[x]/psum,lt);
-            for (int x = 0; x < 4; x++) S.tr[g][d][s*4+x] = v[x];          // (tr's readers of the step before are behind its last sync)
+            for (int x = 0; x < 4; x++) v[x] = cp_log_t(v[x]/psum,lt);     // row s of tr: it stays in the lane's registers
           }
-        grp_sync<WPB>();
+        RP_STAMP(1);
       }
       else
       {
@@ -2522,23 +2644,32 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
       // ballot, instead of every lane doing all six maxima (a quarter of this kernel's vector instructions).
       const bool st_lane = on && ld < 4;
       const int l16 = ld & 3;
-      const double *tr = S.tr[g][d];
-      double dp[4] = { 0., 0., 0., 0. };
+      // LD = 4: lane s holds row s of tr (v) and dp of source s.  The state lane t takes its row from its own registers,
+      // column t and the two diagonal entries H->H, D->D from the quad's (DPP): tr never goes through LDS
+      const double *tr = nullptr;
+      double dp[4] = { 0., 0., 0., 0. }, col[4] = { 0., 0., 0., 0. }, tr_hh = 0., tr_dd = 0.;
+      if constexpr (LD == 4)
+        { dp[0] = quad_bcast<0>(dp_own); dp[1] = quad_bcast<1>(dp_own); dp[2] = quad_bcast<2>(dp_own); dp[3] = quad_bcast<3>(dp_own);
+          col[0] = quad_col<0>(v,l16); col[1] = quad_col<1>(v,l16); col[2] = quad_col<2>(v,l16); col[3] = quad_col<3>(v,l16);
+          tr_hh = quad_bcast<CP_HAPLO>(v[CP_HAPLO]); tr_dd = quad_bcast<CP_DIPLO>(v[CP_DIPLO]);
+        }
+      else tr = S.tr[g][d];
       bool row_r = false;
       int  col_s = CP_N_STATE;
       double col_logp = -INFINITY;
       if (st_lane)
-        { for (int x = 0; x < 4; x++) dp[x] = S.cell[g][d][cur][x].dp;
+        { if constexpr (LD != 4)
+            for (int x = 0; x < 4; x++) dp[x] = S.cell[g][d][cur][x].dp;
           { double best = -INFINITY;                       // best target of source l16 (cp_argmax_tr with s fixed)
             int maxt = CP_N_STATE;
             for (int x = 0; x < 4; x++)
-              { const double logp = dp[l16]+tr[l16*4+x];
+              { const double logp = dp[l16]+(LD == 4 ? v[x] : tr[l16*4+x]);
                 if (best < logp) { best = logp; maxt = x; }
               }
             row_r = (maxt == CP_N_STATE || maxt == CP_REPEAT);
           }
           for (int x = 0; x < 4; x++)                      // best source of target l16 (t fixed), before the equalisation
-            { const double logp = dp[x]+tr[x*4+l16];
+            { const double logp = dp[x]+(LD == 4 ? col[x] : tr[x*4+l16]);
               if (col_logp < logp) { col_logp = logp; col_s = x; }
             }
         }
@@ -2547,11 +2678,14 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
       const bool equal  = ((__ballot(st_lane && ((l16 == CP_HAPLO || l16 == CP_DIPLO) && col_s == l16)) >> qsh) & 0xf)
                           == ((1u << CP_HAPLO) | (1u << CP_DIPLO));
       if (st_lane)
-        { cp_cell c;
+        { dp_cell c;
           int pv = l16;
           if (only_r)
-            { c = (cp_cell)S.cell[g][d][cur][l16];
-              cp_rel_only_r_cell(l16,i,&c);
+            { c = (dp_cell)S.cell[g][d][cur][l16];
+              cp_rel_only_r_cell(l16,i,&c,standin);
+              if constexpr (LD == 4)
+                { if (l16 == 0) S.rpos[g][d][i >> 5] |= 1u << (i & 31); }
+              else
               if (l16 == 0)
                 S.eff[g][d][i] = (typename rel_grp_lds<MAXM,G>::eff_t)(S.eff[g][d][i_pred] | rel_grp_lds<MAXM,G>::RPOS);
             }
@@ -2559,16 +2693,18 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
             { double max_logp = col_logp;
               int max_s = col_s;
               if (equal && (l16 == CP_HAPLO || l16 == CP_DIPLO))                      // :382-386, then :391 again for this target
-                { const double a = tr[CP_HAPLO*4+CP_HAPLO], bb = tr[CP_DIPLO*4+CP_DIPLO];
+                { const double a = (LD == 4) ? tr_hh : tr[CP_HAPLO*4+CP_HAPLO], bb = (LD == 4) ? tr_dd : tr[CP_DIPLO*4+CP_DIPLO];
                   const double mn = a < bb ? a : bb;
                   max_logp = -INFINITY; max_s = CP_N_STATE;
                   for (int x = 0; x < 4; x++)
-                    { const double w = (x == l16) ? mn : tr[x*4+l16];
+                    { const double w = (x == l16) ? mn : (LD == 4 ? col[x] : tr[x*4+l16]);
                       const double logp = dp[x]+w;
                       if (max_logp < logp) { max_logp = logp; max_s = x; }
                     }
                 }
               pv = (max_s == CP_N_STATE) ? l16 : max_s;
+              if constexpr (LD == 4) standin = cp_anc_pair(I,F);
+              else
               if (l16 == 0)
                 S.eff[g][d][i] = (typename rel_grp_lds<MAXM,G>::eff_t)i;
               cp_rel_target_cell(P,l16,i,I,F,COV,max_s,max_logp,&S.cell[g][d][cur][0],view,&c);
@@ -2579,7 +2715,9 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
           if (l16 == 0)
             S.parent[g][d][i] = (uint8_t)pk;
         }
+      RP_STAMP(2);
       grp_sync<WPB>();
+      RP_STAMP(3);
       cur ^= 1;
     }
   // the buffer holding the last interval's cells: M-1 swaps happened for this read
@@ -2597,17 +2735,120 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
       if (F)
         for (int k = M-1; k >= 0; k--)
           { const int pk = S.parent[g][d][k];
-            as[k] = (S.eff[g][d][k] & rel_grp_lds<MAXM,G>::RPOS) ? (int8_t)CP_REPEAT : (int8_t)st;
+            as[k] = rel_is_rpos(S,g,d,k) ? (int8_t)CP_REPEAT : (int8_t)st;
             st = (pk >> (2*st)) & 3;
           }
       else
         for (int k = 0; k < M; k++)
           { const int pk = S.parent[g][d][k];
-            as[k] = (S.eff[g][d][k] & rel_grp_lds<MAXM,G>::RPOS) ? (int8_t)CP_REPEAT : (int8_t)st;
+            as[k] = rel_is_rpos(S,g,d,k) ? (int8_t)CP_REPEAT : (int8_t)st;
             st = (pk >> (2*st)) & 3;
           }
     }
   grp_sync<WPB>();
+  RP_STAMP(4);
+  RP_FLUSH(G == 8,0,4,0);
+  RP_FLUSH(G == 8,10,10,0);
+}
+
+// The coverage heuristics behind a pass (cp_rel_post1 / cp_rel_post2 of cp_class.h, class_rel.c:629-735) for the main
+// class, on the four lanes of a (read, direction) instead of its lead lane: they are counts, first / last indices and the
+// integer sums lsum, csum over the intervals of one class -- exact in any order -- so lane ld takes the intervals ld, ld+4, ...
+// and the quad's partial results are joined through DPP moves; every lane of the quad holds the results.  A lane rewrites
+// only the assignments it reads, so the stages need no sync between them.  The interval fields come from the records in
+// global memory, four loads in flight where the lead lane had one.
+__device__ __forceinline__ int quad_isum(int x)
+{ x += __builtin_amdgcn_mov_dpp(x,0xb1,0xf,0xf,true);      // quad_perm [1,0,3,2]
+  x += __builtin_amdgcn_mov_dpp(x,0x4e,0xf,0xf,true);      // quad_perm [2,3,0,1]
+  return x;
+}
+__device__ __forceinline__ int quad_imin(int x)
+{ int y = __builtin_amdgcn_mov_dpp(x,0xb1,0xf,0xf,true); x = y < x ? y : x;
+  y = __builtin_amdgcn_mov_dpp(x,0x4e,0xf,0xf,true); return y < x ? y : x;
+}
+__device__ __forceinline__ int quad_imax(int x)
+{ int y = __builtin_amdgcn_mov_dpp(x,0xb1,0xf,0xf,true); x = y > x ? y : x;
+  y = __builtin_amdgcn_mov_dpp(x,0x4e,0xf,0xf,true); return y > x ? y : x;
+}
+// lsum, csum over the intervals of class `cls` (all of them: cls < 0)
+template <class Rv>
+__device__ __forceinline__ void quad_cov_sums(const Rv &rv, const int8_t *asgn, int M, int ld, int cls, int &lsum, int &csum)
+{ int ls = 0, cs = 0;
+  for (int i = ld; i < M; i += 4)
+    if (cls < 0 || asgn[i] == cls)
+      { const cp_riv I = rv(i);
+        const int l = I.e-I.b;
+        ls += l;
+        cs += (I.ccb+I.cce)*l/2;
+      }
+  lsum = quad_isum(ls); csum = quad_isum(cs);
+}
+// how many intervals have class `cls`
+__device__ __forceinline__ int quad_count(const int8_t *asgn, int M, int ld, int cls)
+{ int n = 0;
+  for (int i = ld; i < M; i += 4) n += (asgn[i] == cls);
+  return quad_isum(n);
+}
+// first and last interval of class `cls` (-1: none)
+__device__ __forceinline__ void quad_first_last(const int8_t *asgn, int M, int ld, int cls, int &first, int &last)
+{ int f = M, l = -1;
+  for (int i = ld; i < M; i += 4)
+    if (asgn[i] == cls) { if (f == M) f = i; l = i; }
+  f = quad_imin(f); last = quad_imax(l);
+  first = (f == M) ? -1 : f;
+}
+template <class Rv>
+__device__ bool rel_post1_quad(const cp_dev_params *P, const Rv &rv, int M, int F, const int8_t *asgn, int *COV, int ld)
+{ const int *G = P->cov;
+  if (quad_count(asgn,M,ld,CP_HAPLO)) return false;
+  int first_d, last_d;
+  quad_first_last(asgn,M,ld,CP_DIPLO,first_d,last_d);
+  const int seed = F ? first_d : last_d;                   // first D (:641-642) / last D (:757)
+  if (seed < 0) return false;
+  int lsum, csum;
+  quad_cov_sums(rv,asgn,M,ld,CP_DIPLO,lsum,csum);
+  const double mean_dcov = (double)csum/lsum;
+  if (!(mean_dcov < G[CP_DIPLO])) return false;
+  const cp_riv S = rv(seed);
+  COV[CP_HAPLO] = F ? S.ccb : S.cce;
+  COV[CP_DIPLO] = (COV[CP_HAPLO]+G[CP_HAPLO]) & 0xffff;
+  return true;
+}
+template <class Rv>
+__device__ double rel_post2_quad(const cp_dev_params *P, const Rv &rv, int M, int8_t *asgn, bool rerun, int ld)
+{ const int *G = P->cov;
+  int lsum, csum;
+  if (rerun && quad_count(asgn,M,ld,CP_HAPLO) == 0)           // :651-669
+    { quad_cov_sums(rv,asgn,M,ld,CP_DIPLO,lsum,csum);
+      const double mean_dcov = (double)csum/lsum;
+      if (fabs(mean_dcov-G[CP_HAPLO]) <= fabs(mean_dcov-G[CP_DIPLO]))
+        for (int i = ld; i < M; i += 4)
+          if (asgn[i] == CP_DIPLO) asgn[i] = CP_HAPLO;
+    }
+  int n = quad_count(asgn,M,ld,CP_HAPLO);
+  if (n == M)                                               // :674-689
+    { quad_cov_sums(rv,asgn,M,ld,-1,lsum,csum);
+      const double mean_hcov = (double)csum/lsum;
+      if (fabs(mean_hcov-G[CP_HAPLO]) >= fabs(mean_hcov-G[CP_DIPLO]))
+        { for (int i = ld; i < M; i += 4) asgn[i] = CP_DIPLO;
+          n = 0;
+        }
+    }
+  if (n >= M * 0.7)                                         // :691-712
+    { quad_cov_sums(rv,asgn,M,ld,CP_HAPLO,lsum,csum);
+      const double mean_hcov = (double)csum/lsum;
+      if (fabs(mean_hcov-G[CP_HAPLO]) >= fabs(mean_hcov-G[CP_DIPLO]))
+        for (int i = ld; i < M; i += 4)
+          { if (asgn[i] == CP_HAPLO)      asgn[i] = CP_DIPLO;
+            else if (asgn[i] == CP_DIPLO) asgn[i] = CP_REPEAT;
+          }
+    }
+  int first_d, last_d, first_h, last_h;                     // :714-731
+  quad_first_last(asgn,M,ld,CP_DIPLO,first_d,last_d);
+  quad_first_last(asgn,M,ld,CP_HAPLO,first_h,last_h);
+  if (!(first_d >= 0 && first_h >= 0))
+    return 1.;
+  return ((double)rv(first_d).ccb/rv(first_h).ccb)/((double)rv(last_d).cce/rv(last_h).cce);
 }
 
 // size classes of the grouped classify kernels (reads per wave / largest interval count)
@@ -2644,9 +2885,18 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
 #define REL_EXTRA_ATTR
 #endif
 // waves per block of the main size class (they share the block's copy of the libm tables, 4 KB, and nothing else).
-// Two: 40.7 KB per block, four blocks to a CU.  Four-wave blocks (77.3 KB, two to a CU) hold the same 8 waves and the
-// kernel alone runs as fast, but a CU that holds two of them has 6 KB of LDS left for the other stream's kernels: the step
-// takes 24.2 ms with four-wave blocks and 23.6 with two-wave ones.  One-wave blocks (7 to a CU): 4.11 ms alone.
+// With the 18.3-KB record (rows, tr and `eff` in LDS, 2 waves per SIMD): two-wave blocks of 40.7 KB, four to a CU; four-wave
+// blocks (77.3 KB, two to a CU) held the same 8 waves and ran as fast alone, but left 6 KB of a CU's LDS to the other
+// stream's kernels: the step took 24.2 ms with them and 23.6 with two-wave ones.  One-wave blocks (7 to a CU): 4.11 ms alone.
+// With the 9.2-KB record (rel_grp_lds<MAXM,8>) and 3 waves per SIMD, 12 waves to a CU (profiles/rel_grp_occupancy_ab.txt,
+// section 6; the kernel alone / in the two-stream pipeline from one traced run each, the step from the short bench, two runs):
+//   two-wave blocks   (22.5 KB, six to a CU:  135 KB)   2604 us / 6199 us   22.36 22.52 ms
+//   three-wave blocks (31.7 KB, four to a CU: 127 KB)   2672 us / 5189 us   22.37 22.40 ms
+//   four-wave blocks  (41.0 KB, three to a CU: 123 KB)  2624 us / 6060 us   (traced step 22.59, as two-wave blocks)
+//   two-wave blocks at 2 waves per SIMD                 3425 us / 6466 us   23.84 23.76 ms  (the parent: 3249 / 7438, 23.50 23.54)
+// The block shapes are within the run-to-run spread of each other: two stays.  The third wave per SIMD is the gain; the
+// new record at two waves per SIMD is slower than the old one (the quad's DPP moves and the record's loads are in the chain
+// where LDS reads were).
 #ifndef REL_SMALL_WPB
 #define REL_SMALL_WPB 2
 #endif
@@ -2654,13 +2904,17 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
 //  Gbases/s.  Round 4: four-wave blocks with the libm tables in LDS; with 64-byte cells and a size class of 128 a block was
 //  52 KB, three to a CU = 3 waves per SIMD (149 VGPRs, nothing spilled): 194.4 Gbases/s; with the 40-byte cell_t and a
 //  size class of 112 a block is 40.7 KB, four to a CU = 4 waves per SIMD at 128 VGPRs, 14 spilled: 198.6-199.7.
-//  With eight reads per wave LDS allows 2 waves per SIMD, which leaves each up to 256 registers: 170, nothing spilled)
+//  With eight reads per wave and the 18.3-KB record LDS allowed 2 waves per SIMD, which left each up to 256 registers: 171,
+//  nothing spilled.  With the 9.2-KB record LDS allows 3: 168 registers, one 8-byte value spilled with the compact records
+//  and three in the stage API's form -- loop-invariant pointers, stored before the loop over read groups and loaded in the
+//  preheaders of the tails' loops behind the DP of a group; nothing is spilled inside the DP loop.
+//  The rare class (G = 1: 19.5 KB of LDS per wave) stays at 2.)
 #ifndef REL_WAVES_PER_EU
-#define REL_WAVES_PER_EU 2
+#define REL_WAVES_PER_EU 3
 #endif
 
 template <int MINM, int MAXM, int G, int WPB, int COMPACT = 0>
-__global__ void __launch_bounds__(WAVE*WPB) __attribute__((amdgpu_waves_per_eu(REL_WAVES_PER_EU))) REL_EXTRA_ATTR
+__global__ void __launch_bounds__(WAVE*WPB) __attribute__((amdgpu_waves_per_eu(G == 8 ? REL_WAVES_PER_EU : 2))) REL_EXTRA_ATTR
 k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restrict__ prof_off, int nreads,
                    cp_intvl *__restrict__ intvl_all, cp_intvl *__restrict__ rintvl_all, const int32_t *__restrict__ relmap_all,
                    const int64_t *__restrict__ ioff, const int32_t *__restrict__ nrel,
@@ -2696,8 +2950,9 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
   const int64_t o = ioff[rr];
   cp_intvl *rintvl = rintvl_all+o;
   const cp_rrec *rrec = COMPACT ? rrec_all+o : nullptr;
-  const char *pe0 = COMPACT ? reinterpret_cast<const char *>(&rrec[0].pe) : reinterpret_cast<const char *>(&rintvl[0].pe);
-  constexpr int pe_stride = COMPACT ? (int)sizeof(cp_rrec) : (int)sizeof(cp_intvl);
+  rel_rec<COMPACT> rec; rec.rrec = rrec; rec.rintvl = rintvl;
+  if constexpr (G != 8)                                     // (the main class streams the records instead: rel_grp_lds<MAXM,8>)
+  {
   if (COMPACT)
     for (int k = ql; k < M; k += L)
       { const cp_rrec q = rrec[k];
@@ -2709,39 +2964,65 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
         S.ccb[g][k] = rintvl[k].ccb; S.cce[g][k] = rintvl[k].cce;
       }
   grp_sync<WPB>();
+  }
 
   constexpr int LD = REL_LD(G);                            // lanes per direction, see rel_grp_pass
   const int d = (ql / LD) & 1, F = (d == 0);
   const int leadlane = g*L+d*LD;
   const bool lead = (M > 0) && (ql < 2*LD) && ((ql % LD) == 0);
   int COV[4] = { P->cov[0], P->cov[1], P->cov[2], P->cov[3] };
-  rel_grp_rv<MAXM,G> rv; rv.S = &S; rv.g = g;
-  rel_grp_pass<MAXM,G,WPB>(P,S,T,pe0,pe_stride,M,plen,M > 0,COV);
+#ifdef CP_PROF_WALK
+  const unsigned long long rp_g0 = wall_clock64();
+#endif
+  // interval fields of the serial tails: the rows in LDS, or (main class) the records just streamed, warm in L2
+  typename std::conditional<G == 8,rel_rec<COMPACT>,rel_grp_rv<MAXM,G>>::type rv;
+  if constexpr (G == 8) rv = rec;
+  else { rv.S = &S; rv.g = g; }
+  rel_grp_pass<MAXM,G,WPB>(P,S,T,rec,M,plen,M > 0,COV);
 
+  RP_DECL(7);                                              // ([5..11] of g_rel_prof)
   int rerun = 0;                                           // class_rel.c:629-650
+  if constexpr (G == 8)                                    // (every lane of a read belongs to one of its two quads)
+    { if (M > 0) rerun = rel_post1_quad(P,rv,M,F,S.asgn(g,d),COV,ql % LD) ? 1 : 0; }
+  else
   if (lead)
     rerun = cp_rel_post1(P,rv,M,F,S.asgn(g,d),COV) ? 1 : 0;
   rerun = __shfl(rerun,leadlane);
   COV[CP_HAPLO] = __shfl(COV[CP_HAPLO],leadlane);
   COV[CP_DIPLO] = __shfl(COV[CP_DIPLO],leadlane);
   if (M == 0 || ql >= 2*LD) rerun = 0;
+  RP_STAMP(0);
 #ifdef CP_PROF_WALK
   { const uint64_t rm = __ballot(lead && rerun != 0), lm_ = __ballot(lead);      // (read, direction) pairs that repeat the pass / all; waves that do
     if (lane == 0) { atomicAdd(&g_emit_prof[6],(unsigned long long)__popcll(rm) | ((unsigned long long)__popcll(lm_) << 32)); atomicAdd(&g_emit_prof[7],(rm ? 1ull : 0ull) | (1ull << 32)); }
   }
 #endif
   if (__ballot(rerun != 0))
-    rel_grp_pass<MAXM,G,WPB>(P,S,T,pe0,pe_stride,M,plen,rerun != 0,COV);
+    rel_grp_pass<MAXM,G,WPB>(P,S,T,rec,M,plen,rerun != 0,COV);
+#ifdef CP_PROF_WALK
+  rp_t = wall_clock64();                                   // (behind the second pass, if any)
+#endif
   double hdrr = 1.;
+  if constexpr (G == 8)
+    { if (M > 0) hdrr = rel_post2_quad(P,rv,M,S.asgn(g,d),rerun != 0,ql % LD); }
+  else
   if (lead)
     hdrr = cp_rel_post2(P,rv,M,F,S.asgn(g,d),rerun != 0);
   const double hf = __shfl(hdrr,g*L), hb = __shfl(hdrr,g*L+LD);
   grp_sync<WPB>();
+  RP_STAMP(1);
 
   int take_bw = 0;                                         // class_rel.c:904-938
+  bool eq = true;                                          // main class: the compare on the read's eight lanes
+  if constexpr (G == 8)
+    { bool diff = false;
+      const int8_t *fw = S.asgn(g,0), *bw = S.asgn(g,1);
+      for (int i = ql; i < M; i += L) diff |= (fw[i] != bw[i]);
+      eq = ((__ballot(diff) >> (g*L)) & ((1ull << L)-1)) == 0;
+    }
   if (M > 0 && ql == 0)
     { const int8_t *fw = S.asgn(g,0), *bw = S.asgn(g,1);
-      bool eq = true;
+      if constexpr (G != 8)
       for (int i = 0; i < M; i++)
         if (fw[i] != bw[i]) { eq = false; break; }
       if (!eq)
@@ -2764,6 +3045,7 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
         }
     }
   take_bw = __shfl(take_bw,g*L);
+  RP_STAMP(2);
   cp_intvl *intvl = intvl_all+o;
   const int32_t *relmap = relmap_all+o;
   int8_t *gfw = asgn_all+o, *gbw = asgn_all+totalI+o;
@@ -2782,6 +3064,11 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
       if (soa.c) soa.c[o+relmap[i]].asgn = a;
     }
   grp_sync<WPB>();                                             // the LDS record is reused by the block's next group
+  RP_STAMP(6);
+#ifdef CP_PROF_WALK
+  rp_acc[3] = wall_clock64()-rp_g0; rp_acc[4] = 1;
+#endif
+  RP_FLUSH(G == 8,5,11,5);
   }
 }
 

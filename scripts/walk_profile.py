@@ -28,6 +28,7 @@ ph = (C.c_ulonglong * 36)()
 lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
 ur = (C.c_ulonglong * 4)()
+rp = (C.c_ulonglong * 12)()
 clf.classify(b)
 lib().cp_debug_unrel_prof(ur)
 lib().cp_debug_phase_prof(ph)
@@ -38,6 +39,7 @@ lib().cp_debug_phase_prof(ph)
 lib().cp_debug_live_prof(lv)
 lib().cp_debug_emit_prof(em)
 lib().cp_debug_unrel_prof(ur)
+lib().cp_debug_rel_prof(rp)
 pn = {0: "k_wall_tasks: candidate list", 7: "k_wall_tasks: prelude + filters", 6: "k_wall_tasks: live tasks",
       1: "k_find_wall: replay", 2: "unwall/sort/olist", 3: "multi-error search", 4: "merge + sorts",
       8: "components + boundaries", 5: "records + find_rel"}
@@ -54,5 +56,13 @@ print("classify_unrel (main class): %d waves, %.1f ticks per wave: committing th
       % (ur[3], ur[2] / max(1, ur[3]), ur[0] / max(1, ur[3]), 100.0 * ur[0] / max(1, ur[2]), ur[1] / max(1, ur[3]), (ur[2] - ur[0] - ur[1]) / max(1, ur[3])))
 print("classify_rel: %d of %d (read, direction) passes are repeated with adjusted coverages (class_rel.c:629-650); %d of %d waves run the DP a second time"
       % (em[6] & 0xffffffff, em[6] >> 32, em[7] & 0xffffffff, em[7] >> 32))
+if rp[9]:
+    names = ["step: start to the return of its loads", "step: from there to the tr values", "step: state phase", "step: syncs",
+             "traceback", "cp_rel_post1", "cp_rel_post2", "fw / bw compare"]
+    order = [10, 0, 1, 2, 3, 4, 5, 6, 7, 11]
+    label = dict(zip(range(8), names)); label[10] = "init of a pass"; label[11] = "final write"
+    print("classify_rel (main class): %d groups of eight reads, %.1f ticks per group (stamped: every stamp drains the wave's memory operations)" % (rp[9], rp[8] / rp[9]))
+    for k in order:
+        print("    %-42s %9.1f ticks per group  %5.1f %%" % (label[k], rp[k] / rp[9], 100.0 * rp[k] / rp[8]))
 print("reads %d: memo on chip %d, flags on chip to the end %d, sent their flags to the arrays after the replay (more off-list SELF walls than slots) %d, flags on chip after the walk %d" %
       (b.nreads, lv[4], lv[5], lv[6], lv[7]))
