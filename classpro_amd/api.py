@@ -815,6 +815,31 @@ class SortedKmers:
         """(only_a, only_b, both): the tally of `combine` with nothing built (cp_kmer_sorted_combine with out == NULL)."""
         return self._combine(other, "and", "left", a_range, b_range, False)[1][:3]
 
+    _CMP_WEIGHTS = {"keys": 0, "a": 1, "b": 2}
+
+    def compare_hist(self, other, xmax=8, ymax=1000, weight="keys", a_range=None, b_range=None):
+        """cp_kmer_sorted_compare_hist ("Count comparison of sorted k-mers" in include/classpro_amd.h): a numpy int64
+        [xmax+1, ymax+1] whose cell [x, y] sums, over the keys with min(count in this snapshot, xmax) == x and
+        min(count in `other`, ymax) == y (0 for a side the key is not in), 1 for weight "keys", this snapshot's count
+        for "a" and the other's for "b".  Ranges are those of `combine`; `other` may be `self`."""
+        if weight not in self._CMP_WEIGHTS:
+            raise ValueError("weight must be one of 'keys', 'a', 'b'")
+        if not isinstance(other, SortedKmers):
+            raise ValueError("the other operand must be a SortedKmers")
+        if self.s is None or other.s is None:
+            raise ValueError("SortedKmers is closed")
+        if other.K != self.K or other.device != self.device:
+            raise ValueError("the operands must hold k-mers of the same length on the same device")
+        xmax, ymax = int(xmax), int(ymax)
+        if not (1 <= xmax <= 32767 and 1 <= ymax <= 32767 and (xmax + 1) * (ymax + 1) <= 1 << 22):
+            raise ValueError("xmax and ymax must lie in [1, 32767] and span at most 2^22 cells")
+        mat = np.zeros((xmax + 1, ymax + 1), np.int64)
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_compare_hist(self.s, other.s, self._range4(a_range, b_range),
+                                                     self._CMP_WEIGHTS[weight], xmax, ymax, mat.ctypes.data,
+                                                     _stream_of(self.device)))
+        return mat
+
     def hist(self):
         """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
         (1, 32767, ilowcnt, ihighcnt, int64[32767])."""
@@ -849,6 +874,14 @@ def bin_calls(hits, only_a, only_b, min_markers=1, normalise=True):
     for i in range(len(h)):
         out[i] = check(L.cp_bin_call(h[i].ctypes.data, int(only_a), int(only_b), int(min_markers), 1 if normalise else 0))
     return bytes(out)
+
+
+def kmer_qv(K, a_only, a_total):
+    """cp_kmer_qv: (qv, err) by Merqury's rule from the "a"-weighted `compare_hist` of an assembly against its reads:
+    `a_only` the sum of column 0, `a_total` the sum of the whole matrix.  qv is inf when a_only is 0."""
+    qv, err = C.c_double(), C.c_double()
+    check(lib().cp_kmer_qv(int(K), int(a_only), int(a_total), C.byref(qv), C.byref(err)))
+    return qv.value, err.value
 
 
 def ktab_tile():

@@ -1179,5 +1179,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // set algebra on sorted snapshots and the histogram of one (tabop): kmer_setops.hip
 #include "kmer_setops.hip"
 
+// 2-D count comparison of two sorted snapshots and the k-mer QV (tabcmp): kmer_cmphist.hip
+#include "kmer_cmphist.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

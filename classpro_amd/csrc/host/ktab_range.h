@@ -1,4 +1,4 @@
-// ktab_range.h -- the count range of a table operand, "<path>[:<lo>-<hi>]", for the tools that take one (tabop, tabbin):
+// ktab_range.h -- the count range of a table operand, "<path>[:<lo>-<hi>]", for the tools that take one (tabop, tabbin, tabcmp):
 // one parser, one message.  Plain C++; no device code.
 #pragma once
 #include <cerrno>

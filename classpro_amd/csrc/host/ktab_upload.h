@@ -1,4 +1,4 @@
-// ktab_upload.h -- a FASTK k-mer table from the host onto the device as a sorted snapshot (tab2prof, tabop, tabbin): the
+// ktab_upload.h -- a FASTK k-mer table from the host onto the device as a sorted snapshot (tab2prof, tabop, tabbin, tabcmp): the
 // records of an opened KtabReader go up in pieces of TAB_RANGE entries through one device buffer into
 // cp_kmer_sorted_load_records and are checked there (cp_kmer_sorted_load_end: strictly ascending keys; "Sorted k-mers as
 // input" in include/classpro_amd.h).  A failed call ends the tool.  The buffer is the caller's, so that several tables

@@ -649,6 +649,45 @@ int     cp_bin_call(const int64_t *hit /* [CP_HIT_WIDTH] */, int64_t only_a, int
                     int normalise);
 
 /* ------------------------------------------------------------------------------------------
+ * Count comparison of sorted k-mers (tabcmp): the joint distribution of the counts that two snapshots give one key -- the
+ * matrix of KAT's comp and the spectra-cn of Merqury (the read-count spectrum split by the copy number in an assembly) --
+ * by the streaming merge of "Set algebra on sorted k-mers", and the k-mer QV that follows from it.  Everything on the
+ * device is in integers and independent of tile size, grid and scheduling.
+ *
+ *   Presence   exactly as in cp_kmer_sorted_combine: a key is IN A when A holds it and a_min <= cntA <= a_max with the
+ *              snapshot's own d_cnt; IN B likewise.  `range` is a HOST array a_min a_max b_min b_max; NULL means
+ *              [1, INT64_MAX] for both.  An entry outside its range is treated exactly as if it were absent.
+ *   Cell       a key that is in A or in B has x = min(cntA, xmax), 0 when it is not in A, and y = min(cntB, ymax), 0 when
+ *              it is not in B.  The counts are the exact 64-bit d_cnt, so a snapshot sorted here may hold counts above
+ *              32767.  mat[x*(ymax+1)+y] receives 1 under CP_CMP_KEYS, cntA under CP_CMP_A and cntB under CP_CMP_B, the
+ *              count of a side the key is not in being 0.  A key in neither is not counted, so mat[0] is always 0.  Row
+ *              xmax and column ymax are the "at least" cells.
+ *   Sums       exact in 64 bits (taken modulo 2^64).  `mat` is a HOST array and is overwritten.
+ *   Operands   both ready and of the same K; a == b is legal (only cells (min(c, xmax), min(c, ymax)) are non-zero), so
+ *              are size 0 (two empty operands give a matrix of zeros) and K < 5.  Both are only read.
+ *   Errors     all before any launch: CP_EINVAL for a NULL a, b or mat, an unready operand, differing K, a range with
+ *              min < 1 or max < min, a weight outside the enum, xmax or ymax outside [1, 32767], and
+ *              (xmax+1)*(ymax+1) > 2^22.  An allocation that fails is CP_ENOMEM with the byte count in the message,
+ *              nothing leaked.  Synchronises `stream`.
+ *   Memory     16 bytes per tile of cp_ktab_tile() entries of the two operands together, and the matrix; never anything
+ *              per entry.
+ *   Knobs      read per call from the environment, for measurements and tests: CLASSPRO_CMP_GRID=<n> sets the number of
+ *              blocks, clamped to [1, the default]; CLASSPRO_CMP_LDS=0 sends every cell straight to the matrix in device
+ *              memory instead of summing the low corner on chip.  Neither changes a result.
+ *
+ * cp_kmer_qv is Merqury's rule; host only, no device involved.  a_only and a_total are the CP_CMP_A sums over column
+ * y = 0 and over the whole matrix: the k-mers of A (an assembly) that B (the reads) does not hold, and all of A's.
+ * err = 1 - pow(1 - (double)a_only / a_total, 1.0 / K), qv = -10 * log10(err), and qv = +inf when a_only == 0.  CP_EINVAL
+ * for a_total <= 0, a_only < 0, a_only > a_total, K < 1 or a NULL qv or err.
+ */
+enum { CP_CMP_KEYS = 0, CP_CMP_A = 1, CP_CMP_B = 2 };
+int     cp_kmer_sorted_compare_hist(const cp_kmer_sorted *a, const cp_kmer_sorted *b,
+                                    const int64_t *range /* host [4]: a_min a_max b_min b_max, or NULL */,
+                                    int weight, int xmax, int ymax,
+                                    int64_t *mat /* host [(xmax+1)*(ymax+1)], overwritten */, void *stream);
+int     cp_kmer_qv(int K, int64_t a_only, int64_t a_total, double *qv, double *err);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
