@@ -134,10 +134,18 @@ CP_HD int cp_check_cnt(int n)
 }
 
 // ---- prob.c:33-39 ---------------------------------------------------------------------------
+// In two steps for a caller whose lambda is constant and whose logfact[k] is loaded ahead (k_classify_unrel_grp):
+// log(lambda), then the value from it and logfact[k] of the checked k.
+CP_HD double cp_poisson_loglambda(const cp_dev_params *P, int lambda)
+{ return (lambda >= 0 && lambda <= CP_MAX_KMER_CNT) ? P->logint[lambda] : cp_log((double)lambda); }
+
+CP_HD double cp_logp_poisson_vals(int k, double ll, int lambda, double lfk)
+{ return k * ll - lambda - lfk; }
+
 CP_HD double cp_logp_poisson(const cp_dev_params *P, int k, int lambda)
 { k = cp_check_cnt(k);
-  double ll = (lambda >= 0 && lambda <= CP_MAX_KMER_CNT) ? P->logint[lambda] : cp_log((double)lambda);
-  return k * ll - lambda - P->logfact[k];
+  double ll = cp_poisson_loglambda(P,lambda);
+  return cp_logp_poisson_vals(k,ll,lambda,P->logfact[k]);
 }
 
 // ---- prob.c:41-44 ---------------------------------------------------------------------------
@@ -146,11 +154,15 @@ CP_HD double cp_logp_skellam(int k, double lambda)
 
 // ---- prob.c:59-73 with log(p), log(1-p) supplied ----------------------------------------------
 // `lf` is anything indexable like the log-factorial table: P->logfact, or an LDS-backed accessor.
+// (cp_logp_binom_vals: from the three log-factorials of the checked k <= n, for a caller that loads them ahead)
+CP_HD double cp_logp_binom_vals(double lfn, double lfk, double lfnk, int k, int n, double lpe, double l1mpe)
+{ return lfn - lfk - lfnk + k * lpe + (n-k) * l1mpe; }
+
 template <class LF>
 CP_HD double cp_logp_binom_pre(const LF &lf, int k, int n, double lpe, double l1mpe)
 { k = cp_check_cnt(k);
   n = cp_check_cnt(n);
-  return lf[n] - lf[k] - lf[n-k] + k * lpe + (n-k) * l1mpe;
+  return cp_logp_binom_vals(lf[n],lf[k],lf[n-k],k,n,lpe,l1mpe);
 }
 
 // ---- prob.c:76-112, exact == false ------------------------------------------------------------
@@ -198,15 +210,22 @@ static inline
 double cp_logp_trans_calc(const cp_dev_params *P, int k, double cd)
 { return cp_logp_skellam(k,cd/P->read_len); }
 
+// Where the table holds the value for the checked cov and d = |e-b| (NULL: outside it, or no table): "address first,
+// load later" for a caller that puts its loads in flight together; the table's base and limits are the caller's copies
+// of P's.
+CP_HD const double *cp_logp_trans_at(const double *skel, int skel_kmax, long long skel_cdmax, int d, int cb, int ce, int cov)
+{ const int k = ce-cb < 0 ? cb-ce : ce-cb;
+  const long long cd = (long long)cov*d;
+  return (skel && k <= skel_kmax && cd <= skel_cdmax) ? skel+(cd*(skel_kmax+1)+k) : nullptr;
+}
+
 CP_HD double cp_logp_trans(const cp_dev_params *P, int b, int e, int cb, int ce, int cov)
 { cov &= 0xffff;
   int d = e-b;
   if (d < 0) d = -d;
 #if defined(__HIP_DEVICE_COMPILE__)
-  const int k = ce-cb < 0 ? cb-ce : ce-cb;
-  const long long cd = (long long)cov*d;
-  if (P->skel && k <= P->skel_kmax && cd <= P->skel_cdmax)
-    return P->skel[cd*(P->skel_kmax+1)+k];
+  if (const double *at = cp_logp_trans_at(P->skel,P->skel_kmax,P->skel_cdmax,d,cb,ce,cov))
+    return *at;
 #endif
   return cp_logp_trans_calc(P,ce-cb,(double)cov*d);
 }
@@ -257,11 +276,15 @@ static inline
 double cp_logp_uerr_calc(const cp_dev_params *P, int est, int c)
 { return cp_log(cp_p_errorin(P->logfact,CP_OTHERS,0.1,P->u_lpe,P->u_l1mpe,est,c)); }
 
+// (cp_logp_uerr_at: where the table holds the value, NULL outside it -- as cp_logp_trans_at)
+CP_HD const double *cp_logp_uerr_at(const double *uerr, int uerr_max, int est, int c)
+{ return (uerr && est <= uerr_max && c >= 0 && c <= est) ? uerr+((long long)est*(uerr_max+1)+c) : nullptr; }
+
 CP_HD double cp_logp_uerr(const cp_dev_params *P, int est, int c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (P->uerr && est <= P->uerr_max && c >= 0 && c <= est)
-    return P->uerr[(long long)est*(P->uerr_max+1)+c];
+  if (const double *at = cp_logp_uerr_at(P->uerr,P->uerr_max,est,c))
+    return *at;
 #endif
   return cp_logp_uerr_calc(P,est,c);
 }

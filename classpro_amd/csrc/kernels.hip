@@ -863,7 +863,7 @@ __device__ __forceinline__ cp_intvl cp_soa_get(const cp_soa &S, int64_t at)
 #ifdef CP_PROF_WALK
 __device__ unsigned long long g_phase_max[12], g_phase_sum[12], g_phase_arg[12];
 __device__ unsigned long long g_live_prof[8];
-__device__ unsigned long long g_unrel_prof[4];          // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] in the rest of the rounds, [2] of the kernel; [3] waves
+__device__ unsigned long long g_unrel_prof[8];          // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] of a round up to its first global load, [2] of the kernel; [3] waves; [4] of a round from there to the new classes (waiting for the loads and using them); [5] of the interval load before the rounds, [6] of the sort
 __device__ unsigned long long g_emit_prof[8];           // wave time inside the emission loop: [0] boundaries, [1] make_interval, [2] find_rel, [3] record stores, [4] compaction
 #ifdef CP_PROF_INNER
 #define EM_LT0() unsigned long long em_t = wall_clock64()
@@ -3131,6 +3131,19 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   static_assert(L >= 8 && (L % 8) == 0, "8 role lanes per read");
   const int lane = lane_id();
   const int g = lane/L, ql = lane%L, gbase = g*L;
+  // role of this lane inside its slot: class (H,D) x side (L,R) x kind (0: max(er,sf), 1: sf_er) -- see the rounds below
+  constexpr int K = L/8;
+  const int sub = ql >> 3, role = ql & 7, sbase = gbase+sub*8;
+  const int s2 = (role >> 2) & 1, side = (role >> 1) & 1, kind = role & 1;
+  const int s = s2 ? CP_DIPLO : CP_HAPLO;
+  // What a round reads of *P is constant for the kernel, and between two rounds lie LDS atomics and stores, behind which
+  // the compiler reads every field again: once per block, here.  log(lambda) of the three Poisson terms is constant too.
+  const double *const skel = P->skel, *const uerr = P->uerr, *const logfact = P->logfact;
+  const int skel_kmax = P->skel_kmax, uerr_max = P->uerr_max;
+  const long long skel_cdmax = P->skel_cdmax;
+  const int covE = P->cov[CP_ERROR], REP = P->cov[CP_REPEAT], covH = P->cov[CP_HAPLO], covD = P->cov[CP_DIPLO];
+  const double llE = cp_poisson_loglambda(P,covE), llH = cp_poisson_loglambda(P,covH), llD = cp_poisson_loglambda(P,covD);
+  const double dr_ratio = P->dr_ratio, r_lp = P->r_lp, r_l1mp = P->r_l1mp;
   for (int blk = blockIdx.x; blk*G < nreads; blk += gridDim.x)     // groups of a block, as in k_classify_rel_grp
   {
 #ifdef CP_PROF_WALK
@@ -3146,8 +3159,13 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   cp_intvl *intvl = intvl_all+io;
   if (N <= MINN || N > MAXN || too_long) N = 0;            // other size classes / sequential kernel
   if (__ballot(N > 0) == 0) continue;
+#ifdef CP_PROF_WALK
+  unsigned long long ur_commit = 0, ur_pre = 0, ur_use = 0, ur_load = 0, ur_sort = 0, ur_t = wall_clock64();
+#define UR_STAMP(acc) do { const unsigned long long t_ = wall_clock64(); acc += t_-ur_t; ur_t = t_; } while (0)
+#else
+#define UR_STAMP(acc) ((void)0)
+#endif
   const int nwords = (N+63) >> 6;
-  const int REP = P->cov[CP_REPEAT];
   int maxN = N;
   for (int o = 32; o > 0; o >>= 1)
     { int x = __shfl_xor(maxN,o); maxN = x > maxN ? x : maxN; }
@@ -3183,6 +3201,7 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
         }
     }
   wave_sync();
+  UR_STAMP(ur_load);
   // The order of the updates (class_unrel.c:246-258): a stable sort of ALL intervals by min(cb,ce), of which the loops then
   // skip the fixed ones.  The same order from less work (round 5): the non-fixed intervals first, in index order (ballot +
   // popcount, L at a time), then a stable rank sort of those alone -- rank = keys below mine + equal keys before me, the
@@ -3231,7 +3250,6 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
     { int x = __shfl_xor(maxNF,o); maxNF = x > maxNF ? x : maxNF; }
   wave_sync();
 
-  // role of this lane inside its slot: class (H,D) x side (L,R) x kind (0: max(er,sf), 1: sf_er).
   // The reference updates the non-fixed intervals one after the other (class_unrel.c:260-274), and an
   // update costs one Bessel recurrence of latency.  An update reads the neighbouring intervals' classes
   // and the reliable-H / reliable-D sets, which most updates leave untouched, so the K = L/8 groups of 8
@@ -3253,20 +3271,21 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   // (tests/test_unrel_memo.py runs this rule against the two plain sweeps on the host).  A round of the second sweep
   // looks at the next L order positions, gives its K slots the first K whose bit is set, and ends behind a slot that
   // changes a class (what lies behind may have been skipped on the strength of a bit that slot has just set).
-  constexpr int K = L/8;
-  const int sub = ql >> 3, role = ql & 7, sbase = gbase+sub*8;
-  const int s2 = (role >> 2) & 1, side = (role >> 1) & 1, kind = role & 1;
-  const int s = s2 ? CP_DIPLO : CP_HAPLO;
+  //
+  // A ROUND'S GLOBAL LOADS ARE IN FLIGHT TOGETHER.  A round is one dependent chain, and at four waves per SIMD its length is
+  // the kernel's time.  Every address of a round is known once the slot's LDS fields and bit scans are: the interval's
+  // cold record (pe on every lane, peo_b / peo_e on the lane whose role asks for it), logfact of the two counts (shared
+  // by the E term, the R term and the Poisson fallback), logfact of the R term's other four arguments, and the lane's
+  // Skellam or uerr table entry.  They are issued in that order with nothing waiting in between -- the estimate behind
+  // the uerr address (an FP64 division) is computed while the others are under way -- and the values are selected
+  // afterwards exactly as class_unrel.c does.  A slot without an update forms no address.
   const uint64_t glm = (L == 64) ? ~0ull : ((1ull << L)-1);
   int pass = 0, it = 0;                                    // class_unrel.c:260-274, position of this read
   bool done = (N == 0) || (nnf == 0);
 #ifdef CP_PROF_WALK
   int prof_rounds[2] = { 0, 0 };
-  unsigned long long ur_commit = 0, ur_rest = 0, ur_t = wall_clock64();
-#define UR_STAMP(acc) do { const unsigned long long t_ = wall_clock64(); acc += t_-ur_t; ur_t = t_; } while (0)
-#else
-#define UR_STAMP(acc) ((void)0)
 #endif
+  UR_STAMP(ur_sort);
   while (__ballot(!done) != 0)
       { int mypos = it+sub;                                // order position of this slot's update
         int cover = (it+K < nnf) ? it+K : nnf;             // the round settles the positions [it, cover) if every slot commits
@@ -3292,64 +3311,93 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
         if (act)
           idx = S_ORD(pass == 0 ? nnf-1-mypos : mypos);
         int snew = -1;
-        bool do_sf = false, do_bin = false;
-        int tb = 0, te = 0, tcb = 0, tce = 0, tcov = 0, est = 0, c = 0;
-        int Icb = 0, Ice = 0, lD = -1, rD = -1;
-        double er = -INFINITY;
+        int Icb = 0, Ice = 0, lH = -1, rH = -1, lD = -1, rD = -1;
         if (on)
-          { const int Ib = S.b[g][idx], Ie = S.e[g][idx];
-            Icb = S.cb[g][idx]; Ice = S.ce[g][idx];
+          { Icb = S.cb[g][idx]; Ice = S.ce[g][idx];
             if ((Icb > Ice ? Icb : Ice) >= REP)            // update_state, class_unrel.c:195-199
               { snew = CP_REPEAT;
                 on = false;
               }
             else
-              { const int lH = bits_left(S.rel[g][0],idx), rH = bits_right(S.rel[g][0],idx,nwords);
+              { lH = bits_left(S.rel[g][0],idx); rH = bits_right(S.rel[g][0],idx,nwords);
                 lD = bits_left(S.rel[g][1],idx); rD = bits_right(S.rel[g][1],idx,nwords);
-                const int l_rel = s2 ? lD : lH, r_rel = s2 ? rD : rH;
-                { if (kind == 0)                           // class_unrel.c:123-163, arguments only
-                      { if (side == 0)
-                          { if (idx-1 >= 0 && S.asgn[g][idx-1] == (int8_t)s) er = COMPACT ? soa.b[io+idx].peo_b : intvl[idx].peo_b;
-                            if (l_rel != -1)
-                              { do_sf = true; tb = S.e[g][l_rel]-1; te = Ib; tcb = S.cce[g][l_rel]; tce = Icb; tcov = tcb; }
-                          }
-                        else
-                          { if (idx+1 < N && S.asgn[g][idx+1] == (int8_t)s) er = COMPACT ? soa.b[io+idx].peo_e : intvl[idx].peo_e;
-                            if (r_rel != -1)
-                              { do_sf = true; tb = Ie-1; te = S.b[g][r_rel]; tcb = Ice; tce = S.ccb[g][r_rel]; tcov = tce; }
-                          }
-                      }
-                    else
-                      { const int x = side ? Ie-1 : Ib;
-                        c = side ? Ice : Icb;
-                        // est_cov, class_unrel.c:27-51: this class's neighbours, else the other class's
-                        int ll = l_rel, rr = r_rel, e1 = -1;
-                        for (int rep = 0; rep < 2 && e1 < 0; rep++)
-                          { if (ll != -1 && rr != -1)
-                              e1 = (int)(uint16_t)cp_linear_interpolation(x,S.e[g][ll]-1,S.cce[g][ll],S.b[g][rr],S.ccb[g][rr]);
-                            else if (ll != -1) e1 = S.cce[g][ll];
-                            else if (rr != -1) e1 = S.ccb[g][rr];
-                            if (e1 < 0)
-                              { if (rep == 0) { ll = s2 ? lH : lD; rr = s2 ? rH : rD; }
-                                else e1 = -2;
-                              }
-                            else if (rep == 1)
-                              e1 = (e1 > 0) ? (((s == CP_HAPLO) ? e1/2 : e1*2) & 0xffff) : -2;
-                          }
-                        est = (e1 >= 0) ? e1 : P->cov[s];
-                        do_bin = est >= c;
-                      }
-                  }
               }
           }
+        UR_STAMP(ur_pre);
         // The Skellam term and the binomial term are table look-ups (cp_types.h: skel, uerr; the recurrence / the
         // tail sum only outside the tables), so the second sweep simply evaluates them again: the per-interval memo
         // in HBM that used to carry them from the first sweep cost more than that.
-        double val = -INFINITY;
-        if (do_sf)
-          val = cp_logp_trans(P,tb,te,tcb,tce,tcov);
-        if (do_bin)
-          val = cp_logp_uerr(P,est,c);
+        bool do_sf = false, do_bin = false, in_tab = false, r_in = false;
+        int oa = 0, ob = 0, oc = 0;                        // outside the tables: (ce-cb, cov, d) of the Skellam term, (est, c) of the binomial one
+        int kb = 0, ke = 0, nl = 0, nr = 0;                // the checked counts of the interval and of the R term
+        double er = -INFINITY, val = -INFINITY, pe = 0., lfb = 0., lfe = 0., lfnl = 0., lfdl = 0., lfnr = 0., lfdr = 0.;
+        if (on)
+          { const double *const rec = COMPACT ? &soa.b[io+idx].pe : &intvl[idx].pe;
+            const double *const rec_er = side ? (COMPACT ? &soa.b[io+idx].peo_e : &intvl[idx].peo_e)
+                                              : (COMPACT ? &soa.b[io+idx].peo_b : &intvl[idx].peo_b);
+            const int nb = side ? idx+1 : idx-1;           // class_unrel.c:126,145: the neighbour on this lane's side has class s
+            if (kind == 0 && nb >= 0 && nb < N && S.asgn[g][nb] == (int8_t)s) er = *rec_er;
+            pe = *rec;
+            kb = cp_check_cnt(Icb); ke = cp_check_cnt(Ice);
+            lfb = logfact[kb]; lfe = logfact[ke];
+            { int dcov_l, dcov_r;                          // R, class_unrel.c:53-113
+              if (lD == -1 && rD == -1) dcov_l = dcov_r = covD;
+              else if (lD == -1)        dcov_l = dcov_r = S.cb[g][rD];
+              else if (rD == -1)        dcov_l = dcov_r = S.ce[g][lD];
+              else                      { dcov_l = S.ce[g][lD]; dcov_r = S.cb[g][rD]; }
+              const int rcov_l = (uint16_t)(dr_ratio*dcov_l);
+              const int rcov_r = (uint16_t)(dr_ratio*dcov_r);
+              r_in = !(Icb >= rcov_l || Ice >= rcov_r);
+              if (r_in)                                    // (kb <= nl and ke <= nr: the check is monotone)
+                { nl = cp_check_cnt(rcov_l); nr = cp_check_cnt(rcov_r);
+                  lfnl = logfact[nl]; lfdl = logfact[nl-kb]; lfnr = logfact[nr]; lfdr = logfact[nr-ke];
+                }
+            }
+            const double *at = nullptr;
+            const int Ib = S.b[g][idx], Ie = S.e[g][idx];
+            const int l_rel = s2 ? lD : lH, r_rel = s2 ? rD : rH;
+            if (kind == 0)                                 // class_unrel.c:123-163, arguments only
+              { int tb = 0, te = 0, tcb = 0, tce = 0, tcov = 0;
+                if (side == 0 && l_rel != -1)
+                  { do_sf = true; tb = S.e[g][l_rel]-1; te = Ib; tcb = S.cce[g][l_rel]; tce = Icb; tcov = tcb; }
+                if (side == 1 && r_rel != -1)
+                  { do_sf = true; tb = Ie-1; te = S.b[g][r_rel]; tcb = Ice; tce = S.ccb[g][r_rel]; tcov = tce; }
+                if (do_sf)                                 // cp_logp_trans, its two steps apart
+                  { oa = tce-tcb; ob = tcov & 0xffff; oc = te-tb < 0 ? tb-te : te-tb;
+                    at = cp_logp_trans_at(skel,skel_kmax,skel_cdmax,oc,tcb,tce,ob);
+                  }
+              }
+            else
+              { const int x = side ? Ie-1 : Ib;
+                const int c = side ? Ice : Icb;
+                // est_cov, class_unrel.c:27-51: this class's neighbours, else the other class's
+                int ll = l_rel, rr = r_rel, e1 = -1;
+                for (int rep = 0; rep < 2 && e1 < 0; rep++)
+                  { if (ll != -1 && rr != -1)
+                      e1 = (int)(uint16_t)cp_linear_interpolation(x,S.e[g][ll]-1,S.cce[g][ll],S.b[g][rr],S.ccb[g][rr]);
+                    else if (ll != -1) e1 = S.cce[g][ll];
+                    else if (rr != -1) e1 = S.ccb[g][rr];
+                    if (e1 < 0)
+                      { if (rep == 0) { ll = s2 ? lH : lD; rr = s2 ? rH : rD; }
+                        else e1 = -2;
+                      }
+                    else if (rep == 1)
+                      e1 = (e1 > 0) ? (((s == CP_HAPLO) ? e1/2 : e1*2) & 0xffff) : -2;
+                  }
+                const int est = (e1 >= 0) ? e1 : (s2 ? covD : covH);
+                do_bin = est >= c;
+                if (do_bin)                                // cp_logp_uerr, its two steps apart
+                  { oa = est; ob = c;
+                    at = cp_logp_uerr_at(uerr,uerr_max,est,c);
+                  }
+              }
+            in_tab = at != nullptr;
+            if (in_tab) val = *at;
+          }
+        if (do_sf && !in_tab)
+          val = cp_logp_trans_calc(P,oa,(double)ob*oc);
+        if (do_bin && !in_tab)
+          val = cp_logp_uerr_calc(P,oa,ob);
         if (on)
           { if (kind == 0)
               val = (er > val) ? er : val;
@@ -3357,31 +3405,20 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
             double sidev = (val > v1) ? val : v1;              // MAX(MAX(er,sf),sf_er) on lanes with kind 0
             double vr = __shfl_down(sidev,2);
             double logp_l = sidev, logp_r = vr;                // meaningful on role lanes 0 (H) and 4 (D)
-            if (logp_l == -INFINITY && logp_r == -INFINITY)    // class_unrel.c:165-173
-              { logp_l = cp_logp_poisson(P,Icb,P->cov[s]);
-                logp_r = cp_logp_poisson(P,Ice,P->cov[s]);
+            if (logp_l == -INFINITY && logp_r == -INFINITY)    // class_unrel.c:165-173 (cp_logp_poisson on what is loaded)
+              { logp_l = cp_logp_poisson_vals(kb,s2 ? llD : llH,s2 ? covD : covH,lfb);
+                logp_r = cp_logp_poisson_vals(ke,s2 ? llD : llH,s2 ? covD : covH,lfe);
               }
             else if (logp_l == -INFINITY) logp_l = logp_r;
             else if (logp_r == -INFINITY) logp_r = logp_l;
             const double logp_s = logp_l+logp_r;
             const double vH = __shfl(logp_s,sbase), vD = __shfl(logp_s,sbase+4);
             // E and R are table look-ups (class_unrel.c:53-113)
-            const double pe = COMPACT ? soa.b[io+idx].pe : intvl[idx].pe;
-            const double po = cp_logp_poisson(P,Icb,P->cov[CP_ERROR])+cp_logp_poisson(P,Ice,P->cov[CP_ERROR])+CP_E_PO_BASE;
+            const double po = cp_logp_poisson_vals(kb,llE,covE,lfb)+cp_logp_poisson_vals(ke,llE,covE,lfe)+CP_E_PO_BASE;
             const double vE = (pe > po) ? pe : po;
-            double vR;
-            { int dcov_l, dcov_r;
-              if (lD == -1 && rD == -1) dcov_l = dcov_r = P->cov[CP_DIPLO];
-              else if (lD == -1)        dcov_l = dcov_r = S.cb[g][rD];
-              else if (rD == -1)        dcov_l = dcov_r = S.ce[g][lD];
-              else                      { dcov_l = S.ce[g][lD]; dcov_r = S.cb[g][rD]; }
-              int rcov_l = (uint16_t)(P->dr_ratio*dcov_l);
-              int rcov_r = (uint16_t)(P->dr_ratio*dcov_r);
-              if (Icb >= rcov_l || Ice >= rcov_r)
-                vR = CP_R_LOGP;
-              else
-                vR = cp_logp_binom_pre(P->logfact,Icb,rcov_l,P->r_lp,P->r_l1mp)+cp_logp_binom_pre(P->logfact,Ice,rcov_r,P->r_lp,P->r_l1mp);
-            }
+            double vR = CP_R_LOGP;
+            if (r_in)                                          // cp_logp_binom_pre(logfact,Icb,rcov_l,..)+cp_logp_binom_pre(logfact,Ice,rcov_r,..)
+              vR = cp_logp_binom_vals(lfnl,lfb,lfdl,kb,nl,r_lp,r_l1mp)+cp_logp_binom_vals(lfnr,lfe,lfdr,ke,nr,r_lp,r_l1mp);
             double logpmax = -INFINITY;                        // class_unrel.c:208-218: E,R,H,D with strict <
             if (logpmax < vE) { logpmax = vE; snew = CP_ERROR; }
             if (logpmax < vR) { logpmax = vR; snew = CP_REPEAT; }
@@ -3389,7 +3426,7 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
             if (logpmax < vD) { logpmax = vD; snew = CP_DIPLO; }
           }
         wave_sync();                                           // every slot has read the old state
-        UR_STAMP(ur_rest);
+        UR_STAMP(ur_use);
         // Commit the round's slots in order (every lane of a read computes where the round stops; the slots' lead lanes
         // write).  Serially: slot j is committed unless an earlier slot of the round changed the H-or-D-ness of one of
         // its index neighbours or either reliable set; the round ends at the first slot without an update (the rest of
@@ -3462,8 +3499,8 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
     { atomicAdd(&g_phase_sum[9],(unsigned long long)prof_rounds[0]); atomicAdd(&g_phase_max[9],(unsigned long long)prof_rounds[1]);
       atomicAdd(&g_phase_sum[10],(unsigned long long)nnf); atomicAdd(&g_phase_sum[11],1ull); }
   if (lane == 0 && MINN == 0)
-    { UR_STAMP(ur_rest);
-      atomicAdd(&g_unrel_prof[0],ur_commit); atomicAdd(&g_unrel_prof[1],ur_rest);
+    { atomicAdd(&g_unrel_prof[0],ur_commit); atomicAdd(&g_unrel_prof[1],ur_pre); atomicAdd(&g_unrel_prof[4],ur_use);
+      atomicAdd(&g_unrel_prof[5],ur_load); atomicAdd(&g_unrel_prof[6],ur_sort);
       atomicAdd(&g_unrel_prof[2],wall_clock64()-ur_t0); atomicAdd(&g_unrel_prof[3],1ull); }
 #endif
 #undef UR_STAMP

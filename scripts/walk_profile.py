@@ -27,7 +27,7 @@ clf = Classifier(40, 20000, hc, dc)
 ph = (C.c_ulonglong * 36)()
 lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
-ur = (C.c_ulonglong * 4)()
+ur = (C.c_ulonglong * 8)()
 rp = (C.c_ulonglong * 12)()
 clf.classify(b)
 lib().cp_debug_unrel_prof(ur)
@@ -52,8 +52,12 @@ print("E-interval lists of at most 64 (the wave-parallel forms): before the un-w
       % (em[0], em[1] / b.nreads, em[2], em[3] / b.nreads, em[4], em[5] / b.nreads))
 print("classify_unrel (main class): %.1f non-fixed intervals per read, %.1f speculation rounds in the first sweep (four slots per round), %.1f in the second"
       % (ph[12 + 10] / max(1, ph[12 + 11]), ph[12 + 9] / max(1, ph[12 + 11]), ph[9] / max(1, ph[12 + 11])))
-print("classify_unrel (main class): %d waves, %.1f ticks per wave: committing the slots %.1f (%.1f %% of the wave time), the rest of the rounds %.1f, before and behind the rounds %.1f"
-      % (ur[3], ur[2] / max(1, ur[3]), ur[0] / max(1, ur[3]), 100.0 * ur[0] / max(1, ur[2]), ur[1] / max(1, ur[3]), (ur[2] - ur[0] - ur[1]) / max(1, ur[3])))
+nw, tot = max(1, ur[3]), max(1, ur[2])
+print("classify_unrel (main class): %d waves, %.1f ticks per wave" % (ur[3], ur[2] / nw))
+for name, v in (("interval load before the rounds", ur[5]), ("sort of the non-fixed intervals", ur[6]),
+                ("round: up to the first global load issued", ur[1]), ("round: waiting for the loads and using them", ur[4]),
+                ("round: committing the slots", ur[0]), ("head and final write", ur[2] - ur[0] - ur[1] - ur[4] - ur[5] - ur[6])):
+    print("    %-46s %9.1f ticks per wave  %5.1f %%" % (name, v / nw, 100.0 * v / tot))
 print("classify_rel: %d of %d (read, direction) passes are repeated with adjusted coverages (class_rel.c:629-650); %d of %d waves run the DP a second time"
       % (em[6] & 0xffffffff, em[6] >> 32, em[7] & 0xffffffff, em[7] >> 32))
 if rp[9]:
