@@ -30,6 +30,7 @@ SYMBOLS = [
     "cp_kmer_sorted_combine", "cp_kmer_sorted_hist",
     "cp_kmer_sorted_read_hits", "cp_bin_call",
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
+    "cp_kmer_sorted_het_pairs",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -173,6 +174,7 @@ def lib():
     L.cp_bin_call.argtypes = [vp, i64, i64, i64, i32]
     L.cp_kmer_sorted_compare_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.cp_kmer_qv.argtypes = [i32, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.cp_kmer_sorted_het_pairs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
     L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -840,6 +840,43 @@ class SortedKmers:
                                                      _stream_of(self.device)))
         return mat
 
+    _HET_TALLY = ("keys", "paired", "multi", "pairs", "unique", "out")
+
+    def het_pairs(self, xmax=1000, ymax=1000, unique=True, count_range=None, degrees=False, table=False):
+        """cp_kmer_sorted_het_pairs ("Heterozygous pairs of sorted k-mers" in include/classpro_amd.h): the pairs of keys
+        of this snapshot that differ only at the centre base.  Returns (matrix, tally): a numpy int64 [xmax+1, ymax+1]
+        whose cell [a, b] counts the pairs with min(smaller count, xmax) == a and min(larger count, ymax) == b -- the
+        unique pairs (both members have no other partner) with unique=True, every pair otherwise -- and a dict with
+        "keys", "paired", "multi", "pairs", "unique" and "out".  `count_range` is (lo, hi) as in `combine`: a key outside
+        it counts as absent.  degrees=True appends the degree of every entry as a uint8 device tensor, table=True a
+        new `SortedKmers` of the members of the counted pairs, which keeps no reference to this one."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        xmax, ymax = int(xmax), int(ymax)
+        if not (1 <= xmax <= 32767 and 1 <= ymax <= 32767 and (xmax + 1) * (ymax + 1) <= 1 << 22):
+            raise ValueError("xmax and ymax must lie in [1, 32767] and span at most 2^22 cells")
+        rng = None
+        if count_range is not None:
+            lo, hi = count_range
+            rng = (C.c_int64 * 2)(1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi))
+        mat = np.zeros((xmax + 1, ymax + 1), np.int64)
+        tally = (C.c_int64 * 6)()
+        deg = torch.zeros(self.n, dtype=torch.uint8, device=self.device) if degrees else None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_het_pairs(self.s, rng, 1 if unique else 0, xmax, ymax, mat.ctypes.data, tally,
+                                                  deg.data_ptr() if degrees and self.n else None, _stream_of(self.device),
+                                                  C.byref(h) if table else None))
+        res = [mat, dict(zip(self._HET_TALLY, tally))]
+        if degrees:
+            res.append(deg)
+        if table:
+            out = SortedKmers.__new__(SortedKmers)
+            out.L, out.device, out.K = self.L, self.device, self.K
+            out._adopt(h)
+            res.append(out)
+        return tuple(res)
+
     def hist(self):
         """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
         (1, 32767, ilowcnt, ihighcnt, int64[32767])."""

@@ -1182,5 +1182,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // 2-D count comparison of two sorted snapshots and the k-mer QV (tabcmp): kmer_cmphist.hip
 #include "kmer_cmphist.hip"
 
+// heterozygous k-mer pairs of one sorted snapshot (tabhet): kmer_hetpairs.hip
+#include "kmer_hetpairs.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

@@ -56,6 +56,39 @@ __global__ void __launch_bounds__(KT_BLOCK) so_cut_kernel(so_view a, so_view b, 
     }
 }
 
+// The kept entries of a tile from LDS to their places base.. of the result by coalesced 8-byte stores: entry i of the nk
+// is slot at(i) of (shi, slo, scn).  A run of one bucket adds its length to cnt_of[bucket] by at most two 64-bit atomics
+// (minus its first place, plus one past its last; per_entry: one atomic per entry instead).  Shared with kmer_hetpairs.hip.
+template <bool HI, class AT>
+__device__ static inline void so_store_kept(const unsigned long long *shi, const unsigned long long *slo,
+                                            const unsigned long long *scn, AT at, int nk, int64_t base,
+                                            unsigned long long *ohi, unsigned long long *olo, unsigned long long *ocn,
+                                            int64_t on, unsigned long long *cnt_of, int64_t nb, int shift, bool per_entry)
+{ for (int i = threadIdx.x; i < nk; i += KS_BLOCK)
+    { const int s = at(i);
+      const int64_t g = base+i;
+      if ((unsigned long long)g >= (unsigned long long)on) continue;    // cannot happen while the operands are only read
+      const unsigned long long kh = HI ? shi[s] : 0, kl = slo[s];
+      if (HI) ohi[g] = kh; else ohi[g] = 0;
+      olo[g] = kl;
+      ocn[g] = scn[s];
+      const unsigned long long bk = ks_bucket(kh,kl,shift);
+      if (bk >= (unsigned long long)nb) continue;
+      bool head = per_entry || i == 0, tail = per_entry || i == nk-1;
+      if (!head)
+        { const int p = at(i-1);
+          head = ks_bucket(HI ? shi[p] : 0,slo[p],shift) != bk;
+        }
+      if (!tail)
+        { const int p = at(i+1);
+          tail = ks_bucket(HI ? shi[p] : 0,slo[p],shift) != bk;
+        }
+      if (head && tail) atomicAdd(&cnt_of[bk],1ull);
+      else if (head) atomicAdd(&cnt_of[bk],0ull-(unsigned long long)g);      // the sums wrap to the run's length
+      else if (tail) atomicAdd(&cnt_of[bk],(unsigned long long)g+1);
+    }
+}
+
 // WRITE = false: tile_n[t] = the kept entries of tile t, tally += only in A, only in B, in both.
 // WRITE = true: tile_n holds the inclusive sums of those; the kept entries go to their places in (ohi, olo, ocn) and
 // the bucket counters cnt_of[bucket] take the run lengths.
@@ -140,30 +173,8 @@ __global__ void __launch_bounds__(KS_BLOCK) so_tile_kernel(so_view a, so_view b,
     }
   __syncthreads();
   const int nk = (int)min(part[KS_BLOCK-1],(unsigned long long)SO_CAP);
-  const int64_t base = t ? tile_n[t-1] : 0;
-  for (int i = threadIdx.x; i < nk; i += KS_BLOCK)
-    { const int s = min((int)pack[i],SO_CAP-1);
-      const int64_t g = base+i;
-      if ((unsigned long long)g >= (unsigned long long)on) continue;    // cannot happen while the operands are only read
-      const unsigned long long kh = HI ? shi[s] : 0, kl = slo[s];
-      if (HI) ohi[g] = kh; else ohi[g] = 0;
-      olo[g] = kl;
-      ocn[g] = scn[s];
-      const unsigned long long bk = ks_bucket(kh,kl,shift);
-      if (bk >= (unsigned long long)nb) continue;
-      bool head = per_entry || i == 0, tail = per_entry || i == nk-1;
-      if (!head)
-        { const int p = min((int)pack[i-1],SO_CAP-1);
-          head = ks_bucket(HI ? shi[p] : 0,slo[p],shift) != bk;
-        }
-      if (!tail)
-        { const int p = min((int)pack[i+1],SO_CAP-1);
-          tail = ks_bucket(HI ? shi[p] : 0,slo[p],shift) != bk;
-        }
-      if (head && tail) atomicAdd(&cnt_of[bk],1ull);
-      else if (head) atomicAdd(&cnt_of[bk],0ull-(unsigned long long)g);      // the sums wrap to the run's length
-      else if (tail) atomicAdd(&cnt_of[bk],(unsigned long long)g+1);
-    }
+  so_store_kept<HI>(shi,slo,scn,[&](int i) { return min((int)pack[i],SO_CAP-1); },nk,t ? tile_n[t-1] : 0,ohi,olo,ocn,on,cnt_of,
+                    nb,shift,per_entry);
 }
 
 // the layout of kc_hist_kernel over the counts of a snapshot
@@ -198,6 +209,16 @@ static void so_scan(int64_t *v, int64_t n, unsigned long long *sum, hipStream_t 
   ks_chunk_sum_kernel<<<nchunk,KS_BLOCK,0,st>>>(v,n,sum);
   ks_sum_scan_kernel<<<1,KS_BLOCK,0,st>>>(sum,nchunk);
   ks_chunk_scan_kernel<<<nchunk,KS_BLOCK,0,st>>>(v,n,sum);
+}
+
+// the memory of a result of n_out entries: its bucket counters, zeroed, and its entries (none for an empty result)
+static int so_result_alloc(const char *who, cp_kmer_sorted *s, int64_t n_out, hipStream_t st)
+{ int rc = ks_alloc(who,(void **)&s->start,(size_t)(s->nb+1)*8,"the bucket starts");
+  if (rc != CP_OK) return rc;
+  HIPCHK(hipMemsetAsync(s->start,0,(size_t)(s->nb+1)*8,st));
+  s->n = n_out;
+  if (n_out > 0) rc = ks_alloc(who,(void **)&s->key,(size_t)n_out*24,"the result's entries");
+  return rc;
 }
 
 // the two passes; scratch and the result's memory are freed by the caller when this fails
@@ -238,14 +259,10 @@ static int so_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b, const so
       tally[3] = n_out;
     }
   if (!s) return CP_OK;
-  rc = ks_alloc(who,(void **)&s->start,(size_t)(s->nb+1)*8,"the bucket starts");
+  rc = so_result_alloc(who,s,n_out,st);
   if (rc != CP_OK) return rc;
-  HIPCHK(hipMemsetAsync(s->start,0,(size_t)(s->nb+1)*8,st));
-  s->n = n_out;
   if (n_out > 0)
-    { rc = ks_alloc(who,(void **)&s->key,(size_t)n_out*24,"the result's entries");
-      if (rc != CP_OK) return rc;
-      unsigned long long *hi = s->key, *lo = s->key+n_out, *cnt = s->key+2*n_out;
+    { unsigned long long *hi = s->key, *lo = s->key+n_out, *cnt = s->key+2*n_out;
       unsigned long long *cnt_of = (unsigned long long *)s->start+1;       // start[p+1] counts bucket p, then ends it
       const int shift = 2*s->K-s->pbits;
       if (with_hi)

@@ -688,6 +688,56 @@ int     cp_kmer_sorted_compare_hist(const cp_kmer_sorted *a, const cp_kmer_sorte
 int     cp_kmer_qv(int K, int64_t a_only, int64_t a_total, double *qv, double *err);
 
 /* ------------------------------------------------------------------------------------------
+ * Heterozygous pairs of sorted k-mers (tabhet): every key of ONE snapshot paired with the keys that differ from it only at
+ * the centre base, and the 2-D histogram of the two counts of such pairs -- the first step of Smudgeplot and of FASTK's
+ * PloidyPlot, which gives ploidy and heterozygosity from the reads alone.  The pairing rule for even K is this library's
+ * own, chosen to be strand-symmetric.  Everything is in integers and independent of grid, block size and scheduling.
+ *
+ *   In         a key is IN when lo <= cnt <= hi with the snapshot's own d_cnt; `range` is a HOST array lo hi, NULL means
+ *              [1, INT64_MAX].  A key outside the range is treated exactly as if it were absent.
+ *   Siblings   positions are 0-based from the first (most significant) base; m = K/2 rounded down and m' = K-1-m (m' = m
+ *              for odd K, m-1 for even K).  The candidates of an in key X are the canonical forms (the minimum of a k-mer
+ *              and its reverse complement) of X with one base replaced at position m or at position m', X itself and
+ *              repeats removed: at most 3 for odd K, at most 6 for even K.  Y is a sibling of X when it is a candidate of X
+ *              and is in.  Equivalently some orientation of X and some orientation of Y differ at position m and nowhere
+ *              else; the relation is symmetric.  The keys are taken to be canonical, as every table of `kprof -t` is.
+ *   Degree     deg(X) = the number of siblings of X, 0 for a key that is not in.
+ *   Pair       an unordered {X, Y} of siblings, counted once; UNIQUE when deg(X) = deg(Y) = 1.  For even K a component
+ *              need not be a clique: AACA ~ AAAA ~ ACAA at K = 4, but AACA and ACAA are no siblings.
+ *   Cell       a counted pair has a = min(cntX, cntY) and b = max(cntX, cntY) of the exact 64-bit d_cnt and adds 1 to
+ *              mat[min(a, xmax)*(ymax+1) + min(b, ymax)].  Row 0 and column 0 stay 0.  `unique` non-zero counts the
+ *              unique pairs only (Smudgeplot's choice), 0 every pair.  `mat` is a HOST array and is overwritten.
+ *   Tally      HOST int64 [CP_HET_WIDTH]: CP_HET_KEYS the in keys, CP_HET_PAIRED the keys with deg >= 1, CP_HET_MULTI
+ *              those with deg >= 2, CP_HET_PAIRS all pairs (the sum of the degrees / 2), CP_HET_UNIQUE the unique pairs,
+ *              CP_HET_OUT the size of the result under the mode.  The first five do not depend on `unique`.
+ *   d_deg      a DEVICE array of `size` bytes, overwritten with the degrees (at most 6).
+ *   out        an ordinary ready cp_kmer_sorted of the keys that are members of a counted pair under the mode, ascending,
+ *              each with its own count.  It owns its memory and its bucket starts are rebuilt, so every query and
+ *              cp_kmer_sorted_combine take it; an empty result has size 0 and null arrays.  To be destroyed by the caller.
+ *   Operand    ready, any K a snapshot can have (2..63), any size.  It is only read.  Lookups are those of "Sorted k-mers
+ *              as input": clamped ranges, at most 64 probes.
+ *   Errors     all before any launch: CP_EINVAL for a NULL s, an unready snapshot, mat, tally, d_deg and out all NULL, a
+ *              range with lo < 1 or hi < lo, and -- when mat is given -- xmax or ymax outside [1, 32767] or
+ *              (xmax+1)*(ymax+1) > 2^22, and -- when out is given -- a snapshot of more than 2^24 tiles of
+ *              cp_ktab_tile() entries.  An allocation that fails is CP_ENOMEM with the byte count in the message,
+ *              nothing leaked.  After any error the contents of mat, tally and d_deg are unspecified.  Synchronises
+ *              `stream`.
+ *   Memory     one byte per entry (none when d_deg is given: it serves as that scratch), the matrix, and with `out` 8
+ *              bytes per tile of cp_ktab_tile() entries; then the result itself.
+ *   Knobs      read per call from the environment, for measurements and tests: CLASSPRO_HET_LDS=0 sends every cell
+ *              straight to the matrix in device memory instead of summing the low corner on chip; CLASSPRO_HET_STAGE=1
+ *              (0) selects (deselects) the staged form, in which a block holds its tile of cp_ktab_tile() consecutive
+ *              entries on chip and resolves the candidates that fall inside the tile there.  Neither changes a result.
+ */
+enum { CP_HET_KEYS = 0, CP_HET_PAIRED = 1, CP_HET_MULTI = 2, CP_HET_PAIRS = 3, CP_HET_UNIQUE = 4, CP_HET_OUT = 5, CP_HET_WIDTH = 6 };
+int     cp_kmer_sorted_het_pairs(const cp_kmer_sorted *s, const int64_t *range /* host [2]: lo hi, or NULL */,
+                                 int unique, int xmax, int ymax,
+                                 int64_t *mat /* host [(xmax+1)*(ymax+1)], overwritten, or NULL */,
+                                 int64_t *tally /* host [CP_HET_WIDTH], or NULL */,
+                                 uint8_t *d_deg /* device [size], overwritten, or NULL */,
+                                 void *stream, cp_kmer_sorted **out /* or NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
