@@ -29,6 +29,7 @@ SYMBOLS = [
     "cp_kmer_sorted_profiles",
     "cp_kmer_sorted_combine", "cp_kmer_sorted_hist",
     "cp_kmer_sorted_read_hits", "cp_bin_call",
+    "cp_kmer_sorted_read_runs", "cp_run_blocks",
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
     "cp_kmer_sorted_het_pairs",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
@@ -63,6 +64,10 @@ class AccStats(C.Structure):
                 ("ntot_normal", C.c_int64), ("ncor_normal", C.c_int64), ("nfne_normal", C.c_int64),
                 ("ntot_repeat", C.c_int64), ("ncor_repeat", C.c_int64), ("nfne_repeat", C.c_int64),
                 ("n_reads", C.c_int64), ("n_reads_filtered", C.c_int64), ("n_invalid", C.c_int64)]
+
+
+# the error codes of include/classpro_amd.h
+CP_OK, CP_EINVAL, CP_ENOPEAK, CP_ERCOV, CP_EHIP, CP_EOVERFLOW, CP_ENOMEM = 0, -1, -2, -3, -4, -5, -6
 
 
 class ClassProError(RuntimeError):
@@ -172,6 +177,9 @@ def lib():
     L.cp_kmer_sorted_hist.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     L.cp_kmer_sorted_read_hits.argtypes = [vp, vp, i32, vp, vp, vp, i32, i64, vp, vp]
     L.cp_bin_call.argtypes = [vp, i64, i64, i64, i32]
+    L.cp_kmer_sorted_read_runs.argtypes = [vp, vp, i32, vp, C.c_uint, C.c_uint, vp, vp, i32, i64, vp, i64, vp, C.POINTER(i64), vp]
+    L.cp_run_blocks.argtypes = [vp, i64, i64, vp, C.POINTER(i64)]
+    L.cp_run_blocks.restype = i64
     L.cp_kmer_sorted_compare_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.cp_kmer_qv.argtypes = [i32, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.cp_kmer_sorted_het_pairs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]

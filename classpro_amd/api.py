@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import CP_EOVERFLOW, lib, check
 
 STAGE_SCAN, STAGE_WALL, STAGE_REL, STAGE_CLASS_REL, STAGE_CLASS_ALL, STAGE_LABELS = 1, 2, 3, 4, 5, 6
 
@@ -811,6 +811,49 @@ class SortedKmers:
                                                   hits.data_ptr() if n > 0 else None, _stream_of(self.device)))
         return hits
 
+    RUN_NONE, RUN_A, RUN_B, RUN_BOTH, RUN_OTHER = 1, 2, 4, 8, 16      # the bits of `skip` and `emit`: 1 << state
+
+    def read_runs(self, other, batch, skip=0, emit=None, canonical=True, a_range=None, b_range=None):
+        """cp_kmer_sorted_read_runs ("Runs of k-mer states along reads" in include/classpro_amd.h): the k-mer positions of
+        a `Batch` or of a tuple of device tensors (seq uint8, seq_off int64 [n+1]) looked up in this snapshot (A) and in
+        `other` (B, or None for no second table) and reduced to runs of equal state on the device.  `skip` and `emit`
+        are masks of 1 << state (states 0 none, 1 A, 2 B, 3 both, 4 other byte); positions in `skip` are transparent, runs
+        outside `emit` (default: every state not skipped) are not returned.  Returns (run_off, runs): run_off an int64
+        device tensor [n+1], the runs of read r being records run_off[r] .. run_off[r+1]; runs a dict of device tensors
+        "first", "last", "n" (int64) and "read", "state" (int32).  One call with a guessed capacity, one more at the exact
+        size when that was too small."""
+        if other is not None and not isinstance(other, SortedKmers):
+            raise ValueError("the other operand must be a SortedKmers or None")
+        if self.s is None or (other is not None and other.s is None):
+            raise ValueError("SortedKmers is closed")
+        if other is not None and (other.K != self.K or other.device != self.device):
+            raise ValueError("the operands must hold k-mers of the same length on the same device")
+        skip = int(skip)
+        emit = 0x1f & ~skip if emit is None else int(emit)
+        if isinstance(batch, Batch):
+            seq, seq_off, n, total = batch.seq, batch.seq_off, batch.nreads, batch.total_bases
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+        run_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=self.device)
+        capacity = max(1024, total // 16)
+        count = C.c_int64()
+        with torch.cuda.device(self.device):
+            for _ in range(2):
+                buf = torch.empty((capacity, 4), dtype=torch.int64, device=self.device)
+                rc = self.L.cp_kmer_sorted_read_runs(self.s, other.s if other is not None else None, 1 if canonical else 0,
+                                                     self._range4(a_range, b_range), skip, emit, seq.data_ptr(),
+                                                     seq_off.data_ptr(), n, total, buf.data_ptr(), capacity,
+                                                     run_off.data_ptr(), C.byref(count), _stream_of(self.device))
+                if rc != CP_EOVERFLOW:                     # count is exact: once more at that size
+                    break
+                capacity = count.value
+            check(rc)
+        buf = buf[:count.value]
+        tail = buf.view(torch.int32)[:, 6:]
+        return run_off, {"first": buf[:, 0], "last": buf[:, 1], "n": buf[:, 2], "read": tail[:, 0], "state": tail[:, 1]}
+
     def compare(self, other, a_range=None, b_range=None):
         """(only_a, only_b, both): the tally of `combine` with nothing built (cp_kmer_sorted_combine with out == NULL)."""
         return self._combine(other, "and", "left", a_range, b_range, False)[1][:3]
@@ -911,6 +954,25 @@ def bin_calls(hits, only_a, only_b, min_markers=1, normalise=True):
     for i in range(len(h)):
         out[i] = check(L.cp_bin_call(h[i].ctypes.data, int(only_a), int(only_b), int(min_markers), 1 if normalise else 0))
     return bytes(out)
+
+
+RUN_DTYPE = np.dtype([("first", np.int64), ("last", np.int64), ("n", np.int64), ("read", np.int32), ("state", np.int32)])
+
+
+def run_blocks(runs, min_n=1):
+    """cp_run_blocks: the runs of ONE read, every state that is not skipped emitted, as a list of (first, last, n, read,
+    state) tuples or the dict of `SortedKmers.read_runs` cut to that read.  Runs with n < min_n are dropped, neighbours of
+    equal state among the rest are merged.  Returns (blocks, dropped): a list of such tuples and the number of dropped
+    runs."""
+    if isinstance(runs, dict):
+        cols = [runs[k].cpu().numpy() if isinstance(runs[k], torch.Tensor) else np.asarray(runs[k]) for k in RUN_DTYPE.names]
+        runs = list(zip(*[c.tolist() for c in cols]))
+    arr = np.array([tuple(int(x) for x in r) for r in runs], RUN_DTYPE).reshape(-1)
+    out = np.zeros(max(len(arr), 1), RUN_DTYPE)
+    dropped = C.c_int64()
+    nb = check(lib().cp_run_blocks(arr.ctypes.data if len(arr) else out.ctypes.data, len(arr), int(min_n), out.ctypes.data,
+                                   C.byref(dropped)))
+    return [tuple(int(x) for x in b) for b in out[:nb].tolist()], dropped.value
 
 
 def kmer_qv(K, a_only, a_total):

@@ -1176,6 +1176,9 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // read hits in two sorted snapshots and the bin call of a read (tabbin): kmer_hits.hip
 #include "kmer_hits.hip"
 
+// runs of k-mer states along reads and the blocks of a read's runs (tabtrack): kmer_runs.hip
+#include "kmer_runs.hip"
+
 // set algebra on sorted snapshots and the histogram of one (tabop): kmer_setops.hip
 #include "kmer_setops.hip"
 

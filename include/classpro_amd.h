@@ -649,6 +649,65 @@ int     cp_bin_call(const int64_t *hit /* [CP_HIT_WIDTH] */, int64_t only_a, int
                     int normalise);
 
 /* ------------------------------------------------------------------------------------------
+ * Runs of k-mer states along reads (tabtrack): the k-mer positions of a batch in the flat layout above, looked up in one
+ * or two snapshots and reduced to runs of equal state on the device -- WHERE along a read or a contig the k-mers are that
+ * a table does not hold (the intervals of an assembly that the reads do not support, the errors of a read), and where the
+ * A and B markers of "Read hits in two sorted k-mer sets" form phase blocks.  Only the runs come down, never a value per
+ * base.  Every key is rolled once and looked up once per snapshot.  Everything is in integers.
+ *
+ *   State      of a k-mer position: the marker of cp_kmer_sorted_read_hits, with the same key choice (`canonical`), the
+ *              same presence rule and the same HOST `range` a_min a_max b_min b_max (NULL: [1, INT64_MAX] for both).
+ *              CP_RUN_NONE a key in neither, CP_RUN_A in A and not in B, CP_RUN_B in B and not in A, CP_RUN_BOTH in both,
+ *              CP_RUN_OTHER a k-mer that holds a byte other than upper-case A C G T.  b == NULL means no second table:
+ *              the states are NONE, A and OTHER only, and a key is looked up once.
+ *   Run        `skip` and `emit` are masks over the states, bit 1 << state.  A position whose state is in `skip` is
+ *              transparent: it neither breaks nor extends anything.  Of the other positions of ONE read, in order, a run is
+ *              a maximal stretch of equal state.  Its record: `first` and `last` the ordinals in the read of its first and
+ *              last position (k-mer i covers the bases [i, i+K) of the read), `n` the number of its positions (with
+ *              skip == 0, n == last-first+1), `read` the read's index in the batch, `state`.  A run whose state is not in
+ *              `emit` is not written, but still separates its neighbours.
+ *   Output     d_run_off[r] .. d_run_off[r+1] are the records of read r in d_runs, ascending in `first`; all nreads+1
+ *              offsets are overwritten, and *total (HOST) = d_run_off[nreads].  Reads shorter than K, empty reads and
+ *              nreads == 0 give no runs and are no error.
+ *   Capacity   d_runs holds `capacity` records.  With *total > capacity the call returns CP_EOVERFLOW; d_run_off and
+ *              *total are exact all the same, the records below `capacity` are written and nothing beyond them is touched.
+ *              d_runs == NULL with capacity == 0 is the counting call.
+ *   Fixed      the records of a read are a function of the read, the snapshots, the ranges and the masks alone: not of what
+ *              else is in the batch, of the order of the reads, or of the grid, block and chunk sizes of the kernels.
+ *   Operands   ready and of the same K; a == b is legal, so is a snapshot of size 0.  Both are only read.  Lookups are
+ *              those of "Sorted k-mers as input": clamped ranges, at most 64 probes.
+ *   Errors     all before any launch: CP_EINVAL for a NULL a or total, an unready snapshot, differing K, a range with
+ *              min < 1 or max < min, emit == 0, emit & skip != 0, a mask above 0x1f, a negative nreads, total_bases or
+ *              capacity, a null device pointer where there is work (d_runs with capacity > 0, d_run_off and d_seq_off
+ *              with nreads > 0, d_seq with total_bases > 0).
+ *   Memory     scratch of one byte per base of the batch and 32 bytes per 16384 bases, allocated and freed in stream
+ *              order per call; when that fails it is CP_ENOMEM with the byte count in the message.
+ *              Nothing is queued on `stream` before that allocation has succeeded.
+ *   Cost       one pass of lookups and two light passes over the state bytes.  The offsets of a stretch of reads without a
+ *              k-mer position (shorter than K, or empty) are stored one after the other by the one lane that meets the
+ *              next read, and a read's last run is closed by one binary search over d_seq_off: nothing for reads and
+ *              contigs, but a batch of millions of reads shorter than K is serialised in single lanes.
+ * Synchronises `stream`: the total must be known to return it.
+ *
+ * cp_run_blocks is the one rule by which the runs of ONE read -- every state that is not skipped emitted -- become blocks;
+ * host only, no device involved.  The runs with n < min_n are dropped; of those that are left, neighbours of equal state
+ * are merged into one block: `first` of the first, `last` of the last, n summed, `read` and `state` of the first.  It
+ * writes the blocks in order (at most nruns; `blocks` may be `runs`), sets *dropped to the number of dropped runs and
+ * returns the number of blocks.  The rule is this library's own, not Merqury's, which tolerates switches within a
+ * distance.  CP_EINVAL for a NULL runs, blocks or dropped, min_n < 1 or a negative nruns.
+ */
+enum { CP_RUN_NONE = 0, CP_RUN_A = 1, CP_RUN_B = 2, CP_RUN_BOTH = 3, CP_RUN_OTHER = 4 };
+typedef struct cp_kmer_run { int64_t first, last, n; int32_t read, state; } cp_kmer_run;
+int     cp_kmer_sorted_read_runs(const cp_kmer_sorted *a, const cp_kmer_sorted *b /* or NULL */, int canonical,
+                                 const int64_t *range /* host [4]: a_min a_max b_min b_max, or NULL */,
+                                 unsigned int skip, unsigned int emit,
+                                 const char *d_seq, const int64_t *d_seq_off, int nreads, int64_t total_bases,
+                                 cp_kmer_run *d_runs /* device [capacity], or NULL */, int64_t capacity,
+                                 int64_t *d_run_off /* device [nreads+1], overwritten */, int64_t *total /* host */,
+                                 void *stream);
+int64_t cp_run_blocks(const cp_kmer_run *runs, int64_t nruns, int64_t min_n, cp_kmer_run *blocks, int64_t *dropped);
+
+/* ------------------------------------------------------------------------------------------
  * Count comparison of sorted k-mers (tabcmp): the joint distribution of the counts that two snapshots give one key -- the
  * matrix of KAT's comp and the spectra-cn of Merqury (the read-count spectrum split by the copy number in an assembly) --
  * by the streaming merge of "Set algebra on sorted k-mers", and the k-mer QV that follows from it.  Everything on the
