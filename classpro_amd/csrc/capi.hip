@@ -1136,14 +1136,31 @@ static int prof_read(unsigned long long *out, const void *sym, size_t n, bool re
 extern "C" int cp_debug_seed_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_seed_prof),8); }
 #endif
-#ifdef CP_PROF_WALK
-// diagnostic builds only: per read (candidates, tasks, SELF tasks, overflow) as k_wall_tasks left them (scripts/count_dist.py)
+// Every build, but not part of the public interface (tests/test_gpu_wall_paths.py, scripts/count_dist.py): per read
+// (candidates, tasks, SELF tasks, overflow) as k_wall_tasks left them for k_find_wall, after a call that ran STAGE_WALL.
 extern "C" int cp_debug_task_counts(cp_workspace *ws, int32_t *out, int64_t nreads)
-{ if (!ws || nreads > ws->nreads) return set_err(CP_EINVAL,"cp_debug_task_counts: bad arguments");
+{ if (!ws || !out || nreads < 0 || nreads > ws->nreads || ws->b.fwc.cap < (size_t)nreads*16)
+    return set_err(CP_EINVAL,"cp_debug_task_counts: bad arguments");
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out,ws->b.fwc.p,(size_t)nreads*4*sizeof(int32_t),hipMemcpyDeviceToHost));
+  if (nreads > 0) HIPCHK(hipMemcpy(out,ws->b.fwc.p,(size_t)nreads*4*sizeof(int32_t),hipMemcpyDeviceToHost));
   return CP_OK;
 }
+// The same standing: how many bytes of the two flag arrays of the wall stage (whole buffers) are not zero.  Between calls
+// it is none: the arrays are zeroed when they are allocated and every read clears what it wrote (k_find_wall's last step).
+extern "C" int cp_debug_flag_bytes(cp_workspace *ws, int64_t *out2)
+{ if (!ws || !out2) return set_err(CP_EINVAL,"cp_debug_flag_bytes: bad arguments");
+  HIPCHK(hipDeviceSynchronize());
+  const dbuf *arr[2] = { &ws->b.wall, &ws->b.wall_s };
+  for (int a = 0; a < 2; a++)
+    { std::vector<uint8_t> h(arr[a]->cap);
+      if (arr[a]->cap) HIPCHK(hipMemcpy(h.data(),arr[a]->p,arr[a]->cap,hipMemcpyDeviceToHost));
+      int64_t n = 0;
+      for (uint8_t v : h) n += v != 0;
+      out2[a] = n;
+    }
+  return CP_OK;
+}
+#ifdef CP_PROF_WALK
 // per-phase wave times of k_find_wall (max / sum / arg-max over reads), then reset
 extern "C" int cp_debug_live_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_live_prof),8); }

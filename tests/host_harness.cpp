@@ -76,31 +76,62 @@ static void sort_e(cp_eintvl *v, int n)
 
 static thread_local std::vector<cp_intvl> g_pre_unrel;
 
-// Sequential orchestration of the scalar device functions for one read (mirrors what the kernels do
-// with lanes).  Returns N or -1 on list overflow.
-int hh_classify_read(void *Pv, const char *seq, int rlen, const uint16_t *prof, char *labels,
-                     cp_intvl *intvl, int cap, int *M_out, cp_intvl *rintvl, int8_t *fw, int8_t *bw)
-{ const cp_dev_params *P = (const cp_dev_params *)Pv;
-  const int K = P->K, plen = rlen-(K-1);
-  for (int i = 0; i < K-1 && i < rlen; i++) labels[i] = 'N';
-  if (plen <= 0) return 0;
-  std::vector<uint8_t> wall(plen+1,0);
-  std::vector<double> perror((size_t)(plen+1)*4,-INFINITY);
-  int ecap = 16*plen+64;
-  std::vector<cp_eintvl> ev(ecap), ov(ecap);
-  cp_read_t<cp_perr_dense> R;
-  R.P = P; R.prof = prof; R.seq = seq; R.lf = P->logfact; R.plen = plen; R.rlen = rlen;
-  R.wall = wall.data(); R.wall_s = wall.data(); R.perror.a = perror.data();
-  R.eintvl = ev.data(); R.ointvl = ov.data();
-  R.ecap = ecap; R.eidx = R.oidx = 0; R.overflow = 0;
+// One read's buffers and the view of it that the scalar device functions take (dense perror memo, the two flag
+// arrays as one, lists of 16*plen+64 slots).
+struct hh_read
+  { std::vector<uint8_t> wall;
+    std::vector<double> perror;
+    std::vector<cp_eintvl> ev, ov;
+    cp_read_t<cp_perr_dense> R;
+    hh_read(const cp_dev_params *P, const char *seq, int rlen, const uint16_t *prof, int plen)
+      : wall(plen+1,0), perror((size_t)(plen+1)*4,-INFINITY), ev(16*plen+64), ov(16*plen+64)
+    { R.P = P; R.prof = prof; R.seq = seq; R.lf = P->logfact; R.plen = plen; R.rlen = rlen;
+      R.wall = wall.data(); R.wall_s = wall.data(); R.perror.a = perror.data();
+      R.eintvl = ev.data(); R.ointvl = ov.data();
+      R.ecap = (int)ev.size(); R.eidx = R.oidx = 0; R.overflow = 0;
+    }
+  };
 
+// What hh_wall_paths reports of a read, in this order (tests/wall_path_inputs.py: ACCOUNT).
+enum { HW_NC, HW_NT, HW_NLIVE0, HW_X, HW_NSW, HW_NO, HW_NSD, HW_MIDX, HW_M1, HW_NSM, HW_C, HW_OVERFLOW, HW_N };
+
+// find_wall up to the final sorted E-interval list (wall.c:590-910), the part of hh_classify_read that k_wall_tasks and
+// k_find_wall spread over lanes.  Returns the length of the list (R.overflow says whether a list ran over).  With `acct`
+// the numbers that decide which of k_find_wall's paths the read takes are counted on the way: nothing the walk computes
+// depends on them.
+static int hh_find_wall(hh_read &H, int64_t *acct)
+{ cp_read_t<cp_perr_dense> &R = H.R;
+  const cp_dev_params *P = R.P;
+  const uint16_t *prof = R.prof;
+  const int plen = R.plen;
+  std::vector<uint8_t> &wall = H.wall;
+  std::vector<cp_eintvl> &ev = H.ev, &ov = H.ov;
+  std::vector<uint8_t> cand;
+  if (acct)
+    { for (int k = 0; k < HW_N; k++) acct[k] = 0;
+      cand.assign(plen+1,0);
+    }
   for (int i = 1; i < plen; i++)
     { int a = prof[i-1], b = prof[i];
       if ((a < b ? a : b) >= P->cov[CP_REPEAT]) continue;
       if (abs(a-b) < CP_MIN_CNT_CHANGE) continue;
+      if (acct)                                           // k_wall_tasks, phase 1a: a task per pass whose filter says "live"
+        { cp_wall_pre pre;
+          cp_wall_candidate_pre(&R,i,&pre);
+          const int l0 = (cp_wall_candidate_filter(P,CP_SELF,pre) & CP_CF_LIVE) ? 1 : 0;
+          const int l1 = (cp_wall_candidate_filter(P,CP_OTHERS,pre) & CP_CF_LIVE) ? 1 : 0;
+          acct[HW_NC]++; acct[HW_NT] += l0+l1; acct[HW_NLIVE0] += l0;
+          cand[i] = 1;
+        }
       cp_wall_candidate(&R,i);
     }
   int NS = R.eidx, NO = R.oidx;
+  if (acct)
+    { acct[HW_NSW] = NS; acct[HW_NO] = NO;
+      for (int k = 0; k < NS; k++)                        // ends of accepted SELF pairs that are no candidates, each once
+        for (int pos : { ev[k].b, ev[k].e })
+          if (!cand[pos]) { cand[pos] = 2; acct[HW_X]++; }
+    }
   for (int i = 0; i < NO; i++) { wall[ov[i].b] &= ~CP_W_WALL_O; wall[ov[i].e] &= ~CP_W_WALL_O; }
   for (int i = 0; i < NS; i++) for (int j = ev[i].b+1; j < ev[i].e; j++) wall[j] &= ~CP_W_WALL_O;
   sort_e(ev.data(),NS); NS = cp_dedupe_sorted(ev.data(),NS);
@@ -110,10 +141,54 @@ int hh_classify_read(void *Pv, const char *seq, int rlen, const uint16_t *prof, 
       if (wall[i] & CP_W_PAIRED_M) continue;
       cp_wall_mult(&R,i,NS,&midx);
     }
+  if (acct) { acct[HW_NSD] = NS; acct[HW_MIDX] = midx; }
   for (int i = NS; i < midx; i++) for (int j = ev[i].b+1; j < ev[i].e; j++) wall[j] &= ~CP_W_WALL_O;
   if (NS < midx) { NS = midx; sort_e(ev.data(),NS); }
+  if (acct)                                               // k_find_wall's lane-parallel merge: the runs before the one that holds the last interval
+    { int hl = 0;
+      for (int k = 1; k < NS; k++) if (!(ev[k].b <= ev[k-1].e)) hl = k;
+      for (int k = 0; k < NS-1; k++)
+        { const bool head = k == 0 || !(ev[k].b <= ev[k-1].e), link = ev[k+1].b <= ev[k].e;
+          if (head && link && k != hl) acct[HW_M1]++;
+        }
+    }
   NS = cp_merge_eintvl(&R,NS);
   sort_e(ev.data(),NS);
+  if (acct)
+    { acct[HW_NSM] = NS; acct[HW_OVERFLOW] = R.overflow;
+      for (int k = 0; k < NS; )                           // connected components of the union of the list
+        { int ce = ev[k].e;
+          for (k++; k < NS && ev[k].b <= ce; k++) if (ev[k].e > ce) ce = ev[k].e;
+          acct[HW_C]++;
+        }
+    }
+  return NS;
+}
+
+// The account alone (tests/wall_path_inputs.py).  Returns 0, or -1 for a read without a k-mer.
+int hh_wall_paths(void *Pv, const char *seq, int rlen, const uint16_t *prof, int64_t *out)
+{ const cp_dev_params *P = (const cp_dev_params *)Pv;
+  const int plen = rlen-(P->K-1);
+  for (int k = 0; k < HW_N; k++) out[k] = 0;
+  if (plen <= 0) return -1;
+  hh_read H(P,seq,rlen,prof,plen);
+  hh_find_wall(H,out);
+  return 0;
+}
+
+// Sequential orchestration of the scalar device functions for one read (mirrors what the kernels do
+// with lanes).  Returns N or -1 on list overflow.
+int hh_classify_read(void *Pv, const char *seq, int rlen, const uint16_t *prof, char *labels,
+                     cp_intvl *intvl, int cap, int *M_out, cp_intvl *rintvl, int8_t *fw, int8_t *bw)
+{ const cp_dev_params *P = (const cp_dev_params *)Pv;
+  const int K = P->K, plen = rlen-(K-1);
+  for (int i = 0; i < K-1 && i < rlen; i++) labels[i] = 'N';
+  if (plen <= 0) return 0;
+  hh_read H(P,seq,rlen,prof,plen);
+  cp_read_t<cp_perr_dense> &R = H.R;
+  std::vector<uint8_t> &wall = H.wall;
+  std::vector<cp_eintvl> &ev = H.ev;
+  const int NS = hh_find_wall(H,nullptr);
   if (R.overflow) return -1;
   for (int i = 0; i < NS; i++) for (int j = ev[i].b; j < ev[i].e; j++) wall[j] |= CP_W_ERROR;
   int N = 0, b = 0;
