@@ -219,15 +219,31 @@ CP_HD const double *cp_logp_trans_at(const double *skel, int skel_kmax, long lon
   return (skel && k <= skel_kmax && cd <= skel_cdmax) ? skel+(cd*(skel_kmax+1)+k) : nullptr;
 }
 
-CP_HD double cp_logp_trans(const cp_dev_params *P, int b, int e, int cb, int ce, int cov)
-{ cov &= 0xffff;
+// The same for the arguments of cp_logp_trans itself (NULL on the host, which has no table): a caller loads from it
+// when it likes and hands the value to cp_logp_trans_from, which computes on the spot where there was nothing to load.
+CP_HD const double *cp_logp_trans_addr(const cp_dev_params *P, int b, int e, int cb, int ce, int cov)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  cov &= 0xffff;
   int d = e-b;
   if (d < 0) d = -d;
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (const double *at = cp_logp_trans_at(P->skel,P->skel_kmax,P->skel_cdmax,d,cb,ce,cov))
-    return *at;
+  return cp_logp_trans_at(P->skel,P->skel_kmax,P->skel_cdmax,d,cb,ce,cov);
+#else
+  (void)P; (void)b; (void)e; (void)cb; (void)ce; (void)cov;
+  return nullptr;
 #endif
+}
+CP_HD double cp_logp_trans_from(const cp_dev_params *P, bool have, double loaded, int b, int e, int cb, int ce, int cov)
+{ if (have) return loaded;
+  cov &= 0xffff;
+  int d = e-b;
+  if (d < 0) d = -d;
   return cp_logp_trans_calc(P,ce-cb,(double)cov*d);
+}
+
+CP_HD double cp_logp_trans(const cp_dev_params *P, int b, int e, int cb, int ce, int cov)
+{ const double *at = cp_logp_trans_addr(P,b,e,cb,ce,cov);
+  return cp_logp_trans_from(P,at != nullptr,at ? *at : 0.,b,e,cb,ce,cov);
 }
 
 // exp(logp_trans(...)): what the DP step of classify_rel needs of a transition (class_rel.c:300-319 exponentiates every
@@ -258,12 +274,33 @@ static inline
 double cp_p_errorin_calc(const cp_dev_params *P, int e, int t, int l, int cout, int cin)
 { return cp_p_errorin(P->logfact,e,P->pe[t][l],P->lpe[t][l],P->l1mpe[t][l],cout,cin); }
 
-CP_HD double cp_p_errorin_tl(const cp_dev_params *P, int e, int t, int l, int cout, int cin)
+// A load from one of the tables of cp_dev_params (or from the block itself) for a caller that chose the address with a
+// select: said to lie in global memory, or the device takes a generic load, which also waits for the wave's LDS traffic.
+CP_HD double cp_load_table(const double *p)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (P->petab && cin >= 0 && cin <= cout && cout <= P->pe_cmax)
-    return P->petab[((long long)(e*63+t*21+l)*(P->pe_cmax+1)+cout)*(P->pe_cmax+1)+cin];
+  return *(const __attribute__((address_space(1))) double *)p;
+#else
+  return *p;
 #endif
+}
+
+// Where the table holds the value (NULL: outside it, no table, or the host): "address first, load later", as
+// cp_logp_trans_at; the table's base and limit are the caller's copies of P's.
+CP_HD const double *cp_p_errorin_at(const double *petab, int pe_cmax, int e, int t, int l, int cout, int cin)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (petab && cin >= 0 && cin <= cout && cout <= pe_cmax)
+    return petab+(((long long)(e*63+t*21+l)*(pe_cmax+1)+cout)*(pe_cmax+1)+cin);
+#else
+  (void)petab; (void)pe_cmax; (void)e; (void)t; (void)l; (void)cout; (void)cin;
+#endif
+  return nullptr;
+}
+
+CP_HD double cp_p_errorin_tl(const cp_dev_params *P, int e, int t, int l, int cout, int cin)
+{ if (const double *at = cp_p_errorin_at(P->petab,P->pe_cmax,e,t,l,cout,cin))
+    return *at;
   return cp_p_errorin_calc(P,e,t,l,cout,cin);
 }
 

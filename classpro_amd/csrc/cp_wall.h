@@ -203,6 +203,13 @@ struct __attribute__((packed, aligned(2))) cp_u16x8 { uint16_t v[8]; };
 template <class PROF>
 CP_HD cp_u16x8 cp_load_u16x8(const PROF &prof, int lo) { return *reinterpret_cast<const cp_u16x8 *>(CP_SPAN(prof,lo,8)); }
 
+// the same sixteen bytes as four words, for a caller that takes the counts apart only later (cp_u16x8_get): taken apart
+// at the load, they are waited for at the load
+struct __attribute__((packed, aligned(2))) cp_u16x8w { uint32_t w[4]; };
+template <class PROF>
+CP_HD cp_u16x8w cp_load_u16x8w(const PROF &prof, int lo) { return *reinterpret_cast<const cp_u16x8w *>(CP_SPAN(prof,lo,8)); }
+CP_HD int cp_u16x8_get(const cp_u16x8w &x, int q) { return (int)((x.w[q >> 1] >> (16*(q & 1))) & 0xffffu); }
+
 // wall.c:324-329
 CP_HD bool cp_cthres_ng(int e, int cin, int ct)
 { return (e == CP_SELF) ? (cin >= ct) : (cin < ct); }
@@ -296,9 +303,11 @@ CP_HD int cp_wall_candidate_filter(const cp_dev_params *P, int e, const cp_wall_
   return CP_CF_LIVE;
 }
 
-// The expensive, read-only part of a pass whose filter said CP_CF_LIVE.
-template <class RD>
-CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, cp_cand_pure *out)
+// The expensive, read-only part of a pass whose filter said CP_CF_LIVE.  `prep` is called once the first group of
+// loads has left: a caller's own loads (k_wall_tasks: the base window of the partner loop) join that round trip.
+struct cp_no_prep { CP_HDM void operator()() const {} };
+template <class RD, class PREP>
+CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, cp_cand_pure *out, PREP prep)
 { const cp_dev_params *P = R->P;
   const auto &pr = R->prof;
   const int plen = R->plen, K = P->K, CMAX = P->cmax;
@@ -307,14 +316,36 @@ CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, c
   out->flags = CP_CF_LIVE; out->lc_kind = CP_LC_NONE; out->lc_j = -1; out->hc_j = -1;
   out->lc_v = out->hc_pe = CP_NEG_INF;
   CP_LT0();
-  out->own_pe = cp_p_errorin_tl(P,e,t,l,cout,cin);
-  CP_LT(0);
-
   // find_gain (w == DROP: partner GAIN to the right of i) / find_drop (w == GAIN: partner DROP to the
   // left), wall.c:331-507, folded into one routine by mirroring the index arithmetic.
   const int ulen = t+1;
   const bool right = (w == CP_DROP);
   int n, j, cout_j, cin_j;
+
+  // Every look-up below is a cold miss and most of their addresses hang on the one before, so the loads leave in THREE
+  // GROUPS and each group is used only after the next piece of work ("address first, load later", cp_math.h).  The top
+  // group is what the candidate alone decides: its own P(error), the entry and the threshold of the high-complexity
+  // scores' common factor pe_i, and the counts around the high-complexity partners.  A look-up outside its table
+  // is computed where the reference computes it; a lane with nothing to fetch loads a cell of the parameter block
+  // instead of branching around the load.
+  const double *nowhere = &P->pe[0][0];
+  const double *petab = P->petab;                         // (copies: read once, not again after every store)
+  const int pe_cmax = P->pe_cmax;
+  const double *own_at = cp_p_errorin_at(petab,pe_cmax,e,t,l,cout,cin);
+  const double *pei_at = cp_p_errorin_at(petab,pe_cmax,e,CP_HP,1,cout,cin);
+  const double own_ld = cp_load_table(own_at ? own_at : nowhere), pei_ld = cp_load_table(pei_at ? pei_at : nowhere);
+  const int    thr_i  = P->cthres[CP_HP][1][cout < CMAX ? cout : 0][CP_FINAL][e];
+  // The six high-complexity partners sit at consecutive positions: their seven counts come from ONE 16-byte load where
+  // that stays inside the read, and its eighth count is the one before them: the low-complexity partner of a candidate
+  // in no run at all (HP, l = 1, n = 0: most of them) lies one position before the first high-complexity one.
+  cp_u16x8w cx;
+  const int j0 = right ? (i+K-1) : (i-K+1);                // the n = 0 partner
+  const int lo8 = right ? j0-2 : j0-(CP_MAX_N_HC+1);      // counts at j0-2 .. j0+5 (right) / j0-6 .. j0+1 (left)
+  const bool wide = lo8 >= 0 && lo8+8 <= plen;
+  cx.w[0] = cx.w[1] = cx.w[2] = cx.w[3] = 0;
+  if (wide) cx = cp_load_u16x8w(pr,lo8);
+  prep();
+  CP_LT(0);
 
   // low-complexity partner (wall.c:345-378 / 432-467)
   const int m = ulen*l;
@@ -328,75 +359,105 @@ CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, c
       n++;
     }
   CP_LT(1);
-  j = right ? (i+K-1)+n-m : (i-K+1)-n+m;
+  out->own_pe = own_at ? own_ld : cp_p_errorin_calc(P,e,t,l,cout,cin);
+  const int dlc = n-m;                                   // the low-complexity partner lies where high-complexity partner number dlc would
+  j = right ? j0+dlc : j0-dlc;
   if (right ? (j <= i) : (j >= i))
     return;                                              // lc_kind NONE: no pair at all (wall.c:355 / 442)
-  if (right ? (j >= plen) : (j <= 0))
+
+  // Second group: the counts of the partners that the wide load does not hold -- the low-complexity partner outside
+  // the six positions, and all of them next to an end of the read.  Partner 0 of the arrays below is the
+  // low-complexity one, partner 1+n the high-complexity one of step n; pcin / pcout are its counts on the side of
+  // the error and beyond it (wall.c:362-363), pj < 0 = there is no such position.
+  constexpr int NP = CP_MAX_N_HC+2;
+  int pj[NP], pcin[NP], pcout[NP], cw[8];                 // cw[d+1], cw[d+2]: the counts (in, out) of partner d = -1 .. 5, on either side
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int q = 0; q < 8; q++) cw[q] = right ? cp_u16x8_get(cx,q) : cp_u16x8_get(cx,7-q);
+  const bool lc_in = !(right ? (j >= plen) : (j <= 0));
+  pj[0] = lc_in ? j : -1; pcin[0] = pcout[0] = 0;
+  if (lc_in)
+    { if (wide && dlc >= -1 && dlc <= CP_MAX_N_HC)
+        {
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+          for (int q = -1; q <= CP_MAX_N_HC; q++)
+            if (dlc == q) { pcin[0] = cw[q+1]; pcout[0] = cw[q+2]; }
+        }
+      else if (right) { pcin[0] = pr[j-1]; pcout[0] = pr[j]; }
+      else            { pcout[0] = pr[j-1]; pcin[0] = pr[j]; }
+    }
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (n = 0; n <= CP_MAX_N_HC; n++)
+    { const int jn = right ? j0+n : j0-n;
+      const bool in = !(right ? (jn >= plen) : (jn <= 0));      // the reference's loop ends at the first that is not
+      pj[1+n] = in ? jn : -1; pcin[1+n] = pcout[1+n] = 0;
+      if (!in) continue;
+      if (wide) { pcin[1+n] = cw[n+1]; pcout[1+n] = cw[n+2]; }
+      else if (right) { pcin[1+n] = pr[jn-1]; pcout[1+n] = pr[jn]; }
+      else            { pcout[1+n] = pr[jn-1]; pcin[1+n] = pr[jn]; }
+    }
+
+  // Third group: per partner its threshold and its P(error) entry.  All of them are fetched, also for partners that
+  // the filters below reject: those are simply not used.  (The Skellam term of logp_diff_pair, wall.c:317-322, which
+  // the OTHERS pass needs of a partner that passed its threshold, is looked up on the spot: one task in fourteen is an
+  // OTHERS task, and seven more values in flight for every lane spill registers at four waves per SIMD.)
+  const int pim1 = right ? cout : cin, pi = right ? cin : cout;      // the counts at i-1, i (cp_wall_candidate_pre)
+  int    pthr[NP];
+  double ppe[NP];
+  unsigned pe_in = 0;                                     // bit p: the look-up of partner p lies in its table
+  struct targs { int b, e, cb, ce, cv; };
+  auto trans_args = [&](int p) -> targs                   // logp_diff_pair's call of logp_trans for the candidate and partner p
+    { const int jp = pj[p] < 0 ? i : pj[p];
+      const int a = right ? pcin[p] : pcout[p], b = right ? pcout[p] : pcin[p];      // the counts at j-1, j
+      targs x;
+      x.b  = right ? i : jp; x.e = right ? jp : i;
+      x.cb = right ? pim1-pi : a-b;                       // (p[i-1]-p[i]) of the DROP position
+      x.ce = right ? b-a : pi-pim1;                       // (p[j]-p[j-1]) of the GAIN position
+      x.cv = right ? (pim1 > b ? pim1 : b) : (a > pi ? a : pi);
+      return x;
+    };
+  auto trans_val = [&](int p) -> double
+    { const targs x = trans_args(p);
+      return cp_logp_trans(P,x.b,x.e,x.cb,x.ce,x.cv);
+    };
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int p = 0; p < NP; p++)
+    { const int pt = p ? CP_HP : t, pl = p ? 1 : l;
+      const int ci_ = pcin[p], co_ = pcout[p];
+      const double *pe_at = cp_p_errorin_at(petab,pe_cmax,e,pt,pl,co_,ci_);
+      if (pe_at) pe_in |= 1u << p;
+      pthr[p] = P->cthres[pt][pl][co_ < CMAX ? co_ : 0][CP_FINAL][e];
+      ppe[p]  = cp_load_table(pe_at ? pe_at : nowhere);
+    }
+  CP_LT(2);
+
+  // low-complexity partner (wall.c:345-378 / 432-467)
+  if (!lc_in)
     { out->lc_kind = CP_LC_BOUNDARY;
       out->lc_j = right ? plen : 0;
     }
   else
-    { if (right) { cin_j = pr[j-1]; cout_j = pr[j]; }
-      else       { cout_j = pr[j-1]; cin_j = pr[j]; }
+    { cin_j = pcin[0]; cout_j = pcout[0];
       out->lc_j = j;
       if (cin_j <= cout_j
-          && !(cout_j < CMAX && cp_cthres_ng(e,cin_j,P->cthres[t][l][cout_j][CP_FINAL][e]))
-          && (e == CP_SELF || (right ? cp_logp_diff_pair(R,i,j) : cp_logp_diff_pair(R,j,i)) >= CP_THRES_DIFF_EO))
+          && !(cout_j < CMAX && cp_cthres_ng(e,cin_j,pthr[0]))
+          && (e == CP_SELF || trans_val(0) >= CP_THRES_DIFF_EO))
         { out->lc_kind = CP_LC_PAIR;
-          out->lc_v = cp_p_errorin_tl(P,e,t,l,cout_j,cin_j);
+          out->lc_v = (pe_in & 1u) ? ppe[0] : cp_p_errorin_calc(P,e,t,l,cout_j,cin_j);
         }
       else
         out->lc_kind = CP_LC_REJECT;
     }
 
-  CP_LT(2);
-  // high-complexity partners (wall.c:380-404 / 469-493).  The six partners sit at consecutive positions, so their
-  // seven counts come from ONE 16-byte load where that stays inside the read, and each partner's two look-ups (its
-  // P(error in), and for OTHERS the Skellam term of logp_diff_pair) are independent of the other partners': all of
-  // them are issued before the first is used (first pass), then the reference's loop picks the first strict maximum
-  // (second pass).  One dependent chain of six round trips became two.
-  int    hcj[CP_MAX_N_HC+1], hcin[CP_MAX_N_HC+1], hcout[CP_MAX_N_HC+1];
-  bool   hok[CP_MAX_N_HC+1];
-  double hpe[CP_MAX_N_HC+1], hdiff[CP_MAX_N_HC+1];
-  int    cw[CP_MAX_N_HC+2];                               // counts at j0-1 .. j0+5 (right) / j0-6 .. j0 (left), j0 = the n = 0 partner
-  const int j0 = right ? (i+K-1) : (i-K+1);
-  const int lo8 = right ? j0-1 : j0-(CP_MAX_N_HC+1);
-  const bool wide = lo8 >= 0 && lo8+8 <= plen;
-  if (wide)
-    { const cp_u16x8 x = cp_load_u16x8(pr,lo8);
-#ifdef __HIPCC__
-#pragma unroll
-#endif
-      for (int q = 0; q < CP_MAX_N_HC+2; q++) cw[q] = x.v[q];
-    }
-  const bool pass_i = !(cout < CMAX && cp_cthres_ng(e,cin,P->cthres[CP_HP][1][cout][CP_FINAL][e]));
-#ifdef __HIPCC__
-#pragma unroll
-#endif
-  for (n = 0; n <= CP_MAX_N_HC; n++)
-    { j = right ? j0+n : j0-n;
-      hcj[n] = j; hok[n] = false; hpe[n] = 0.; hdiff[n] = 0.;
-      if (right ? (j >= plen) : (j <= 0))
-        { hcj[n] = -1; continue; }                        // the reference's loop ends here
-      int a, b;                                           // counts at j-1, j
-      if (wide) { a = cw[right ? n : CP_MAX_N_HC-n]; b = cw[right ? n+1 : CP_MAX_N_HC+1-n]; }
-      else      { a = pr[j-1]; b = pr[j]; }
-      if (right) { cin_j = a; cout_j = b; }
-      else       { cout_j = a; cin_j = b; }
-      hcin[n] = cin_j; hcout[n] = cout_j;
-      if (!(cin_j <= cout_j) || !pass_i
-          || (cout_j < CMAX && cp_cthres_ng(e,cin_j,P->cthres[CP_HP][1][cout_j][CP_FINAL][e])))
-        continue;
-      hok[n] = true;
-      if (e == CP_OTHERS)                                 // logp_diff_pair (wall.c:317-322) with the counts already in hand
-        { const int pim1 = pr[i-1], pi = pr[i];
-          const int n_drop = right ? pim1-pi : a-b;       // (p[i-1]-p[i]) of the DROP position
-          const int n_gain = right ? b-a : pi-pim1;       // (p[j]-p[j-1]) of the GAIN position
-          const int cv = right ? (pim1 > b ? pim1 : b) : (a > pi ? a : pi);
-          hdiff[n] = cp_logp_trans(P,right ? i : j,right ? j : i,n_drop,n_gain,cv);
-        }
-      hpe[n] = cp_p_errorin_tl(P,e,CP_HP,1,cout_j,cin_j);
-    }
+  // high-complexity partners (wall.c:380-404 / 469-493): the reference's loop picks the first strict maximum
+  const bool pass_i = !(cout < CMAX && cp_cthres_ng(e,cin,thr_i));
   bool   have_pe_i = false;
   double pe_i = 0., max_pe = CP_NEG_INF;
   int    max_j = -1;
@@ -404,17 +465,22 @@ CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, c
 #pragma unroll
 #endif
   for (n = 0; n <= CP_MAX_N_HC; n++)
-    { if (hcj[n] < 0) break;
-      if (!hok[n]) continue;
-      if (e == CP_OTHERS && hdiff[n] < CP_THRES_DIFF_EO)
+    { const int p = 1+n;
+      if (pj[p] < 0) break;
+      cin_j = pcin[p]; cout_j = pcout[p];
+      if (!(cin_j <= cout_j) || !pass_i
+          || (cout_j < CMAX && cp_cthres_ng(e,cin_j,pthr[p])))
+        continue;
+      if (e == CP_OTHERS && trans_val(p) < CP_THRES_DIFF_EO)
         continue;
       if (!have_pe_i)                                   // same arguments every time (wall.c:398)
-        { pe_i = cp_p_errorin_tl(P,e,CP_HP,1,cout,cin);      // HC_ERATE = pe[HP][1], wall.c:180
+        { pe_i = pei_at ? pei_ld : cp_p_errorin_calc(P,e,CP_HP,1,cout,cin);      // HC_ERATE = pe[HP][1], wall.c:180
           have_pe_i = true;
         }
-      double pe = pe_i * hpe[n];
+      const double hpe = ((pe_in >> p) & 1u) ? ppe[p] : cp_p_errorin_calc(P,e,CP_HP,1,cout_j,cin_j);
+      double pe = pe_i * hpe;
       if (max_pe < pe)
-        { max_j  = hcj[n];
+        { max_j  = pj[p];
           max_pe = pe;
         }
     }
@@ -422,6 +488,10 @@ CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, c
   out->hc_pe = max_pe;
   CP_LT(3);
 }
+
+template <class RD>
+CP_HD void cp_wall_candidate_live(RD *R, int i, int e, const cp_wall_pre &pre, cp_cand_pure *out)
+{ cp_wall_candidate_live(R,i,e,pre,out,cp_no_prep()); }
 
 template <class RD>
 CP_HD void cp_wall_candidate_pure(RD *R, int i, int e, const cp_wall_pre &pre, cp_cand_pure *out)

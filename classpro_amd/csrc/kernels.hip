@@ -50,6 +50,11 @@ __device__ unsigned long long g_bounds[4];               // cp_bounds.h
 
 // Make one lane's global stores visible to the other lanes of the same wave (blocks are one wave).
 __device__ __forceinline__ void wave_sync() { __syncthreads(); }
+// The same for a block of ONE wave that only hands LDS cells from lane to lane: a wave's LDS operations complete in
+// order, so nothing has to be waited for -- in particular not the wave's outstanding global stores, which the fence of
+// __syncthreads() drains.
+__device__ __forceinline__ void wave_sync_lds()
+{ __builtin_amdgcn_fence(__ATOMIC_RELEASE,"wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE,"wavefront"); }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE-1); }
 // the value of the lane below (lane 0: `first`) as a DPP move (wave_shr:1), the last lane's value as a readlane: neither
@@ -1000,6 +1005,9 @@ __device__ __forceinline__ void fr_seq_win_load(cp_seq_lwin &sq, char *row, int 
 #ifndef FW_WAVES_PER_EU
 #define FW_WAVES_PER_EU 4
 #endif
+#ifndef FW_LISTS
+#define FW_LISTS 255                 // candidates of a read whose lists k_wall_tasks keeps on chip
+#endif
 #undef PH_STOP_EXTRA
 #define PH_STOP_EXTRA do { if (lane == 0) { fwc[4*(int64_t)r] = 0; fwc[4*(int64_t)r+1] = 0; fwc[4*(int64_t)r+2] = 0; fwc[4*(int64_t)r+3] = 0; } } while (0)
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(FW_WAVES_PER_EU)))
@@ -1015,6 +1023,15 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
   const int plen = (int)(prof_off[r+1]-po);
   const int rlen = (int)(seq_off[r+1]-seq_off[r]);
   __shared__ __attribute__((aligned(4))) char s_win[WAVE*FW_SEQ_STRIDE];
+  // The lists ON CHIP for a read of at most FW_LISTS candidates (all but the pathological ones; the same bound as
+  // k_find_wall's on-chip flags): phase 0 fills the positions, 1a the info words, the count pairs and the task codes, and
+  // 1a / 1b read them back from here.  The copies in `wl` are still stored, for k_find_wall, but this kernel neither
+  // loads them nor waits for the stores: a phase used to begin with a drain of the one before and a cold load of what
+  // it had just written.  Every row is written before it is read for the read at hand; a longer read takes the lists
+  // in HBM as before.
+  static_assert(FW_LISTS <= 255,"the on-chip lists have 256 rows");
+  __shared__ int32_t  s_cl[256], s_cc[256];
+  __shared__ uint16_t s_ci[256], s_tl[512];
   cp_read_t<cp_perr_hybrid,cp_seq_lwin> R;
   R.P = P; R.prof = CP_PROF_VIEW(prof+po,plen); R.lf = P->logfact; R.plen = plen; R.rlen = rlen;
   R.seq.g = CP_SEQ_VIEW(seq+seq_off[r],rlen); R.seq.w = (CP_LDS_PTR(const char))(s_win+lane*FW_SEQ_STRIDE); R.seq.lo = 0; R.seq.len = 0;
@@ -1046,19 +1063,25 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
           for (uint64_t t = bits; t; t &= t-1)
             { const int k = __ffsll((long long)t)-1;
               if (off < icap) clist[off] = (int)((w << 6)+k-po);
+              if (off < FW_LISTS) s_cl[off] = (int)((w << 6)+k-po);
               off++;
             }
           n_c += tot;
         }
     }
   if (n_c > icap) n_c = icap;                           // cannot happen: icap = 2*ncand+4
-  wave_sync();
+  const bool lists = n_c <= FW_LISTS;                   // (wave-uniform)
+  if (lists) wave_sync_lds(); else wave_sync();
   PH_STAMP(0);
   int n_t = 0, n_live0 = 0;                             // tasks so far, SELF tasks among them
+  // (a long read stages the rows of a step in the first 64 rows on chip, lane by lane, and the step reads them there as
+  //  a short read's: with a choice between the list on chip and the one in HBM at every use, the compiler makes generic
+  //  loads of them, which wait for both kinds of memory)
   for (int base = 0; base < n_c; base += WAVE)          // 1a
     { int f0 = 0, f1 = 0;
+      if (!lists) { if (base+lane < n_c) s_cl[lane] = clist[base+lane]; wave_sync_lds(); }
       if (base+lane < n_c)
-        { const int i = clist[base+lane];
+        { const int i = s_cl[lists ? base+lane : lane];
           const bool drop = R.prof[i-1] > R.prof[i];       // (cp_wall_candidate_pre's rule: the contexts of a DROP end at i+K-2, those of a GAIN begin at i)
           cp_seq_rsrc rs; rs.g = R.seq.g;
           R1.seq = cp_seq_window(rs,drop ? i+P->K-2 : i,rlen,drop ? -1 : +1);
@@ -1068,6 +1091,10 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
           f1 = cp_wall_candidate_filter(P,CP_OTHERS,pre);
           cinfo[base+lane] = pre.maxt*32+pre.maxl+(f0 << 8)+(f1 << 12);
           ccnt[base+lane] = (int)R.prof[i-1] | ((int)R.prof[i] << 16);
+          if (lists)
+            { s_ci[base+lane] = (uint16_t)(pre.maxt*32+pre.maxl+(f0 << 8)+(f1 << 12));
+              s_cc[base+lane] = (int)R.prof[i-1] | ((int)R.prof[i] << 16);
+            }
           // (a candidate that is an OTHERS wall whatever the replay finds -- CP_CF_WALLNOW in f1 -- gets its flag from
           //  k_find_wall, which knows whether the read's flags live on chip or in the flag array)
         }
@@ -1077,24 +1104,26 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
         { int x = __shfl_up(off,o); if (lane >= o) off += x; }
       const int tot = __shfl(off,WAVE-1);
       off = n_t+off-c;
-      if (l0) { if (off < icap) tlist[off] = (base+lane)*2;   off++; }
-      if (l1) { if (off < icap) tlist[off] = (base+lane)*2+1; }
+      if (l0) { if (off < icap) tlist[off] = (base+lane)*2;   if (lists) s_tl[off] = (uint16_t)((base+lane)*2);   off++; }
+      if (l1) { if (off < icap) tlist[off] = (base+lane)*2+1; if (lists) s_tl[off] = (uint16_t)((base+lane)*2+1); }
       n_t += tot;
       n_live0 += __popcll(__ballot(l0));
     }
   int ovf = 0;
   if (n_t > icap) { ovf = 1; n_t = 0; n_c = 0; }        // cannot happen: 2*n_c <= icap
-  wave_sync();
+  if (lists) wave_sync_lds(); else wave_sync();
   PH_STAMP(7);
   for (int tb = 0; tb < n_t; tb += WAVE)                // 1b: lane k evaluates task k
     { const int nb = (n_t-tb < WAVE) ? n_t-tb : WAVE;
       if (lane < nb)
-        { const int code = tlist[tb+lane], k = code >> 1, e = code & 1;
-          const int i = clist[k], tl = cinfo[k] & 255, cc = ccnt[k];
+        { if (!lists)
+            { const int code = tlist[tb+lane], k = code >> 1;
+              s_tl[lane] = (uint16_t)(lane*2+(code & 1)); s_cl[lane] = clist[k]; s_ci[lane] = (uint16_t)cinfo[k]; s_cc[lane] = ccnt[k];
+            }
+          const int code = s_tl[lists ? tb+lane : lane], k = code >> 1, e = code & 1;      // (k: the candidate's row on chip)
+          const int i = s_cl[k], tl = s_ci[k] & 255, cc = s_cc[k];
           cp_wall_pre pre;
           const int cim1 = cc & 0xffff, ci = (cc >> 16) & 0xffff;
-          // the partners of a DROP lie to the right and their contexts end K-2 bases further on, those of a GAIN to the left
-          fr_seq_win_load(R.seq,s_win+lane*FW_SEQ_STRIDE,cim1 > ci ? i+P->K-16 : i-24,rlen);
           pre.cng = cim1 > ci ? cim1-ci : ci-cim1;
           if (cim1 > ci) { pre.wtype = CP_DROP; pre.cin = ci;   pre.cout = cim1; }
           else           { pre.wtype = CP_GAIN; pre.cin = cim1; pre.cout = ci;   }
@@ -1103,7 +1132,9 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
           pre.lpe   = P->lpe[pre.maxt][pre.maxl];
           pre.l1mpe = P->l1mpe[pre.maxt][pre.maxl];
           cp_cand_pure c;
-          cp_wall_candidate_live(&R,i,e,pre,&c);
+          // the partners of a DROP lie to the right and their contexts end K-2 bases further on, those of a GAIN to the left;
+          // the window's two loads leave with the first load group of the look-ups
+          cp_wall_candidate_live(&R,i,e,pre,&c,[&]() { fr_seq_win_load(R.seq,s_win+lane*FW_SEQ_STRIDE,cim1 > ci ? i+P->K-16 : i-24,rlen); });
           task_res q;
           q.own_pe = c.own_pe; q.lc_v = c.lc_v; q.hc_pe = c.hc_pe;
           q.lc_j = c.lc_j;
