@@ -1166,6 +1166,8 @@ extern "C" int cp_debug_live_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_live_prof),8); }
 extern "C" int cp_debug_emit_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_emit_prof),8); }
+extern "C" int cp_debug_fw_prof(unsigned long long *out12)
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_fw_prof),12); }
 extern "C" int cp_debug_unrel_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_unrel_prof),8); }
 extern "C" int cp_debug_rel_prof(unsigned long long *out12)

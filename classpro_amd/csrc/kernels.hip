@@ -869,11 +869,15 @@ __device__ __forceinline__ cp_intvl cp_soa_get(const cp_soa &S, int64_t at)
 __device__ unsigned long long g_phase_max[12], g_phase_sum[12], g_phase_arg[12];
 __device__ unsigned long long g_live_prof[8];
 __device__ unsigned long long g_unrel_prof[8];          // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] of a round up to its first global load, [2] of the kernel; [3] waves; [4] of a round from there to the new classes (waiting for the loads and using them); [5] of the interval load before the rounds, [6] of the sort
-__device__ unsigned long long g_emit_prof[8];           // wave time inside the emission loop: [0] boundaries, [1] make_interval, [2] find_rel, [3] record stores, [4] compaction
-#ifdef CP_PROF_INNER
+__device__ unsigned long long g_emit_prof[8];           // k_find_wall: reads whose E-interval list has at most 64 entries and the summed list lengths, [0],[1] before the un-wall, [2],[3] before the merge, [4],[5] before the components; k_classify_rel_grp: [6] repeated passes, [7] waves with a second DP (count | total << 32)
+// k_find_wall's hand-off from k_wall_tasks and its emission loop, slots of their own (g_emit_prof and g_live_prof are shared with
+// the list-length and round statistics): wave time [0] of the head, from entry until the replay's first chunk begins,
+// [1] of a chunk's head, until position, wall type and task result are in registers; [2] chunks, [3] reads on the
+// lane-parallel replay; [4..7] inside the emission loop (EM_LT): components and boundaries, cp_make_interval, find_rel, record
+// stores and compaction
+__device__ unsigned long long g_fw_prof[12];
 #define EM_LT0() unsigned long long em_t = wall_clock64()
-#define EM_LT(k) do { unsigned long long t_ = wall_clock64(); if (lane == 0) atomicAdd(&g_emit_prof[k],t_-em_t); em_t = wall_clock64(); } while (0)
-#endif
+#define EM_LT(k) do { unsigned long long t_ = wall_clock64(); if (lane == 0) atomicAdd(&g_fw_prof[4+(k)],t_-em_t); em_t = wall_clock64(); } while (0)
 #define PH_STAMP(k) do { if (lane == 0) { unsigned long long t_ = wall_clock64(); unsigned long long d_ = t_-ph_t; ph_t = t_; \
       atomicAdd(&g_phase_sum[k],d_); unsigned long long o_ = atomicMax(&g_phase_max[k],d_); if (d_ > o_) g_phase_arg[k] = ((unsigned long long)r << 32) | (unsigned)n_c; } } while (0)
 #elif defined(CP_STOP_AT)
@@ -907,8 +911,24 @@ __device__ unsigned long long g_emit_prof[8];           // wave time inside the 
 // k_wall_tasks does 0-1b (4 waves per SIMD) and leaves the lists and the task results in HBM; k_find_wall does 2 and
 // the list phases after the walk at 5.5 waves per SIMD: they are chains of dependent loads and want waves, not registers.
 // Scratch: the four int lists of `wl` hold per candidate [0] maxt,maxl and both filter results, [1] the position,
-// [2] the count pair, and [3] the task list; `tres` the task results; `fwc` per read n_c, n_t, SELF tasks, overflow.
-struct task_res { double own_pe, lc_v, hc_pe; int lc_j, hc;  };   // hc: lc_kind | (hc_j >= 0) << 2 | (hc_j - i) << 16
+// [2] the count pair, and [3] the task list -- [2] and [3] only for a read of more than FW_LISTS candidates, whose own
+// phases 1a / 1b read them back; `tres` the task records; `fwc` per read n_c, n_t, SELF tasks, overflow.
+// A task record holds all the replay needs of its task: k_find_wall loads a chunk's records at tb+lane and nothing behind
+// them (until the record carried them, position and wall type were a look-up through the task list: tlist -> clist, ccnt,
+// a second cold round trip per chunk).
+//   hc    lc_kind | (hc_j >= 0) << 2 | e << 3 | wall type << 4 | (hc_j - i) << 16   (|hc_j - i| <= K-1+CP_MAX_N_HC, signed)
+//   lc_j  the low-complexity partner's position, 0 .. plen (both ends occur with CP_LC_BOUNDARY)
+//   pos   the candidate's position, 1 .. plen-1
+//   kc    the candidate's row in the read's candidate list: a whole int, so it holds the row of any read (it is read only
+//         while the flags are on chip, n_c <= 255)
+struct task_res { double own_pe, lc_v, hc_pe; int lc_j, hc, pos, kc; };
+#define TR_E(hc)     (((hc) >> 3) & 1)
+#define TR_WTYPE(hc) (((hc) >> 4) & 1)
+static_assert(sizeof(task_res) == 40,"three doubles and four ints, no padding");
+static_assert(CP_DROP == 0 && CP_GAIN == 1 && CP_SELF == 0 && CP_OTHERS == 1,"one bit each in task_res::hc");
+static_assert(CP_LC_REJECT <= 3,"lc_kind takes two bits of task_res::hc");
+// what the one-lane replay stages of a chunk's records in the 2 KB block: the position travels by readlane
+struct task_stage { double own_pe, lc_v, hc_pe; int lc_j, hc; };
 
 // The sequence contexts of the walk (cp_ctx.h) look at the bases next to a position.  Phase 1a needs the three contexts
 // of the candidate itself: eight bases before i+K-2 (a DROP) or on either side of i (a GAIN) -- ONE 16-byte load into
@@ -1025,10 +1045,11 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
   __shared__ __attribute__((aligned(4))) char s_win[WAVE*FW_SEQ_STRIDE];
   // The lists ON CHIP for a read of at most FW_LISTS candidates (all but the pathological ones; the same bound as
   // k_find_wall's on-chip flags): phase 0 fills the positions, 1a the info words, the count pairs and the task codes, and
-  // 1a / 1b read them back from here.  The copies in `wl` are still stored, for k_find_wall, but this kernel neither
-  // loads them nor waits for the stores: a phase used to begin with a drain of the one before and a cold load of what
-  // it had just written.  Every row is written before it is read for the read at hand; a longer read takes the lists
-  // in HBM as before.
+  // 1a / 1b read them back from here.  Positions and info words are still stored to `wl`, for k_find_wall, but this
+  // kernel neither loads them nor waits for the stores: a phase used to begin with a drain of the one before and a cold
+  // load of what it had just written.  Count pairs and task codes are not stored at all for such a read: what
+  // k_find_wall wanted of them is in the task record.  Every row is written before it is read for the read at hand; a
+  // longer read takes the lists in HBM as before.
   static_assert(FW_LISTS <= 255,"the on-chip lists have 256 rows");
   __shared__ int32_t  s_cl[256], s_cc[256];
   __shared__ uint16_t s_ci[256], s_tl[512];
@@ -1090,7 +1111,7 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
           f0 = cp_wall_candidate_filter(P,CP_SELF,pre);
           f1 = cp_wall_candidate_filter(P,CP_OTHERS,pre);
           cinfo[base+lane] = pre.maxt*32+pre.maxl+(f0 << 8)+(f1 << 12);
-          ccnt[base+lane] = (int)R.prof[i-1] | ((int)R.prof[i] << 16);
+          if (!lists) ccnt[base+lane] = (int)R.prof[i-1] | ((int)R.prof[i] << 16);
           if (lists)
             { s_ci[base+lane] = (uint16_t)(pre.maxt*32+pre.maxl+(f0 << 8)+(f1 << 12));
               s_cc[base+lane] = (int)R.prof[i-1] | ((int)R.prof[i] << 16);
@@ -1104,8 +1125,8 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
         { int x = __shfl_up(off,o); if (lane >= o) off += x; }
       const int tot = __shfl(off,WAVE-1);
       off = n_t+off-c;
-      if (l0) { if (off < icap) tlist[off] = (base+lane)*2;   if (lists) s_tl[off] = (uint16_t)((base+lane)*2);   off++; }
-      if (l1) { if (off < icap) tlist[off] = (base+lane)*2+1; if (lists) s_tl[off] = (uint16_t)((base+lane)*2+1); }
+      if (l0) { if (lists) s_tl[off] = (uint16_t)((base+lane)*2);   else if (off < icap) tlist[off] = (base+lane)*2;   off++; }
+      if (l1) { if (lists) s_tl[off] = (uint16_t)((base+lane)*2+1); else if (off < icap) tlist[off] = (base+lane)*2+1; }
       n_t += tot;
       n_live0 += __popcll(__ballot(l0));
     }
@@ -1138,7 +1159,12 @@ k_wall_tasks(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, 
           task_res q;
           q.own_pe = c.own_pe; q.lc_v = c.lc_v; q.hc_pe = c.hc_pe;
           q.lc_j = c.lc_j;
-          q.hc = c.lc_kind | (c.hc_j >= 0 ? 4 : 0) | ((c.hc_j >= 0 ? c.hc_j-i : 0) << 16);
+          // (the task's code once more, from where it lies, instead of a register kept across the look-ups)
+          int code2;
+          if (lists) code2 = s_tl[tb+lane]; else code2 = tlist[tb+lane];
+          q.hc = c.lc_kind | (c.hc_j >= 0 ? 4 : 0) | ((code2 & 1) << 3) | ((int)pre.wtype << 4)
+                 | ((c.hc_j >= 0 ? c.hc_j-i : 0) << 16);
+          q.pos = i; q.kc = code2 >> 1;
           tres[tb+lane] = q;
         }
     }
@@ -1165,15 +1191,27 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
 { if ((int)blockIdx.x >= nreads) return;
   const int r = perm[blockIdx.x];
   const int lane = lane_id();
-  const int64_t po = prof_off[r];
-  const int plen = (int)(prof_off[r+1]-po);
-  const int rlen = (int)(seq_off[r+1]-seq_off[r]);
+  // The head is three rounds of loads: `perm`; the read's ten offsets and the sixteen bytes k_wall_tasks left in `fwc`,
+  // whose addresses need r alone; then the candidates' positions and info words (the flags on chip) and the first
+  // chunk's task records, which leave before the LDS fills that need no loaded value and return under them.
+  const int64_t po = prof_off[r], po1 = prof_off[r+1], so = seq_off[r], so1 = seq_off[r+1];
+  const int64_t ho = hoff[r], ho1 = hoff[r+1], eo = eoff[r], eo1 = eoff[r+1], io = ioff[r], io1 = ioff[r+1];
+  const int4 fw4 = *reinterpret_cast<const int4 *>(fwc+4*(int64_t)r);
+  // (all of the second group is in registers here: left to itself the compiler sinks nine of the loads below the test for a read
+  //  without k-mers, behind the wait for the two it needs there)
+  asm volatile("" :: "s"(po), "s"(po1), "s"(so), "s"(so1), "s"(ho), "s"(ho1), "s"(eo), "s"(eo1), "s"(io), "s"(io1),
+                     "s"(fw4.x), "s"(fw4.y), "s"(fw4.z), "s"(fw4.w));
+  const int plen = (int)(po1-po);
+  const int rlen = (int)(so1-so);
 
 #ifndef FW_XCAP
 #define FW_XCAP 8                     // off-list SELF walls kept on chip per read (a diagnostic build with 1 drives the full-list path: scripts/r5_xcap.sh)
 #endif
 #ifndef FW_LCAP1
 #define FW_LCAP1 64
+#endif
+#ifdef CP_PROF_WALK
+  const unsigned long long fw_t0 = wall_clock64();
 #endif
   if (plen <= 0)                                         // a read shorter than K has no k-mer: no interval (ClassPro.c:209-226 prints
     { if (lane == 0) { nintvl[r] = 0; if (do_rel) nrel[r] = 0; }      // its N's and goes on).  Found by the -DCP_BOUNDS build: the
@@ -1186,10 +1224,10 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
   __shared__ int s_nx;
   __shared__ cp_eintvl s_ev[FW_EVL];                     // the E-interval list while it is short (fw_evl)
   cp_read_t<cp_perr_hybrid,CP_SEQ_T,CP_PROF_T,const double *,fw_evl> R;
-  R.P = P; R.prof = CP_PROF_VIEW(prof+po,plen); R.seq = CP_SEQ_VIEW(seq+seq_off[r],rlen); R.lf = P->logfact; R.plen = plen; R.rlen = rlen;
+  R.P = P; R.prof = CP_PROF_VIEW(prof+po,plen); R.seq = CP_SEQ_VIEW(seq+so,rlen); R.lf = P->logfact; R.plen = plen; R.rlen = rlen;
   R.wall = wall_all+po+r;
   R.wall_s = walls_all+po+r;
-  { const int64_t ho = hoff[r], hc = (hoff[r+1]-ho) >> 1;     // two tables, one per error type
+  { const int64_t hc = (ho1-ho) >> 1;                   // two tables, one per error type
     R.perror.g.keys = hkeys+ho;
     R.perror.g.vals = hvals+ho*4;
     R.perror.g.mask = (uint32_t)hc-1;
@@ -1198,24 +1236,24 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
     R.perror.lcap0 = LCAP0; R.perror.lcap1 = LCAP1;
     R.perror.use_lds = 0;
   }
-  if (lane == 0) s_nx = 0;
-  for (int k = lane; k < LCAP0+LCAP1; k += WAVE)
-    s_mkey[k] = -1;
-  R.eintvl.g = eintvl_all+eoff[r];
+  R.eintvl.g = eintvl_all+eo;
   R.eintvl.l = (CP_LDS_PTR(cp_eintvl))s_ev;
-  R.ointvl.g = ointvl_all+eoff[r];                      // the O-pairs (a handful; only their ends are read back) stay in HBM
-  R.ecap = (int)(eoff[r+1]-eoff[r]);
+  R.ointvl.g = ointvl_all+eo;                           // the O-pairs (a handful; only their ends are read back) stay in HBM
+  R.ecap = (int)(eo1-eo);
   R.eidx = R.oidx = 0; R.overflow = 0;
-  cp_intvl *intvl = intvl_all+ioff[r];
-  const int icap = (int)(ioff[r+1]-ioff[r]);
-  int32_t *wl = wlist+ioff[r]*4;                        // four int32 lists of capacity icap
-  const task_res *tres = tres_all+ioff[r];
+  cp_intvl *intvl = intvl_all+io;
+  const int icap = (int)(io1-io);
+  int32_t *wl = wlist+io*4;                             // four int32 lists of capacity icap (a short read's: the first two)
+  const task_res *tres = tres_all+io;
   uint8_t *wall = R.wall;
   const uint8_t *wall_s = R.wall_s;
-  __shared__ task_res s_res[WAVE];
-  int32_t *clist = wl+icap, *ccnt = wl+2*(int64_t)icap, *tlist = wl+3*(int64_t)icap;
-  const int n_c = fwc[4*(int64_t)r], n_t = fwc[4*(int64_t)r+1], n_live0 = fwc[4*(int64_t)r+2];
-  if (fwc[4*(int64_t)r+3]) R.overflow = 1;
+  // The 2 KB staging block: the candidates' flags and the dependency masks during the replay (or a chunk's records on
+  // the one-lane replay), the short lists of the phases after the walk.  Its size is its own, not the task record's.
+  constexpr int SBLK = 2048;
+  __shared__ unsigned long long s_blk[SBLK/8];
+  int32_t *clist = wl+icap;
+  const int n_c = fw4.x, n_t = fw4.y, n_live0 = fw4.z;
+  if (fw4.w) R.overflow = 1;
 #ifdef CP_PROF_WALK
   unsigned long long ph_t = wall_clock64();
 #endif
@@ -1228,12 +1266,7 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
   R.eintvl.big = (n_live0 > FW_EVL || R.ecap < FW_EVL) ? 1 : 0;
   // a pass whose memo does not fit on chip uses its table in HBM: empty it here (the few reads that need one), instead
   // of a memset over every read's tables per batch
-  { const int hc = (int)R.perror.g.mask+1;
-    for (int e = 0; e < 2; e++)
-      if (!((R.perror.use_lds >> e) & 1))
-        for (int k = lane; k < hc; k += WAVE) R.perror.g.keys[(size_t)e*hc+k] = -1;
-  }
-  wave_sync();
+  // (below, behind the head's third group of loads)
   // 2. The replay (wall.c:639-690 with the values of step 1), 64 tasks at a time, A LANE PER TASK.  What one task reads
   //    of another's: the "paired" flag of its own position, set by an earlier task of the same pass that took the position
   //    as its partner, and the perror memo of its position and of its low-complexity partner's (the first request's value
@@ -1251,25 +1284,58 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
   // clean-up stores that keep the flag arrays zero between batches (together 2/3 of this kernel's write traffic), and
   // k_wall_tasks writes no flag either.  A read whose walk pairs a position that is no candidate (a boundary, a partner
   // below the scan's threshold) starts over with its flags in the arrays.
-  int *sbuf = reinterpret_cast<int *>(s_res);
-  constexpr int SBUF = (int)(sizeof(task_res)*WAVE/sizeof(int));      // 512 ints
+  int *sbuf = reinterpret_cast<int *>(s_blk);
+  constexpr int SBUF = SBLK/(int)sizeof(int);           // 512 ints
   constexpr int SCOMP = 64;                             // components of the error regions kept on chip
   constexpr int U16 = 2*(SBUF-2*SCOMP);                 // 16-bit list slots in front of the component arrays
   uint16_t *s16 = reinterpret_cast<uint16_t *>(sbuf);
   fw_cflags F;
   F.pos = s16; F.fo = reinterpret_cast<uint8_t *>(s16+n_c); F.fs = F.fo+n_c; F.n = n_c;
   constexpr int NDEP = 128;                             // slots of the dependency table (behind the flags: the block's second half)
-  static_assert(sizeof(task_res)*WAVE >= 4*256+NDEP*sizeof(unsigned long long),"flags of 255 candidates and the dependency masks fit the staging block");
+  static_assert(SBLK >= 4*256+NDEP*sizeof(unsigned long long),"flags of 255 candidates and the dependency masks fit the staging block");
+  static_assert(sizeof(task_stage)*WAVE <= SBLK,"a chunk of the one-lane replay fits the staging block");
   bool onchip = R.perror.use_lds == 3 && plen <= 65535 && n_c <= 255 && 3*n_c+2*SCOMP+1 <= U16 && !R.eintvl.big;
   const int32_t *cinfo = wl;
+  unsigned long long *s_dep = s_blk+(SBLK/8-NDEP);
+  // The head's third group of loads.  n_c <= 255 with the flags on chip: four rows per lane at the most.
+  int cl_r[4] = { 0, 0, 0, 0 }, ci_r[4] = { 0, 0, 0, 0 };
+  task_res qr = { 0., 0., 0., -1, 0, 1, 0 };
+  if (R.perror.use_lds == 3)
+    { if (onchip)
+        {
+#pragma unroll
+          for (int j = 0; j < 4; j++)
+            if (j*WAVE+lane < n_c) { cl_r[j] = clist[j*WAVE+lane]; ci_r[j] = cinfo[j*WAVE+lane]; }
+        }
+      if (lane < n_t) qr = tres[lane];
+    }
+  // ... and under it: the memo's keys, the off-list walls' count, the first chunk's dependency masks
+  if (lane == 0) s_nx = 0;
+  for (int k = lane; k < LCAP0+LCAP1; k += WAVE)
+    s_mkey[k] = -1;
+  if (R.perror.use_lds == 3)
+    for (int q = lane; q < NDEP; q += WAVE) s_dep[q] = 0ull;
+  { const int hc = (int)R.perror.g.mask+1;
+    for (int e = 0; e < 2; e++)
+      if (!((R.perror.use_lds >> e) & 1))
+        for (int k = lane; k < hc; k += WAVE) R.perror.g.keys[(size_t)e*hc+k] = -1;
+  }
+  if (R.perror.use_lds == 3 && onchip)
+    {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        { const int q = j*WAVE+lane;
+          if (q < n_c) { F.pos[q] = (uint16_t)cl_r[j]; F.fo[q] = ((ci_r[j] >> 12) & CP_CF_WALLNOW) ? CP_W_WALL_O : 0; F.fs[q] = 0; }
+        }
+    }
+  wave_sync();
   auto flags_to_hbm = [&]()                             // the flags k_wall_tasks knew: OTHERS walls whatever the replay finds (cp_read_t::spec_wallnow)
     { for (int q = lane; q < n_c; q += WAVE)
         if ((cinfo[q] >> 12) & CP_CF_WALLNOW) wall[clist[q]] = CP_W_WALL_O;
       wave_sync();
     };
   if (R.perror.use_lds == 3)
-    { unsigned long long *s_dep = reinterpret_cast<unsigned long long *>(s_res)+(sizeof(task_res)*WAVE/sizeof(unsigned long long)-NDEP);
-      const uint64_t ltm = (1ull << lane)-1;
+    { const uint64_t ltm = (1ull << lane)-1;
       const int ecap = R.ecap;
       const bool ebig = R.eintvl.big != 0;
       int eidx = 0, oidx = 0, ovf = 0;
@@ -1290,30 +1356,36 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
           return off+(int)h;
         };
       for (;;)
-        { if (onchip)
-            { for (int q = lane; q < n_c; q += WAVE)
-                { F.pos[q] = (uint16_t)clist[q]; F.fo[q] = ((cinfo[q] >> 12) & CP_CF_WALLNOW) ? CP_W_WALL_O : 0; F.fs[q] = 0; }
-              wave_sync();
-            }
-          else flags_to_hbm();
+        { if (!onchip) flags_to_hbm();                   // (on chip: filled in the head)
           bool bail = false;
+#ifdef CP_PROF_WALK
+          if (lane == 0) { atomicAdd(&g_fw_prof[0],wall_clock64()-fw_t0); atomicAdd(&g_fw_prof[3],1ull); }
+#endif
           for (int tb = 0; tb < n_t; tb += WAVE)
             { const int nb = (n_t-tb < WAVE) ? n_t-tb : WAVE;
               bool open = lane < nb;
+#ifdef CP_PROF_WALK
+              const unsigned long long fw_t1 = wall_clock64();
+#endif
               int pos = 1, kc = 0, e = 0, w = 0, lc_j = -1, lc_kind = CP_LC_NONE, hc_j = -1;
               double own_pe = 0., lc_v = 0., hc_pe = 0.;
               if (open)
-                { const int code = tlist[tb+lane], k = code >> 1, cc = ccnt[k];
-                  const task_res q = tres[tb+lane];
-                  pos = clist[k]; kc = k; e = code & 1;
-                  w = (cc & 0xffff) > ((cc >> 16) & 0xffff) ? CP_DROP : CP_GAIN;
+                { if (tb > 0) qr = tres[tb+lane];             // (the first chunk's: loaded in the head)
+                  const task_res &q = qr;
+                  pos = q.pos; kc = q.kc; e = TR_E(q.hc); w = TR_WTYPE(q.hc);
                   own_pe = q.own_pe; lc_v = q.lc_v; hc_pe = q.hc_pe;
                   lc_j = q.lc_j; lc_kind = q.hc & 3;
                   hc_j = (q.hc & 4) ? pos+(q.hc >> 16) : -1;
                 }
+#ifdef CP_PROF_WALK
+              asm volatile("" :: "v"(pos), "v"(kc), "v"(e), "v"(w), "v"(lc_j), "v"(lc_kind), "v"(hc_j), "v"(own_pe), "v"(lc_v), "v"(hc_pe));
+              if (lane == 0) { atomicAdd(&g_fw_prof[1],wall_clock64()-fw_t1); atomicAdd(&g_fw_prof[2],1ull); }
+#endif
               const int p1 = (lc_kind == CP_LC_PAIR || lc_kind == CP_LC_BOUNDARY) ? lc_j : -1, p2 = hc_j;
-              for (int q = lane; q < NDEP; q += WAVE) s_dep[q] = 0ull;
-              wave_sync();
+              if (tb > 0)                                     // (the first chunk's masks: cleared in the head)
+                { for (int q = lane; q < NDEP; q += WAVE) s_dep[q] = 0ull;
+                  wave_sync();
+                }
               const int s0 = (int)((uint32_t)(pos*2+e)*0x9E3779B1u >> 25), s1 = (int)((uint32_t)(p1*2+e)*0x9E3779B1u >> 25),
                         s2 = (int)((uint32_t)(p2*2+e)*0x9E3779B1u >> 25);
               if (open)
@@ -1368,6 +1440,8 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
               for (uint64_t um = __ballot(open); um; um = __ballot(open))
                 { if (open && (dep & um) == 0)
                     { open = false;
+                      // (kc, the record's row, is read only here and below, under `onchip`, which holds only while n_c <= 255
+                      //  -- see its definition: the flag rows in LDS have no more)
                       const uint8_t fl = onchip ? ((e == CP_SELF) ? F.fs[kc] : F.fo[kc]) : ((e == CP_SELF) ? R.wall_s[pos] : wall[pos]);
                       if (!(fl & (e == CP_SELF ? CP_W_PAIRED_S : CP_W_PAIRED_O)))          // wall.c:639
                         { const int ci = memo_cell(pos,e,w);
@@ -1474,8 +1548,8 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
   {
   flags_to_hbm();
   // one-lane replay, 64 tasks at a time: the chunk's task results come from HBM into LDS, then the chunk is replayed in order,
-  //    lane 0 taking the SELF tasks and lane 1 the OTHERS tasks (one lane active per task; position and count pair
-  //    come from the loading lane's registers by readlane).
+  //    lane 0 taking the SELF tasks and lane 1 the OTHERS tasks (one lane active per task; its position and the `hc` word
+  //    with pass and wall type come from the loading lane's registers by readlane).
   if (lane < 2)
     { R.use_win = (P->K+24+CP_MAX_N_HC < 128) ? 1 : 0;
       R.win_base = 0; R.win_lo = R.win_hi = 0;
@@ -1483,24 +1557,26 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
     }
   for (int tb = 0; tb < n_t; tb += WAVE)
     { const int nb = (n_t-tb < WAVE) ? n_t-tb : WAVE;
-      int code_l = 0, cc_l = 0, pos_l = 1;
+      task_stage *s_st = reinterpret_cast<task_stage *>(s_blk);
+      int hc_l = 0, pos_l = 1;
       if (lane < nb)
-        { const int code = tlist[tb+lane], k = code >> 1;
-          code_l = code; cc_l = ccnt[k]; pos_l = clist[k];
-          s_res[lane] = tres[tb+lane];
+        { const task_res q = tres[tb+lane];
+          hc_l = q.hc; pos_l = q.pos;
+          task_stage t; t.own_pe = q.own_pe; t.lc_v = q.lc_v; t.hc_pe = q.hc_pe; t.lc_j = q.lc_j; t.hc = q.hc;
+          s_st[lane] = t;
         }
       wave_sync();
       for (int k = 0; k < nb; k++)
-        { const int code = __builtin_amdgcn_readlane(code_l,k), cc = __builtin_amdgcn_readlane(cc_l,k);
+        { const int hc = __builtin_amdgcn_readlane(hc_l,k);
           const int pos = __builtin_amdgcn_readlane(pos_l,k);
-          if (lane == (code & 1))
+          if (lane == TR_E(hc))
             { cp_cand_pure c;
-              const task_res &q = s_res[k];
+              const task_stage &q = s_st[k];
               c.flags = CP_CF_LIVE;
               c.own_pe = q.own_pe; c.lc_v = q.lc_v; c.hc_pe = q.hc_pe;
-              c.lc_j = q.lc_j; c.lc_kind = q.hc & 3;
-              c.hc_j = (q.hc & 4) ? pos+(q.hc >> 16) : -1;
-              cp_wall_candidate_replay(&R,pos,lane,(cc & 0xffff) > ((cc >> 16) & 0xffff) ? CP_DROP : CP_GAIN,c);
+              c.lc_j = q.lc_j; c.lc_kind = hc & 3;
+              c.hc_j = (hc & 4) ? pos+(hc >> 16) : -1;
+              cp_wall_candidate_replay(&R,pos,lane,TR_WTYPE(hc),c);
             }
         }
       wave_sync();
@@ -1528,7 +1604,7 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
 
   // ---- un-wall positions explained by O-pairs / inside E-intervals (wall.c:722-731) --------
   // From here on the lists of the walk are dead except the candidate positions (clist, second quarter of
-  // wl); s_res is reused for the short lists of the phases below.
+  // wl); the staging block is reused for the short lists of the phases below.
   int *s_cb = sbuf+SBUF-2*SCOMP, *s_ce = sbuf+SBUF-SCOMP;
   // positions fit 16 bits and the lists of this read fit the slots: O-only walls (<= n_c) during the multi-error search,
   // then the walls outside error regions (<= n_c) followed by the boundaries (<= n_c + 2*SCOMP + 1)
@@ -1995,7 +2071,7 @@ k_find_wall(const cp_dev_params *__restrict__ P, const char *__restrict__ seq, c
           };
         put(k0,b0,e0,c0,pe0,res0);
         if (base+WAVE < Ncl) put(k1,b1,e1,c1,pe1,res1);
-        EM_LT(4);
+        EM_LT(3);
       }
     if (do_rel && lane == 0) nrel[r] = M;
     // the rare size classes (M beyond the main class, or a read beyond GRP_MAX_PLEN k-mers: the one-read-per-wave and the

@@ -29,16 +29,19 @@ lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
 ur = (C.c_ulonglong * 8)()
 rp = (C.c_ulonglong * 12)()
+fw = (C.c_ulonglong * 12)()
 clf.classify(b)
 lib().cp_debug_unrel_prof(ur)
 lib().cp_debug_phase_prof(ph)
 lib().cp_debug_live_prof(lv)
 lib().cp_debug_emit_prof(em)
+lib().cp_debug_fw_prof(fw)
 clf.classify(b)
 lib().cp_debug_phase_prof(ph)
 lib().cp_debug_live_prof(lv)
 lib().cp_debug_emit_prof(em)
 lib().cp_debug_unrel_prof(ur)
+lib().cp_debug_fw_prof(fw)
 lib().cp_debug_rel_prof(rp)
 pn = {0: "k_wall_tasks: candidate list", 7: "k_wall_tasks: prelude + filters", 6: "k_wall_tasks: live tasks",
       1: "k_find_wall: replay", 2: "unwall/sort/olist", 3: "multi-error search", 4: "merge + sorts",
@@ -48,6 +51,10 @@ for k in (0, 7, 6, 1, 2, 3, 4, 8, 5):
     print("  %-34s %12d %12.1f      %d / %d" % (pn[k], ph[k], ph[12 + k] / b.nreads, ph[24 + k] >> 32, ph[24 + k] & 0xffffffff))
 print("replay chunks %d (%.1f tasks each): dependency rounds per chunk %.2f with the hashed table, %.2f with exact key comparisons"
       % (lv[2], lv[3] / max(1, lv[2]), lv[0] / max(1, lv[2]), lv[1] / max(1, lv[2])))
+print("k_find_wall, ticks per read (mean over all reads): head up to the first chunk %.1f (%d reads on the lane-parallel replay), chunk heads %.1f "
+      "(%d chunks, %.1f ticks each)" % (fw[0] / b.nreads, fw[3], fw[1] / b.nreads, fw[2], fw[1] / max(1, fw[2])))
+print("k_find_wall, emission loop, ticks per read: boundaries %.1f, cp_make_interval %.1f, find_rel %.1f, compaction and record stores %.1f"
+      % (fw[4] / b.nreads, fw[5] / b.nreads, fw[6] / b.nreads, fw[7] / b.nreads))
 print("E-interval lists of at most 64 (the wave-parallel forms): before the un-wall %d reads (mean length %.1f), before the merge %d (%.1f), before the components %d (%.1f)"
       % (em[0], em[1] / b.nreads, em[2], em[3] / b.nreads, em[4], em[5] / b.nreads))
 print("classify_unrel (main class): %.1f non-fixed intervals per read, %.1f speculation rounds in the first sweep (four slots per round), %.1f in the second"
