@@ -32,6 +32,7 @@ SYMBOLS = [
     "cp_kmer_sorted_read_runs", "cp_run_blocks",
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
     "cp_kmer_sorted_het_pairs",
+    "cp_kmer_sorted_unitigs", "cp_unitigs_count", "cp_unitigs_bases", "cp_unitigs_arrays", "cp_unitigs_destroy", "cp_unitig_n50",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -183,7 +184,17 @@ def lib():
     L.cp_kmer_sorted_compare_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.cp_kmer_qv.argtypes = [i32, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.cp_kmer_sorted_het_pairs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
-    L.cp_threshold_labels.argtypes = [i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.cp_kmer_sorted_unitigs.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+    L.cp_unitigs_count.argtypes = [vp]
+    L.cp_unitigs_count.restype = i64
+    L.cp_unitigs_bases.argtypes = [vp]
+    L.cp_unitigs_bases.restype = i64
+    L.cp_unitigs_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.cp_unitigs_destroy.argtypes = [vp]
+    L.cp_unitigs_destroy.restype = None
+    L.cp_unitig_n50.argtypes = [vp, i64]
+    L.cp_unitig_n50.restype = i64
+    L.cp_threshold_labels.argtypes =[i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]
     L.cp_acc_destroy.restype = None

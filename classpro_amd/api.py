@@ -920,6 +920,33 @@ class SortedKmers:
             res.append(out)
         return tuple(res)
 
+    def unitigs(self, count_range=None, adjacency=False, where=False, sequences=True):
+        """cp_kmer_sorted_unitigs ("Unitigs of sorted k-mers" in include/classpro_amd.h): the unitigs of the de Bruijn
+        graph of the keys of this snapshot.  Returns a `Unitigs`: len() unitigs, `.seq` (uint8, upper-case A C G T), `.off`
+        (int64 [len+1]), `.kc` (the exact sum of the counts of a unitig's nodes) and `.flag` (bit 0 = circular) as device
+        tensors, `.tally` a dict, `.strings()`.  `count_range` is (lo, hi) as in `combine`: a key outside it counts as
+        absent.  adjacency=True sets `.adj`, the adjacency byte of every entry (uint8); where=True sets `.utg` and `.at`,
+        the unitig of every entry and 2 * (its place in it) + (1 when spelled reversed), -1 for an entry that is not in.
+        sequences=False asks for no unitig object: with `where` the chains are still ranked and numbered (the tally is
+        complete), without it only the adjacency pass runs and the tally's unitig fields are 0.  The object owns its
+        memory and keeps no reference to the snapshot."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        rng = None
+        if count_range is not None:
+            lo, hi = count_range
+            rng = (C.c_int64 * 2)(1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi))
+        tally = (C.c_int64 * len(Unitigs.TALLY))()
+        adj = torch.zeros(self.n, dtype=torch.uint8, device=self.device) if adjacency else None
+        utg = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where else None
+        at = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where else None
+        ptr = lambda x: x.data_ptr() if x is not None and self.n else None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_unitigs(self.s, rng, tally, ptr(adj), ptr(utg), ptr(at), _stream_of(self.device),
+                                                C.byref(h) if sequences else None))
+        return Unitigs(self.L, self.device, self.K, h if sequences else None, dict(zip(Unitigs.TALLY, tally)), adj, utg, at)
+
     def hist(self):
         """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
         (1, 32767, ilowcnt, ihighcnt, int64[32767])."""
@@ -941,6 +968,64 @@ class SortedKmers:
             self.close()
         except Exception:
             pass
+
+
+class Unitigs:
+    """The result of `SortedKmers.unitigs` (a cp_unitigs and the per-entry tensors asked for).  The tensors `.seq`, `.off`,
+    `.kc` and `.flag` VIEW the object's device memory and keep it alive; `close()` frees it at once, after which a tensor
+    still held points at freed memory."""
+    TALLY = ("keys", "unitigs", "bases", "circular", "longest", "isolated", "tips", "branching", "arcs", "rounds", "jump_ns")
+
+    def __init__(self, L, device, K, handle, tally, adj, utg, at):
+        self.L, self.device, self.K, self.u, self.tally = L, device, K, handle, tally
+        self.adj, self.utg, self.at = adj, utg, at
+        self.n, self.bases, self._ptr = tally["unitigs"], tally["bases"], [None] * 4
+        if handle is not None:
+            self.n, self.bases = L.cp_unitigs_count(handle), L.cp_unitigs_bases(handle)
+            p = [C.c_void_p() for _ in range(4)]
+            check(L.cp_unitigs_arrays(handle, *[C.byref(x) for x in p]))
+            self._ptr = [x.value for x in p]
+
+    def __len__(self):
+        return self.n
+
+    def _view(self, which, n, typestr, dtype):
+        if self.u is None:
+            raise ValueError("Unitigs holds no sequences (sequences=False) or is closed")
+        if n == 0 or not self._ptr[which]:
+            return torch.zeros(n if which == 1 else 0, dtype=dtype, device=self.device)
+        iface = {"shape": (n,), "typestr": typestr, "data": (self._ptr[which], False), "version": 2, "strides": None}
+        holder = type("_UgView", (), {"__cuda_array_interface__": iface, "owner": self})()
+        return torch.as_tensor(holder, device=self.device)
+
+    seq = property(lambda self: self._view(0, self.bases, "|u1", torch.uint8))
+    off = property(lambda self: self._view(1, self.n + 1, "<i8", torch.int64))
+    kc = property(lambda self: self._view(2, self.n, "<i8", torch.int64))
+    flag = property(lambda self: self._view(3, self.n, "|u1", torch.uint8))
+
+    def strings(self):
+        """The sequences as a list of `str`, in order (everything comes to the host)."""
+        text, off = bytes(self.seq.cpu().numpy()).decode(), self.off.cpu().tolist()
+        return [text[off[u]:off[u + 1]] for u in range(self.n)]
+
+    def close(self):
+        if getattr(self, "u", None):
+            self.L.cp_unitigs_destroy(self.u)
+            self.u = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def unitig_n50(lengths):
+    """cp_unitig_n50: the largest L such that the unitigs of at least L bases hold at least half of all bases (0 for
+    none); `lengths` is any sequence or tensor of non-negative integers."""
+    v = lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths
+    v = np.ascontiguousarray(v, np.int64).reshape(-1)
+    return check(lib().cp_unitig_n50(v.ctypes.data if len(v) else None, len(v)))
 
 
 def bin_calls(hits, only_a, only_b, min_markers=1, normalise=True):

@@ -1207,5 +1207,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // heterozygous k-mer pairs of one sorted snapshot (tabhet): kmer_hetpairs.hip
 #include "kmer_hetpairs.hip"
 
+// unitigs of the de Bruijn graph of one sorted snapshot (tabunitig): kmer_unitigs.hip
+#include "kmer_unitigs.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

@@ -797,6 +797,81 @@ int     cp_kmer_sorted_het_pairs(const cp_kmer_sorted *s, const int64_t *range /
                                  void *stream, cp_kmer_sorted **out /* or NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Unitigs of sorted k-mers (tabunitig): the de Bruijn graph that ONE snapshot of canonical k-mers implies -- which k-mers
+ * follow which -- and its compaction: the maximal non-branching chains spelled as sequences, what BCALM and GGCAT produce
+ * and what every de Bruijn assembler builds on.  The definitions are this library's own.  Everything is in integers and
+ * independent of grid, block size and scheduling.
+ *
+ *   In         a key is IN when lo <= cnt <= hi with the snapshot's own d_cnt; `range` is a HOST array lo hi, NULL means
+ *              [1, INT64_MAX].  A key outside the range is treated exactly as if it were absent.  A key is the bases as a
+ *              2K-bit number, first base most significant, A C G T = 0 1 2 3; the keys are taken to be canonical.
+ *   State      the in entry with ordinal i has two states: 2i spells the key X, 2i+1 spells rc(X); flip(s) = s ^ 1.
+ *   Successor  for a state spelling w the successors are the strings w[1:]+c, c in A C G T, whose canonical form is in.
+ *              The successor STATE of such a string is 2j when the string equals key j and 2j+1 when it is key j's
+ *              reverse complement.  out(s) is the set of such c.  The predecessors of s are the flips of the successors
+ *              of flip(s).
+ *   d_adj      a DEVICE array of `size` bytes, overwritten: bit c of byte i is set iff c is in out(2i), bit 4+c iff c is in
+ *              out(2i+1); 0 for an entry that is not in.  For a palindromic key (X = rc(X), even K) the nibbles are equal.
+ *   Link       s -> t exists when out(s) has exactly one member and t is its state, out(flip(t)) has exactly one member
+ *              (which is then flip(s)), the node of t is not the node of s (no homopolymer loop t = s, no hairpin
+ *              t = flip(s)), and neither node is palindromic.  Every state has at most one link out and one in, and
+ *              s -> t exists iff flip(t) -> flip(s) does.
+ *   Unitig     a maximal chain of links, taken once for the chain and its mirror image; a chain never meets its own
+ *              mirror, so every in key lies in exactly one unitig, exactly once.
+ *   Spelling   of a path of n nodes: the first state's K bases, then the last base of each further state, n+K-1 bases.
+ *              With h the first state and e the last, the other strand starts at flip(e); the unitig is spelled from the
+ *              smaller of the states h and flip(e), that is from the end node with the smaller key; for n = 1 that is
+ *              state 2i, the canonical k-mer itself.  A closed chain (CIRCULAR) starts at its smallest node in the forward
+ *              state 2i, follows the links once round and is spelled open with n+K-1 bases.
+ *   Order      unitigs are numbered by ascending first state: the output is a function of the table and the range alone.
+ *   out        a cp_unitigs: count unitigs, d_off[count+1] the offsets of their sequences in d_seq (upper-case A C G T;
+ *              bases = d_off[count]; nodes of u = d_off[u+1]-d_off[u]-K+1), d_kc[u] the exact 64-bit sum of the counts of
+ *              its nodes, d_flag[u] bit 0 = circular.  All DEVICE arrays owned by the object, null when count = 0.  To be
+ *              destroyed by the caller; it keeps no reference to the snapshot.
+ *   d_utg d_at DEVICE arrays of `size` int64, overwritten: the unitig of entry i and 2*(its node index within the spelled
+ *              unitig) + (1 when the unitig spells the key's reverse complement); both -1 for an entry that is not in.
+ *   Tally      HOST int64 [CP_UTG_WIDTH]: CP_UTG_KEYS the in keys, CP_UTG_UNITIGS, CP_UTG_BASES, CP_UTG_CIRCULAR the closed
+ *              ones, CP_UTG_LONGEST the longest unitig in bases, CP_UTG_ISOLATED the in keys with adjacency byte 0,
+ *              CP_UTG_TIPS those with one empty nibble and one non-empty, CP_UTG_BRANCHING those with a nibble of two or
+ *              more bits, CP_UTG_ARCS the sum of the popcounts of all bytes.  Two fields are measurements and the only ones
+ *              that may depend on scheduling: CP_UTG_ROUNDS, the jump rounds of the ranking, and CP_UTG_JUMP_NS, the
+ *              nanoseconds of the host's clock that those rounds took, each waited for.
+ *   Passes     with out, d_utg and d_at all NULL only the adjacency pass runs (tally and/or d_adj); the UNITIGS, BASES,
+ *              CIRCULAR, LONGEST, ROUNDS and JUMP_NS fields are then 0.  With d_utg or d_at and no out the chains are ranked and
+ *              numbered and no sequence is written.
+ *   Operand    ready, any K a snapshot can have (2..63).  It is only read.  Lookups are those of "Sorted k-mers as input":
+ *              clamped ranges, at most 64 probes.  An empty table, or one with every key out of range, gives zero unitigs
+ *              and null arrays and is no error.
+ *   Errors     all before any launch: CP_EINVAL for a NULL s, an unready snapshot, tally, d_adj, d_utg, d_at and out all
+ *              NULL, a range with lo < 1 or hi < lo, and -- when unitigs are wanted -- a snapshot of more than 2^30 entries
+ *              (a state and a distance share one 64-bit word).  An allocation that fails is CP_ENOMEM with the byte count
+ *              in the message, nothing leaked.  After any error the contents of the outputs are unspecified.
+ *              Synchronises `stream`.
+ *   Memory     the adjacency pass alone: one byte per entry (none when d_adj is given).  With unitigs 33 bytes per entry
+ *              beside that byte: a 64-bit ranking word (resolved bit, distance, state) and a 32-bit link per state, a
+ *              64-bit ordinal and a head byte per entry; 8 bytes per tile of cp_ktab_tile() entries and per 4096 entries;
+ *              32 bytes per state on a closed chain, on the device and on the host, where closed chains are finished;
+ *              then the result: bases + 17 bytes per unitig.
+ *
+ * cp_unitig_n50: host only, no device involved.  The largest L such that the unitigs of at least L bases hold at least half
+ * of all bases; 0 for n = 0; CP_EINVAL for n < 0, a NULL len with n > 0 or a negative length.
+ */
+enum { CP_UTG_KEYS = 0, CP_UTG_UNITIGS = 1, CP_UTG_BASES = 2, CP_UTG_CIRCULAR = 3, CP_UTG_LONGEST = 4, CP_UTG_ISOLATED = 5,
+       CP_UTG_TIPS = 6, CP_UTG_BRANCHING = 7, CP_UTG_ARCS = 8, CP_UTG_ROUNDS = 9, CP_UTG_JUMP_NS = 10, CP_UTG_WIDTH = 11 };
+typedef struct cp_unitigs cp_unitigs;
+int     cp_kmer_sorted_unitigs(const cp_kmer_sorted *s, const int64_t *range /* host [2]: lo hi, or NULL */,
+                               int64_t *tally /* host [CP_UTG_WIDTH], or NULL */,
+                               uint8_t *d_adj /* device [size], overwritten, or NULL */,
+                               int64_t *d_utg, int64_t *d_at /* device [size] each, overwritten, or NULL */,
+                               void *stream, cp_unitigs **out /* or NULL */);
+int64_t cp_unitigs_count(const cp_unitigs *u);
+int64_t cp_unitigs_bases(const cp_unitigs *u);
+int     cp_unitigs_arrays(const cp_unitigs *u, const char **d_seq, const int64_t **d_off /* [count+1] */,
+                          const int64_t **d_kc, const uint8_t **d_flag);
+void    cp_unitigs_destroy(cp_unitigs *u);
+int64_t cp_unitig_n50(const int64_t *len, int64_t n);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
