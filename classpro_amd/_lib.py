@@ -33,6 +33,7 @@ SYMBOLS = [
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
     "cp_kmer_sorted_het_pairs",
     "cp_kmer_sorted_unitigs", "cp_unitigs_count", "cp_unitigs_bases", "cp_unitigs_arrays", "cp_unitigs_destroy", "cp_unitig_n50",
+    "cp_kmer_sorted_unitig_links", "cp_unitig_graph_links", "cp_unitig_graph_arrays", "cp_unitig_graph_destroy",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -194,6 +195,12 @@ def lib():
     L.cp_unitigs_destroy.restype = None
     L.cp_unitig_n50.argtypes = [vp, i64]
     L.cp_unitig_n50.restype = i64
+    L.cp_kmer_sorted_unitig_links.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(vp)]
+    L.cp_unitig_graph_links.argtypes = [vp]
+    L.cp_unitig_graph_links.restype = i64
+    L.cp_unitig_graph_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.cp_unitig_graph_destroy.argtypes = [vp]
+    L.cp_unitig_graph_destroy.restype = None
     L.cp_threshold_labels.argtypes =[i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

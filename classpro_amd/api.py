@@ -920,7 +920,7 @@ class SortedKmers:
             res.append(out)
         return tuple(res)
 
-    def unitigs(self, count_range=None, adjacency=False, where=False, sequences=True):
+    def unitigs(self, count_range=None, adjacency=False, where=False, sequences=True, links=False, components=False):
         """cp_kmer_sorted_unitigs ("Unitigs of sorted k-mers" in include/classpro_amd.h): the unitigs of the de Bruijn
         graph of the keys of this snapshot.  Returns a `Unitigs`: len() unitigs, `.seq` (uint8, upper-case A C G T), `.off`
         (int64 [len+1]), `.kc` (the exact sum of the counts of a unitig's nodes) and `.flag` (bit 0 = circular) as device
@@ -929,23 +929,43 @@ class SortedKmers:
         the unitig of every entry and 2 * (its place in it) + (1 when spelled reversed), -1 for an entry that is not in.
         sequences=False asks for no unitig object: with `where` the chains are still ranked and numbered (the tally is
         complete), without it only the adjacency pass runs and the tally's unitig fields are 0.  The object owns its
-        memory and keeps no reference to the snapshot."""
+        memory and keeps no reference to the snapshot.
+        links=True or components=True also calls cp_kmer_sorted_unitig_links ("Links between unitigs") with the same
+        range and the where arrays of the first call, made internally: `.loff` (int64 [2*len+1]), `.link` (the target
+        oriented unitig 2v+o of every arc) and `.base` (its base 0..3) as device tensors that view a second object,
+        `.link_tally` a dict, `.links()` the arcs as a host list of (x, c, y); components=True adds `.comp`, the smallest
+        unitig of every unitig's connected component, and fills the tally's components and largest_bases.  Both read the
+        ends of the sequences: with sequences=False they raise ValueError."""
         if self.s is None:
             raise ValueError("SortedKmers is closed")
         rng = None
         if count_range is not None:
             lo, hi = count_range
             rng = (C.c_int64 * 2)(1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi))
+        graph = links or components
+        if graph and not sequences:
+            raise ValueError("links and components are read off the ends of the sequences: sequences=False cannot have them")
         tally = (C.c_int64 * len(Unitigs.TALLY))()
         adj = torch.zeros(self.n, dtype=torch.uint8, device=self.device) if adjacency else None
-        utg = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where else None
-        at = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where else None
+        utg = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where or graph else None
+        at = torch.full((self.n,), -1, dtype=torch.int64, device=self.device) if where or graph else None
         ptr = lambda x: x.data_ptr() if x is not None and self.n else None
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             check(self.L.cp_kmer_sorted_unitigs(self.s, rng, tally, ptr(adj), ptr(utg), ptr(at), _stream_of(self.device),
                                                 C.byref(h) if sequences else None))
-        return Unitigs(self.L, self.device, self.K, h if sequences else None, dict(zip(Unitigs.TALLY, tally)), adj, utg, at)
+        U = Unitigs(self.L, self.device, self.K, h if sequences else None, dict(zip(Unitigs.TALLY, tally)), adj,
+                    utg if where else None, at if where else None)
+        if graph:
+            ltally, g = (C.c_int64 * len(Unitigs.LINK_TALLY))(), C.c_void_p()
+            with torch.cuda.device(self.device):
+                rc = self.L.cp_kmer_sorted_unitig_links(self.s, rng, h, ptr(utg), ptr(at), ltally, 1 if components else 0,
+                                                        _stream_of(self.device), C.byref(g))
+            if rc != 0:
+                U.close()
+            check(rc)
+            U._adopt_graph(g, dict(zip(Unitigs.LINK_TALLY, ltally)), components)
+        return U
 
     def hist(self):
         """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
@@ -973,8 +993,10 @@ class SortedKmers:
 class Unitigs:
     """The result of `SortedKmers.unitigs` (a cp_unitigs and the per-entry tensors asked for).  The tensors `.seq`, `.off`,
     `.kc` and `.flag` VIEW the object's device memory and keep it alive; `close()` frees it at once, after which a tensor
-    still held points at freed memory."""
+    still held points at freed memory.  With links= or components= it also holds a cp_unitig_graph, which `.loff`, `.link`,
+    `.base` and `.comp` view in the same way and `close()` frees with the first."""
     TALLY = ("keys", "unitigs", "bases", "circular", "longest", "isolated", "tips", "branching", "arcs", "rounds", "jump_ns")
+    LINK_TALLY = ("links", "dead_ends", "tip_unitigs", "isolated_unitigs", "self", "components", "largest_bases", "rounds")
 
     def __init__(self, L, device, K, handle, tally, adj, utg, at):
         self.L, self.device, self.K, self.u, self.tally = L, device, K, handle, tally
@@ -985,23 +1007,48 @@ class Unitigs:
             p = [C.c_void_p() for _ in range(4)]
             check(L.cp_unitigs_arrays(handle, *[C.byref(x) for x in p]))
             self._ptr = [x.value for x in p]
+        self.g, self.link_tally, self.nlinks, self._gptr, self._with_comp = None, None, 0, [None] * 4, False
+
+    def _adopt_graph(self, handle, tally, with_comp):
+        self.g, self.link_tally, self.nlinks, self._with_comp = handle, tally, self.L.cp_unitig_graph_links(handle), with_comp
+        p = [C.c_void_p() for _ in range(4)]
+        check(self.L.cp_unitig_graph_arrays(handle, *[C.byref(x) for x in p]))
+        self._gptr = [x.value for x in p]
 
     def __len__(self):
         return self.n
 
+    def _tensor(self, ptr, n, typestr, dtype, pad):
+        if n == 0 or not ptr:
+            return torch.zeros(pad, dtype=dtype, device=self.device)
+        iface = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+        holder = type("_UgView", (), {"__cuda_array_interface__": iface, "owner": self})()
+        return torch.as_tensor(holder, device=self.device)
+
     def _view(self, which, n, typestr, dtype):
         if self.u is None:
             raise ValueError("Unitigs holds no sequences (sequences=False) or is closed")
-        if n == 0 or not self._ptr[which]:
-            return torch.zeros(n if which == 1 else 0, dtype=dtype, device=self.device)
-        iface = {"shape": (n,), "typestr": typestr, "data": (self._ptr[which], False), "version": 2, "strides": None}
-        holder = type("_UgView", (), {"__cuda_array_interface__": iface, "owner": self})()
-        return torch.as_tensor(holder, device=self.device)
+        return self._tensor(self._ptr[which], n, typestr, dtype, n if which == 1 else 0)
+
+    def _gview(self, which, n, typestr, dtype):
+        if self.g is None or (which == 3 and not self._with_comp):
+            raise ValueError("Unitigs holds no links or no components (links=, components=) or is closed")
+        return self._tensor(self._gptr[which], n, typestr, dtype, n if which == 0 else 0)
 
     seq = property(lambda self: self._view(0, self.bases, "|u1", torch.uint8))
     off = property(lambda self: self._view(1, self.n + 1, "<i8", torch.int64))
     kc = property(lambda self: self._view(2, self.n, "<i8", torch.int64))
     flag = property(lambda self: self._view(3, self.n, "|u1", torch.uint8))
+    loff = property(lambda self: self._gview(0, 2 * self.n + 1, "<i8", torch.int64))
+    link = property(lambda self: self._gview(1, self.nlinks, "<i8", torch.int64))
+    base = property(lambda self: self._gview(2, self.nlinks, "|u1", torch.uint8))
+    comp = property(lambda self: self._gview(3, self.n, "<i8", torch.int64))
+
+    def links(self):
+        """The arcs as a list of (x, c, y) in order: the oriented unitig x = 2u+o reaches y by the base c (everything comes
+        to the host)."""
+        loff, link, base = self.loff.cpu().tolist(), self.link.cpu().tolist(), self.base.cpu().tolist()
+        return [(x, base[k], link[k]) for x in range(2 * self.n) for k in range(loff[x], loff[x + 1])]
 
     def strings(self):
         """The sequences as a list of `str`, in order (everything comes to the host)."""
@@ -1012,6 +1059,9 @@ class Unitigs:
         if getattr(self, "u", None):
             self.L.cp_unitigs_destroy(self.u)
             self.u = None
+        if getattr(self, "g", None):
+            self.L.cp_unitig_graph_destroy(self.g)
+            self.g = None
 
     def __del__(self):
         try:

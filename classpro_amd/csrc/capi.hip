@@ -1210,5 +1210,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // unitigs of the de Bruijn graph of one sorted snapshot (tabunitig): kmer_unitigs.hip
 #include "kmer_unitigs.hip"
 
+// links between those unitigs and the components of their graph (tabgraph): kmer_unitig_graph.hip
+#include "kmer_unitig_graph.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

@@ -872,6 +872,68 @@ void    cp_unitigs_destroy(cp_unitigs *u);
 int64_t cp_unitig_n50(const int64_t *len, int64_t n);
 
 /* ------------------------------------------------------------------------------------------
+ * Links between unitigs (tabgraph): which unitig follows which, in which orientation, and the connected components of
+ * the graph they form -- the edges that BCALM ships as L:+:id:- header fields and that GFA writes as L lines.  Builds on
+ * "Unitigs of sorted k-mers" and uses its words State, out(s), Successor, flip and path.  Everything is in integers and,
+ * but for CP_UGL_ROUNDS, independent of grid, block size and scheduling.
+ *
+ *   Oriented   x = 2u + o: o = 0 ('+') is unitig u as spelled, o = 1 ('-') its reverse complement; x ^ 1 is the other
+ *              strand.
+ *   Ends       with p[0..n-1] the states of u's spelled path: end(2u) = p[n-1], end(2u+1) = flip(p[0]) and
+ *              start(x) = flip(end(x ^ 1)), so start(2u) = p[0] and start(2u+1) = flip(p[n-1]).  For a one-node unitig
+ *              with path [s] the two starts are s and flip(s).
+ *   Arc        x -> y with base c exists iff c is in out(end(x)) and the successor state of that string is start(y).
+ *              Every successor state of an end state is the start of exactly one oriented unitig (this follows from
+ *              Link): with the successor state t = 2j + b and r = d_at[j] & 1, y = 2 * d_utg[j] + (b ^ r); the node index
+ *              d_at[j] >> 1 is 0 when b == r and n-1 otherwise.  The overlap of every arc is K-1 bases.
+ *   Hence      a circular unitig has exactly the two arcs 2u -> 2u and 2u+1 -> 2u+1.  A homopolymer node has self arcs, a
+ *              hairpin gives 2u -> 2u+1.  A palindromic node is a one-node unitig spelled in state 2i: both orientations
+ *              carry the same out-arcs and every arc into it lands on '+'.  Off palindromic nodes x -> y exists iff
+ *              y^1 -> x^1 does.  LINKS == CP_UTG_ARCS - 2 * (CP_UTG_KEYS - CP_UTG_UNITIGS).
+ *   Order      arcs are sorted by source x ascending, then by c ascending: a function of the table and the range alone.
+ *   Component  comp[u] is the smallest unitig ordinal in u's connected component, arcs taken as undirected and
+ *              orientation ignored.
+ *   Arguments  `range` is the one given to cp_kmer_sorted_unitigs; u, d_utg and d_at are the object and the where arrays
+ *              of THAT call on THIS snapshot (device, `size` int64 each).  Arrays of another call give unspecified arcs
+ *              but never an access outside the arrays: a unitig read from them is clamped to [0, count).  The snapshot,
+ *              u and the two arrays are only read.
+ *   out        a cp_unitig_graph: d_loff[2*count+1] the offsets of the arcs of every oriented unitig, d_link[links] the
+ *              target y and d_base[links] the base c (0..3) of every arc, d_comp[count] the components (null without
+ *              want_comp).  DEVICE arrays owned by the object, all null when count = 0 (zero unitigs give zero links and
+ *              are no error), d_link and d_base also when links = 0.  To be destroyed by the caller; it keeps no
+ *              reference to the snapshot or to u.
+ *   Tally      HOST int64 [CP_UGL_WIDTH]: CP_UGL_LINKS; CP_UGL_DEAD_ENDS the oriented unitigs without an arc;
+ *              CP_UGL_TIP_UNITIGS the unitigs with exactly one of their two orientations dead; CP_UGL_ISOLATED_UNITIGS
+ *              those with both dead; CP_UGL_SELF the arcs whose target unitig is the source's; CP_UGL_COMPONENTS and
+ *              CP_UGL_LARGEST_BASES, the largest sum of unitig bases over a component, both 0 without want_comp;
+ *              CP_UGL_ROUNDS, a measurement and the only field that may depend on scheduling: the label rounds, the
+ *              last, which changes nothing, included (0 without want_comp or without links).
+ *   Passes     one lane per oriented unitig reads the K bases at its end and makes its four look-ups, one search after
+ *              the other, by the bounded search of "Sorted k-mers as input": 8 look-ups per unitig, not per k-mer.  The
+ *              components are label rounds -- a 64-bit atomic minimum of agent scope per arc, then every label replaced
+ *              by its label's label to a fixed point -- until a round lowers nothing, at most count rounds and no
+ *              smaller cap; the result is the component's minimum whatever the scheduling (kmer_unitig_graph.hip).
+ *   Errors     all before any launch: CP_EINVAL for a NULL s or u, NULL d_utg or d_at with count > 0, an unready
+ *              snapshot, a u whose K differs from the snapshot's, a range with lo < 1 or hi < lo, tally and out both
+ *              NULL.  An allocation that fails is CP_ENOMEM with the byte count in the message, nothing leaked.  A given
+ *              `out` is cleared on every error.  Synchronises `stream`.
+ *   Memory     scratch: 64 bytes per unitig (four staged targets per orientation), 8 more with want_comp, 8 bytes per
+ *              4096 oriented unitigs and under 200 bytes of counters.  Result: 16 bytes per unitig + 8, 9 bytes per link, and 8
+ *              bytes per unitig with want_comp.
+ */
+enum { CP_UGL_LINKS = 0, CP_UGL_DEAD_ENDS = 1, CP_UGL_TIP_UNITIGS = 2, CP_UGL_ISOLATED_UNITIGS = 3, CP_UGL_SELF = 4,
+       CP_UGL_COMPONENTS = 5, CP_UGL_LARGEST_BASES = 6, CP_UGL_ROUNDS = 7, CP_UGL_WIDTH = 8 };
+typedef struct cp_unitig_graph cp_unitig_graph;
+int     cp_kmer_sorted_unitig_links(const cp_kmer_sorted *s, const int64_t *range /* host [2] or NULL, the one given to _unitigs */,
+                                    const cp_unitigs *u, const int64_t *d_utg, const int64_t *d_at /* device [size], of the call that made u */,
+                                    int64_t *tally /* host [CP_UGL_WIDTH], or NULL */, int want_comp,
+                                    void *stream, cp_unitig_graph **out /* or NULL */);
+int64_t cp_unitig_graph_links(const cp_unitig_graph *g);
+int     cp_unitig_graph_arrays(const cp_unitig_graph *g, const int64_t **d_loff /* [2*count+1] */, const int64_t **d_link /* [links]: y */,
+                               const uint8_t **d_base /* [links]: c */, const int64_t **d_comp /* [count], null without want_comp */);
+void    cp_unitig_graph_destroy(cp_unitig_graph *g);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
