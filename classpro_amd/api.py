@@ -854,6 +854,71 @@ class SortedKmers:
         tail = buf.view(torch.int32)[:, 6:]
         return run_off, {"first": buf[:, 0], "last": buf[:, 1], "n": buf[:, 2], "read": tail[:, 0], "state": tail[:, 1]}
 
+    PATH_TALLY = ("positions", "present", "absent", "other", "segments", "joined", "walks")
+
+    def read_paths(self, U, batch, coverage=None, support=None, capacity=None):
+        """cp_kmer_sorted_read_paths ("Reads through the unitig graph" in include/classpro_amd.h): the k-mer positions of a
+        `Batch` or of a tuple of device tensors (seq uint8, seq_off int64 [n+1]) located in the unitigs `U` of this
+        snapshot -- a `Unitigs` made by `unitigs(where=True)`; `support` also needs `links=True` -- and reduced to segments
+        on the device.  Returns (seg_off, segs, tally): seg_off an int64 device tensor [n+1], the segments of read r
+        being records seg_off[r] .. seg_off[r+1]; segs a dict of device tensors "first", "x" (int64) and "n", "q", "read",
+        "flags" (int32); tally a dict of PATH_TALLY.  coverage=True / support=True allocate zeroed int64 tensors [len(U)]
+        / [U.nlinks] and return them as tally["coverage"] / tally["support"]; a tensor passed instead is added to and
+        returned there.  One call with a guessed capacity (`capacity` records when given, else one per 16 bases), one
+        more at the exact size when that was too small (the call that overflows adds nothing to either tensor)."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if not isinstance(U, Unitigs) or U.u is None:
+            raise ValueError("U must be a Unitigs that holds its sequences")
+        if U.K != self.K or U.device != self.device:
+            raise ValueError("the unitigs must be of this snapshot's K and device")
+        if U.utg is None or U.at is None or U.utg.numel() != self.n:
+            raise ValueError("the unitigs must be made with where=True from this snapshot")
+        want_sup = support is not None and support is not False
+        want_cov = coverage is not None and coverage is not False
+        if want_sup and U.g is None:
+            raise ValueError("support needs unitigs made with links=True")
+        cov = sup = None
+        if want_cov:
+            cov = torch.zeros(len(U), dtype=torch.int64, device=self.device) if coverage is True else coverage
+            if cov.dtype != torch.int64 or cov.dim() != 1 or cov.numel() != len(U) or cov.device != self.device or not cov.is_contiguous():
+                raise ValueError("coverage must be a contiguous int64 tensor of len(U) on the snapshot's device")
+        if want_sup:
+            sup = torch.zeros(U.nlinks, dtype=torch.int64, device=self.device) if support is True else support
+            if sup.dtype != torch.int64 or sup.dim() != 1 or sup.numel() != U.nlinks or sup.device != self.device or not sup.is_contiguous():
+                raise ValueError("support must be a contiguous int64 tensor of U.nlinks on the snapshot's device")
+        if isinstance(batch, Batch):
+            seq, seq_off, n, total = batch.seq, batch.seq_off, batch.nreads, batch.total_bases
+        else:
+            seq, seq_off = batch
+            n = seq_off.numel() - 1
+            total = int(seq_off[-1].item()) if n > 0 else 0
+        seg_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=self.device)
+        capacity = max(1024, total // 16) if capacity is None else max(int(capacity), 1)
+        count = C.c_int64()
+        tally = (C.c_int64 * len(self.PATH_TALLY))()
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+        with torch.cuda.device(self.device):
+            for _ in range(2):
+                buf = torch.empty((capacity, 4), dtype=torch.int64, device=self.device)
+                rc = self.L.cp_kmer_sorted_read_paths(self.s, U.u, ptr(U.utg), ptr(U.at), U.g if want_sup else None,
+                                                      seq.data_ptr(), seq_off.data_ptr(), n, total, buf.data_ptr(), capacity,
+                                                      seg_off.data_ptr(), ptr(cov), ptr(sup), tally, C.byref(count),
+                                                      _stream_of(self.device))
+                if rc != CP_EOVERFLOW:                     # count is exact: once more at that size
+                    break
+                capacity = count.value
+            check(rc)
+        buf = buf[:count.value]
+        tail = buf.view(torch.int32)[:, 4:]
+        res = dict(zip(self.PATH_TALLY, tally))
+        if want_cov:
+            res["coverage"] = cov
+        if want_sup:
+            res["support"] = sup
+        return seg_off, {"first": buf[:, 0], "x": buf[:, 1], "n": tail[:, 0], "q": tail[:, 1], "read": tail[:, 2],
+                         "flags": tail[:, 3]}, res
+
     def compare(self, other, a_range=None, b_range=None):
         """(only_a, only_b, both): the tally of `combine` with nothing built (cp_kmer_sorted_combine with out == NULL)."""
         return self._combine(other, "and", "left", a_range, b_range, False)[1][:3]
@@ -1076,6 +1141,30 @@ def unitig_n50(lengths):
     v = lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths
     v = np.ascontiguousarray(v, np.int64).reshape(-1)
     return check(lib().cp_unitig_n50(v.ctypes.data if len(v) else None, len(v)))
+
+
+def path_walks(seg_off, segs, nodes, K):
+    """The walks of the segments that `SortedKmers.read_paths` returned, on the host: a maximal chain of a read's segments in
+    which every one but the first is joined.  `nodes` holds the number of nodes of every unitig (`U.off[1:] - U.off[:-1]
+    - (K-1)`); tensors, arrays and lists are taken alike.  Returns a list of (read, first, end, path, path_length, q) in
+    read order -- the GAF fields: the bases [first, end) of the read run along `path` (">u" / "<u" per segment) from base
+    q of the path on, path_length being the bases of its unitigs less K-1 per join."""
+    host = lambda v: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).tolist()
+    off, nodes, K = host(seg_off), host(nodes), int(K)
+    cols = [host(segs[k]) for k in ("first", "n", "x", "q", "read", "flags")]
+    out = []
+    for r in range(len(off) - 1):
+        for i in range(off[r], off[r + 1]):
+            first, n, x, q, read, flags = (c[i] for c in cols)
+            if read != r:
+                raise ValueError("segment %d is of read %d, not of read %d" % (i, read, r))
+            step = ("<" if x & 1 else ">") + str(x >> 1)
+            if (flags & 1) and i > off[r]:
+                w = out[-1]
+                w[2], w[3], w[4] = first + n + K - 1, w[3] + step, w[4] + nodes[x >> 1]
+            else:
+                out.append([r, first, first + n + K - 1, step, nodes[x >> 1] + K - 1, q])
+    return [tuple(w) for w in out]
 
 
 def bin_calls(hits, only_a, only_b, min_markers=1, normalise=True):

@@ -1213,5 +1213,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // links between those unitigs and the components of their graph (tabgraph): kmer_unitig_graph.hip
 #include "kmer_unitig_graph.hip"
 
+// reads threaded through that graph: segments, coverage and arc support (tabpath): kmer_paths.hip
+#include "kmer_paths.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

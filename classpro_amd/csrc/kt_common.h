@@ -114,6 +114,47 @@ __device__ static inline void kt_walk_all(const char *seq, const int64_t *seq_of
     }
 }
 
+// The canonical walk for callers that must know WHICH strand gave the key: calls f(r, j, ok, hi, lo, rc_won) for every
+// k-mer position; rc_won says that the reverse complement is strictly the smaller of the two strings, so it is false for a
+// palindromic k-mer (and meaningless, like the key, when ok is false).  Positions and keys are those of kt_walk_all<true>.
+template <class F>
+__device__ static inline void kt_walk_strand(const char *seq, const int64_t *seq_off, int nreads, int64_t total, int K,
+                                             int64_t p0, F f)
+{ const int64_t p1 = min(p0+(int64_t)KT_CHUNK,total);
+  int lo_r = 0, hi_r = nreads;                          // the read holding p0: seq_off[r] <= p0 < seq_off[r+1]
+  while (hi_r-lo_r > 1)
+    { const int mid = (lo_r+hi_r) >> 1;
+      if (seq_off[mid] <= p0) lo_r = mid; else hi_r = mid;
+    }
+  const kt_u128 kmask = (((kt_u128)1) << (2*K))-1;
+  const int rshift = 2*K-2;
+  int r = lo_r;
+  for (int64_t p = p0; p < p1 && r < nreads; r++)
+    { const int64_t rs = seq_off[r], re = seq_off[r+1];
+      if (re <= p) continue;                            // empty reads
+      const int64_t q1 = min(p1,re);
+      const int64_t first = max(p,rs+K-1);
+      if (first < q1)
+        { kt_u128 fw = 0, rc = 0;
+          int valid = 0;
+          for (int64_t j = first-K+1; j < q1; j++)
+            { const int b = kt_base((unsigned char)seq[j]);
+              if (b < 0) { valid = 0; fw = 0; rc = 0; }
+              else
+                { fw = ((fw << 2) | (kt_u128)b) & kmask;
+                  rc = (rc >> 2) | (((kt_u128)(3-b)) << rshift);
+                  valid++;
+                }
+              if (j < first) continue;
+              const bool won = rc < fw;
+              const kt_u128 key = won ? rc : fw;
+              f(r,j,valid >= K,(unsigned long long)(key >> 63),(unsigned long long)key & KT_M63,won);
+            }
+        }
+      p = q1;
+    }
+}
+
 // The same walk for callers that only want the k-mers of upper-case A C G T: calls f(j, hi, lo) for each of them and
 // returns the number of the others.
 template <bool CANON, class F>

@@ -934,6 +934,86 @@ int     cp_unitig_graph_arrays(const cp_unitig_graph *g, const int64_t **d_loff 
 void    cp_unitig_graph_destroy(cp_unitig_graph *g);
 
 /* ------------------------------------------------------------------------------------------
+ * Reads through the unitig graph (tabpath): the k-mer positions of a batch in the flat layout above, looked up in ONE
+ * snapshot and located in its unitigs, reduced on the device to the stretches that run along one oriented unitig -- which
+ * way a read or a contig runs through the compacted de Bruijn graph, the read coverage of every unitig and the read
+ * support of every arc.  Builds on "Unitigs of sorted k-mers" and "Links between unitigs" and uses their words State,
+ * Link, Oriented, Ends and Arc.  Only the segments come down, never a value per base.  Every key is rolled once and looked
+ * up once.  Everything is in integers.
+ *
+ *   Step       of k-mer position i of a read (k-mer i covers the bases [i, i+K)), with w the forward k-mer and
+ *              X = min(w, rc(w)): OTHER when w holds a byte other than upper-case A C G T; ABSENT when X is not found, or is
+ *              found at entry e with d_utg[e] < 0 -- an entry outside the range given to cp_kmer_sorted_unitigs is absent
+ *              in this way, so this call needs no range of its own; otherwise the step is (x, q): with b = (w != X),
+ *              u = d_utg[e], k = d_at[e] >> 1, r = d_at[e] & 1 and n the nodes of u, x = 2u + (b ^ r), and q = k when
+ *              b == r, else n-1-k.  q is the place of the position in the oriented unitig x.  A palindromic key has b = 0.
+ *   Segment    a maximal stretch of consecutive positions of one read, with no position between them, whose steps are
+ *              (x, q), (x, q+1), ...  Its record: `first` the ordinal in the read of its first position, `n` the number
+ *              of its positions, `x`, `q` of the first position, `read` the read's index in the batch, `flags`.  Bit 0 of
+ *              flags (CP_PATH_JOINED_FLAG) is JOINED: the position first-1 of the same read is a step as well.  A closed unitig run
+ *              round twice gives two segments, the second joined (the self arc 2u -> 2u); nothing is special-cased.
+ *   Joins      a joined segment follows a segment that ends at the last place of its unitig, starts at place 0, and the arc
+ *              x_prev -> x whose base is the read's base at first+K-1 exists: this follows from Link and Arc.
+ *   Spelling   read[first : first+n+K-1] equals the sequence of the oriented unitig x at [q : q+n+K-1].
+ *   Mirror     the segments of rc(read) are those of the read in reverse order with first' = nk-first-n (nk the k-mer
+ *              positions of the read), q' = nodes-q-n and x' = x ^ 1, but x' = x for the one-node unitig of a palindromic
+ *              key.
+ *   Walk       a maximal chain of a read's segments in which every segment but the first is joined (host side: GAF).
+ *   Output     d_seg_off[r] .. d_seg_off[r+1] are the records of read r in d_segs, ascending in `first`; all nreads+1
+ *              offsets are overwritten, and *total (HOST) = d_seg_off[nreads].  Reads shorter than K, empty reads and
+ *              nreads == 0 give no segments and are no error.  n and q fit 32 bits, because unitigs exist only for
+ *              snapshots of at most 2^30 entries.
+ *   Capacity   d_segs holds `capacity` records.  With *total > capacity the call returns CP_EOVERFLOW; d_seg_off, *total and
+ *              the tally are exact all the same, the records below `capacity` are written and nothing beyond them is
+ *              touched.  d_segs == NULL with capacity == 0 is the counting call.
+ *   Sums       d_cov[u] += n per segment of unitig u; d_support[a] += 1 per joined segment, a the arc in
+ *              d_loff[x_prev] .. d_loff[x_prev+1] of g whose base is the read's.  Both are ADDED TO, so a caller
+ *              accumulates over batches, and only by a call that returns CP_OK: a call that overflows adds nothing, so the
+ *              call that is made again at the exact size does not add twice.  Exact 64-bit integer sums, independent of
+ *              batching, read order, grid and scheduling.  d_support counts the direction the reads were given in; the
+ *              strand-free support of an edge is its own plus its mirror arc's.
+ *   Tally      HOST int64 [CP_PATH_WIDTH], overwritten: CP_PATH_POSITIONS the k-mer positions, CP_PATH_PRESENT those that
+ *              are steps, CP_PATH_ABSENT, CP_PATH_OTHER, CP_PATH_SEGMENTS (= *total), CP_PATH_JOINED, CP_PATH_WALKS
+ *              (= SEGMENTS - JOINED).
+ *   Fixed      the records of a read are a function of the read, the snapshot and the unitigs alone: not of what else is in
+ *              the batch, of the order of the reads, or of the grid, block and chunk sizes of the kernels.
+ *   Arguments  u, d_utg and d_at are the object and the where arrays (device, `size` int64 each) of ONE call of
+ *              cp_kmer_sorted_unitigs on THIS snapshot, g the graph made from them (or NULL; needed for d_support).  Where
+ *              arrays or a g of another call give unspecified records and sums but never an access outside an array: a
+ *              unitig, an oriented unitig and an arc read from them are clamped.  Everything passed in is only read, but
+ *              d_cov (`count` int64) and d_support (`links` int64).
+ *   Errors     all before any launch: CP_EINVAL for a NULL s, u or total, an unready snapshot, a u of another K, NULL where
+ *              arrays with count > 0, d_support without g, a negative nreads, total_bases or capacity, a null device pointer
+ *              where there is work (d_segs with capacity > 0, d_seg_off and d_seq_off with nreads > 0, d_seq with
+ *              total_bases > 0).
+ *   Memory     scratch of 8 bytes per base of the batch, 32 bytes per 16384 bases and 64 bytes more, allocated and freed in
+ *              stream order per call; when that fails it is CP_ENOMEM with the byte count in the message.  Nothing is
+ *              queued on `stream` before that allocation has succeeded.
+ *   Cost       one pass of lookups that stores a 64-bit word per base, and two passes over those words.  Reads without a
+ *              k-mer position are serialised in single lanes as in "Runs of k-mer states along reads".  One 64-bit atomic
+ *              per segment: reads that pile on one repeat unitig add to one address.
+ * Synchronises `stream`: the total must be known to return it.
+ *
+ * cp_count_nonzero: *count (HOST) = the number of values of the DEVICE array d_v[0..n) that are not zero -- the unitigs
+ * touched of a d_cov, the arcs crossed of a d_support -- so that only the number comes down.  CP_EINVAL for a NULL count,
+ * n < 0 or a NULL d_v with n > 0.  Synchronises `stream`.
+ */
+enum { CP_PATH_POSITIONS = 0, CP_PATH_PRESENT = 1, CP_PATH_ABSENT = 2, CP_PATH_OTHER = 3, CP_PATH_SEGMENTS = 4,
+       CP_PATH_JOINED = 5, CP_PATH_WALKS = 6, CP_PATH_WIDTH = 7 };
+enum { CP_PATH_JOINED_FLAG = 1 };
+typedef struct cp_path_seg { int64_t first, x; int32_t n, q, read, flags; } cp_path_seg;   /* 32 bytes */
+int     cp_kmer_sorted_read_paths(const cp_kmer_sorted *s, const cp_unitigs *u,
+                                  const int64_t *d_utg, const int64_t *d_at /* device [size], of the call that made u */,
+                                  const cp_unitig_graph *g /* or NULL; needed for d_support */,
+                                  const char *d_seq, const int64_t *d_seq_off, int nreads, int64_t total_bases,
+                                  cp_path_seg *d_segs /* device [capacity], or NULL */, int64_t capacity,
+                                  int64_t *d_seg_off /* device [nreads+1], overwritten */,
+                                  int64_t *d_cov /* device [count], added to, or NULL */,
+                                  int64_t *d_support /* device [links], added to, or NULL */,
+                                  int64_t *tally /* host [CP_PATH_WIDTH], or NULL */, int64_t *total /* host */, void *stream);
+int     cp_count_nonzero(const int64_t *d_v, int64_t n, int64_t *count /* host */, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
