@@ -865,6 +865,56 @@ CP_HD int cp_sum_steps(const PROF &prof, int lo, int hi, int plen, int sgn)
   return acc;
 }
 
+// Both sums of one end of an interval in one pass over the forty counts prof[at .. at+39], all inside the read (the caller
+// sees to that): five wide loads issued together, every step d = cur-prev taken once and added to the upward sum, the
+// downward sum, both or neither by its number j alone.  Step 0 leads from `lead` to prof[at], step j from prof[at+j-1]
+// to prof[at+j].
+//   HEAD (the begin of an interval): the upward sum takes the steps j < nu, the downward one the steps j < nd;
+//   else (its end): step 0 does not exist (lead is not looked at), upward are the steps j >= nu, downward j >= nd.
+// The terms are those of cp_sum_steps over the same ranges, in the same order.
+template <bool HEAD, class PROF>
+CP_HD void cp_sum_steps_pair(const PROF &prof, int at, int lead, int nu, int nd, int *up, int *dn)
+{ cp_u16x8 x[5];
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int g = 0; g < 5; g++) x[g] = cp_load_u16x8(prof,at+8*g);
+  int u = 0, w = 0, prev = lead;
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int g = 0; g < 5; g++)
+    {
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+      for (int q = 0; q < 8; q++)
+        { const int j = 8*g+q, cur = x[g].v[q], d = cur-prev;
+          if (HEAD || j > 0)
+            { if ((HEAD ? j < nu : j >= nu) && d > 0) u += d;
+              if ((HEAD ? j < nd : j >= nd) && d < 0) w -= d;
+            }
+          prev = cur;
+        }
+#ifdef __HIP_DEVICE_COMPILE__
+      // (both sums exist after every eight steps: left alone, the compiler forms all eighty masked terms first and
+      //  adds them as a tree, eighty registers in a kernel that has six to spare)
+      asm volatile("" : "+v"(u), "+v"(w));
+#endif
+    }
+  *up = u; *dn = w;
+}
+
+// the longest of the three low-complexity contexts of a position, in bases (wall.c:972-975, 988-991)
+CP_HD int cp_lmax3(const int *l3)
+{ int lmax = 0;
+  for (int t = 0; t < 3; t++)
+    { const int l = l3[t]*(t+1);
+      if (lmax < l) lmax = l;
+    }
+  return lmax;
+}
+
 // correct_wall_cnt + the filters of find_rel_intvl, wall.c:960-1051, for interval `idx`.
 // The reference's position-indexed loops at wall.c:999-1006 only ever touch the interval itself when
 // its index equals its start position (SURVEY.md hazard 2); that case is applied explicitly.
@@ -895,42 +945,63 @@ CP_HD bool cp_rel_counts(const cp_dev_params *P, const PROF &prof, const SEQB &s
   const auto wseq_b = cp_seq_window(seq_b,Ib+K-1,rlen,+1);     // rctx scans start here and go right (and a little to the left)
   const auto wseq_e = cp_seq_window(seq_e,Ie-1,rlen,-1);       // lctx scans start here and go left
 
-  int first, last, n_gain = 0, n_drop = 0, lmax;
+  int first, last, n_gain = 0, n_drop = 0, lmax_b = 0, lmax_e = 0;
   const int plen = rlen-(K-1);
-  last = (Ib+K-1 < Ie-1) ? Ib+K-1 : Ie-1;
-  n_gain += cp_sum_steps(prof,Ib,last,plen,+1);
-  CP_ET(5);
-  if (Ib+K-1 < Ie)
-    { lmax = 0;
-      int l3[3];
+  // Both contexts first: they need the two windows alone, and each decides which counts of its end the second sum of
+  // that end walks -- almost always a sub-range of what the first sum of the end loads.
+  const bool two = Ib+K-1 < Ie;                            // (the same test as Ib < Ie-K+1: both sums of both ends exist)
+  if (two)
+    { int l3[3];
       cp_rctx3(wseq_b,rlen,Ib+K-1,l3);
-      for (int t = 0; t < 3; t++)
-        { int l = l3[t]*(t+1);
-          if (lmax < l) lmax = l;
-        }
-      last = Ib+lmax;
-      n_gain -= cp_sum_steps(prof,Ib,last,plen,-1);
-    }
-  first = (Ie-K+1 > Ib) ? Ie-K+1 : Ib;
-  n_drop += cp_sum_steps(prof,first,Ie-1,plen,-1);
-  if (Ib < Ie-K+1)
-    { lmax = 0;
-      int l3[3];
+      lmax_b = cp_lmax3(l3);
       cp_lctx3(wseq_e,rlen,(Ie-K+1)+K-2,l3);                 // ctx[DROP][e-K+1]
-      for (int t = 0; t < 3; t++)
-        { int l = l3[t]*(t+1);
-          if (lmax < l) lmax = l;
+      lmax_e = cp_lmax3(l3);
+    }
+  // An end whose two sums lie within forty counts inside the read takes them in one pass (cp_sum_steps_pair); an `lmax`
+  // of a fall-back scan beyond K-1, K > 41, an interval of fewer than K positions (the prefilter lets none through) and
+  // a group that would leave the read go sum by sum as before (counts at or beyond plen read 0 there).
+  const bool pairs = two && K-1 <= 40;
+  // The begin: upward over [Ib, Ib+K-1), downward over [Ib, Ib+lmax_b).  For K <= 40 the group starts at the lead
+  // count itself (step 0 is Icb -> prof[Ib], nothing), so that it ends at Ib+39 < Ib+K <= Ie: an interval that passed the
+  // length test holds it whole when K = 40; for K = 41 it is prof[Ib+1 .. Ib+40], and Ib+41 <= Ie.
+  const int sb = (K-1 <= 39) ? 1 : 0;
+  if (pairs && lmax_b <= K-1 && Ib+1-sb+40 <= plen)
+    { int up, dn;
+      cp_sum_steps_pair<true>(prof,Ib+1-sb,Icb,K-1+sb,lmax_b+sb,&up,&dn);
+      n_gain = up-dn;
+    }
+  else
+    { last = (Ib+K-1 < Ie-1) ? Ib+K-1 : Ie-1;
+      n_gain += cp_sum_steps(prof,Ib,last,plen,+1);
+      if (two)
+        { last = Ib+lmax_b;
+          n_gain -= cp_sum_steps(prof,Ib,last,plen,-1);
         }
-      first = Ie-lmax;
-      n_drop -= cp_sum_steps(prof,first,Ie-1,plen,+1);
+    }
+  CP_ET(5);
+  // The end: downward over [Ie-K+1, Ie-1), upward over [Ie-lmax_e, Ie-1) (empty for lmax_e <= 1).  The group is
+  // prof[Ie-40 .. Ie-1]: step j leads to prof[Ie-40+j], so the first downward step is number 42-K and the first upward one
+  // number 41-lmax_e, both at least 1.
+  if (pairs && lmax_e <= K-1 && Ie >= 40 && Ie <= plen)
+    { int up, dn;
+      cp_sum_steps_pair<false>(prof,Ie-40,0,41-lmax_e,42-K,&up,&dn);
+      n_drop = dn-up;
+    }
+  else
+    { first = (Ie-K+1 > Ib) ? Ie-K+1 : Ib;
+      n_drop += cp_sum_steps(prof,first,Ie-1,plen,-1);
+      if (two)
+        { first = Ie-lmax_e;
+          n_drop -= cp_sum_steps(prof,first,Ie-1,plen,+1);
+        }
     }
   CP_ET(6);
   int ccb = Icb+(n_gain > 0 ? n_gain : 0);
   int cce = Ice+(n_drop > 0 ? n_drop : 0);
   if (ccb > CP_MAX_KMER_CNT) ccb = CP_MAX_KMER_CNT;
   if (cce > CP_MAX_KMER_CNT) cce = CP_MAX_KMER_CNT;
-  if (idx == Ib && Ie-2*K <= Ib && cce < prof[Ib])       // wall.c:1003-1006 with intvl index == position
-    cce = prof[Ib];
+  if (idx == Ib && Ie-2*K <= Ib && cce < Icb)            // wall.c:1003-1006 with intvl index == position (Icb is prof[Ib])
+    cce = Icb;
   *ccb_out = ccb;
   *cce_out = cce;
 
