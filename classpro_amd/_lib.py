@@ -35,6 +35,7 @@ SYMBOLS = [
     "cp_kmer_sorted_unitigs", "cp_unitigs_count", "cp_unitigs_bases", "cp_unitigs_arrays", "cp_unitigs_destroy", "cp_unitig_n50",
     "cp_kmer_sorted_unitig_links", "cp_unitig_graph_links", "cp_unitig_graph_arrays", "cp_unitig_graph_destroy",
     "cp_kmer_sorted_read_paths", "cp_count_nonzero",
+    "cp_kmer_sorted_unitig_prune",
     "cp_threshold_labels", "cp_acc_create", "cp_acc_destroy", "cp_acc_add", "cp_acc_read",
 ]
 
@@ -204,6 +205,7 @@ def lib():
     L.cp_unitig_graph_destroy.restype = None
     L.cp_kmer_sorted_read_paths.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, C.POINTER(i64), vp]
     L.cp_count_nonzero.argtypes = [vp, i64, C.POINTER(i64), vp]
+    L.cp_kmer_sorted_unitig_prune.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     L.cp_threshold_labels.argtypes =[i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
     L.cp_acc_create.argtypes = [i32, C.c_double, C.c_double, C.POINTER(vp)]
     L.cp_acc_destroy.argtypes = [vp]

@@ -1032,6 +1032,68 @@ class SortedKmers:
             U._adopt_graph(g, dict(zip(Unitigs.LINK_TALLY, ltally)), components)
         return U
 
+    PRUNE_TALLY = ("unitigs", "islands", "tips", "bubbles", "removed_keys", "removed_bases", "kept_keys")
+
+    def prune(self, U, islands=0, tips=0, bubbles=0, weight=None, table=True):
+        """cp_kmer_sorted_unitig_prune ("Pruning the unitig graph" in include/classpro_amd.h): the islands, tips and simple
+        bubbles of the unitig graph `U`, a `Unitigs` of THIS snapshot made with where=True, links=True.  `islands`, `tips`
+        and `bubbles` are the limits in bases, 0 switching a rule off; `weight` an int64 device tensor [len(U)] that takes
+        the place of `U.kc`.  Returns (table, why, tally): a new `SortedKmers` of the entries of the unitigs that stay (None
+        with table=False), which keeps no reference to this one, the mark of every unitig as a uint8 device tensor (0 kept,
+        1 island, 2 tip, 3 bubble) and a dict of PRUNE_TALLY."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if not isinstance(U, Unitigs) or U.u is None or U.g is None or U.utg is None:
+            raise ValueError("prune needs a Unitigs made with where=True, links=True that is not closed")
+        if U.K != self.K or U.utg.numel() != self.n:
+            raise ValueError("the Unitigs are not of this snapshot")
+        limits = (C.c_int64 * 3)(int(islands), int(tips), int(bubbles))
+        if min(limits) < 0:
+            raise ValueError("a limit must not be negative")
+        if weight is not None:
+            if weight.dtype != torch.int64 or weight.dim() != 1 or weight.numel() != len(U):
+                raise ValueError("weight must be a flat int64 tensor with one value per unitig")
+            weight = weight.to(self.device).contiguous()
+        why = torch.zeros(len(U), dtype=torch.uint8, device=self.device)
+        tally, h = (C.c_int64 * len(self.PRUNE_TALLY))(), C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_unitig_prune(self.s, U.u, U.utg.data_ptr() if self.n else None, U.g,
+                                                     weight.data_ptr() if weight is not None and len(U) else None, limits,
+                                                     why.data_ptr() if len(U) else None, tally, _stream_of(self.device),
+                                                     C.byref(h) if table else None))
+        out = None
+        if table:
+            out = SortedKmers.__new__(SortedKmers)
+            out.L, out.device, out.K = self.L, self.device, self.K
+            out._adopt(h)
+        return out, why, dict(zip(self.PRUNE_TALLY, tally))
+
+    def clean(self, count_range=None, islands=0, tips=0, bubbles=0, rounds=10):
+        """The loop of tabclean: rounds of `unitigs` (where arrays), links (no components) and `prune`, the first with
+        `count_range`, the later ones on the previous result with no range, until a round removes nothing or `rounds`
+        rounds are done.  Returns (table, tallies): a new `SortedKmers` and the tally of every round; what it makes in
+        between is closed."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if int(rounds) < 1:
+            raise ValueError("rounds must be positive")
+        cur, tallies = self, []
+        for r in range(int(rounds)):
+            try:
+                U = cur.unitigs(count_range if r == 0 else None, where=True, links=True)
+                try:
+                    nxt, _, t = cur.prune(U, islands, tips, bubbles)
+                finally:
+                    U.close()
+            finally:
+                if cur is not self:
+                    cur.close()
+            cur = nxt
+            tallies.append(t)
+            if t["removed_keys"] == 0:
+                break
+        return cur, tallies
+
     def hist(self):
         """cp_kmer_sorted_hist: the FASTK histogram of the snapshot's counts in the shape `KmerCounts.hist` returns,
         (1, 32767, ilowcnt, ihighcnt, int64[32767])."""

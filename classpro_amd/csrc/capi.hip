@@ -1216,5 +1216,8 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // reads threaded through that graph: segments, coverage and arc support (tabpath): kmer_paths.hip
 #include "kmer_paths.hip"
 
+// islands, tips and simple bubbles of that graph, and the snapshot without them (tabclean): kmer_prune.hip
+#include "kmer_prune.hip"
+
 // global-threshold labels and label accuracy (ClassGS): label_tools.hip
 #include "label_tools.hip"

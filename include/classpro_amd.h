@@ -1014,6 +1014,69 @@ int     cp_kmer_sorted_read_paths(const cp_kmer_sorted *s, const cp_unitigs *u,
 int     cp_count_nonzero(const int64_t *d_v, int64_t n, int64_t *count /* host */, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pruning the unitig graph (tabclean): the structural cleaning that every de Bruijn tool chain makes after compaction --
+ * short dead-end branches clipped, simple bubbles popped, short islands dropped -- as marks per unitig and as the snapshot
+ * without the k-mers of the marked unitigs, an ordinary cp_kmer_sorted that every other call takes.  Builds on "Unitigs of
+ * sorted k-mers" and "Links between unitigs" and uses their words Oriented and Arc.  Everything is in integers.  Every mark
+ * is a function of the input graph of ONE call alone, never of another mark of that call, so the result is independent of
+ * grid, block size and scheduling.
+ *
+ *   Words      for an oriented unitig x: deg(x) = d_loff[x+1] - d_loff[x], T(x) the targets d_link[d_loff[x] .. d_loff[x+1]).
+ *              For a unitig u: bases(u) = d_off[u+1] - d_off[u], nodes(u) = bases(u) - K + 1, circ(u) bit 0 of d_flag[u],
+ *              w(u) its weight: d_weight[u] when d_weight is given, else d_kc[u]; a negative weight counts as 0.
+ *   Limits     a HOST array max_island, max_tip, max_bubble, in bases; 0 switches a rule off.
+ *   why[u]     0 kept, 1 island, 2 tip, 3 bubble.  The three cases exclude each other by their degrees.
+ *   Island     deg(2u) == 0, deg(2u+1) == 0 and bases(u) <= max_island.
+ *   TC(u)      a tip CANDIDATE: exactly one of deg(2u), deg(2u+1) is 0 and bases(u) <= max_tip.  x is then the orientation of
+ *              u that has arcs: it walks from the dead end into the graph.
+ *   Tip        TC(u), and there is an arc x -> y with y >> 1 != u and an arc y^1 -> t such that v = (t^1) >> 1 satisfies
+ *              v != u and v BEATS u: !TC(v), or (nodes(v), w(v)) > (nodes(u), w(u)) lexicographically, or the pairs are
+ *              equal and v < u.  v is another unitig that enters the junction u enters.  A tip with no competitor at its
+ *              junction stays; among competing candidates at one junction the order is strict and total, so the best stays.
+ *   Bubble     the ARM condition: !circ(u), deg(2u) == 1, deg(2u+1) == 1, bases(u) <= max_bubble, and with y = T(2u)[0] and
+ *              t = T(2u+1)[0] neither y >> 1 nor t >> 1 is u.  With p = t^1, every z in T(p) (at most 4) names v = z >> 1,
+ *              an ALTERNATIVE when v != u, !circ(v), bases(v) <= max_bubble, deg(z) == 1, T(z)[0] == y, deg(z^1) == 1 and
+ *              T(z^1)[0] == t.  u goes when some alternative v has w(v) * nodes(u) > w(u) * nodes(v), or the products are
+ *              equal and v < u; the products are exact (128 bits: a weight may reach 2^62, nodes 2^30).  The arm of highest
+ *              mean weight always stays.
+ *   As it is   the rule is written on d_loff and d_link as they are: nothing is special-cased at palindromic nodes, hairpins
+ *              or self arcs (a closed chain, a homopolymer node, a hairpin and a palindromic node all stay).
+ *   Limit      a bubble whose other side is split by a further junction is not simple and is not popped: that is what two
+ *              error sites closer than K give.  A caller's rounds (tabclean, SortedKmers.clean) resolve what other removals
+ *              uncover; two interleaved bubbles stay.
+ *   d_why      a DEVICE array of `count` bytes, overwritten with why[u].
+ *   out        a ready cp_kmer_sorted of the entries with d_utg[i] >= 0 and why[d_utg[i]] == 0, with their own counts, in
+ *              ascending order, its bucket starts rebuilt: cp_kmer_sorted_ktab, _find, _profiles, _combine and _unitigs work
+ *              on it.  An entry outside the range of the unitigs call (d_utg[i] < 0) is not in it.  To be destroyed by the
+ *              caller; it keeps no reference to anything passed in.
+ *   Tally      HOST int64 [CP_PRUNE_WIDTH]: CP_PRUNE_UNITIGS the unitigs looked at, CP_PRUNE_ISLANDS, CP_PRUNE_TIPS and
+ *              CP_PRUNE_BUBBLES those marked, CP_PRUNE_REMOVED_BASES their bases, CP_PRUNE_REMOVED_KEYS the entries of
+ *              marked unitigs, CP_PRUNE_KEPT_KEYS the entries of `out`.  KEPT_KEYS + REMOVED_KEYS == CP_UTG_KEYS of the call
+ *              that made u.
+ *   Arguments  u and d_utg are the object and the where array (device, `size` int64) of ONE call of cp_kmer_sorted_unitigs on
+ *              THIS snapshot, g the graph made from them, d_weight `count` int64 on the device.  Arrays of another call give
+ *              unspecified marks but never an access outside an array: a unitig, an oriented unitig and an offset read from
+ *              them are clamped.  Everything passed in is only read.
+ *   Passes     one lane per unitig applies the rule, its loads issued in groups (kn_rule.h); one pass over the entries
+ *              turns d_utg and why into tile counts; the scan; a pass that writes the kept entries (neither when out is
+ *              NULL; the pass over the entries only when tally or out is given).  The sums are taken per wave before any
+ *              atomic.
+ *   Errors     all before any launch: CP_EINVAL for a NULL s, u, g or limits, an unready snapshot, a u of another K, a g of
+ *              another number of unitigs, a NULL d_utg with count > 0, a negative limit, d_why, tally and out all NULL.  An
+ *              allocation that fails is CP_ENOMEM with the byte count in the message, nothing leaked.  A given `out` is
+ *              cleared on every error.  Zero unitigs give an empty `out` and are no error.  Synchronises `stream`.
+ *   Memory     scratch: 8 bytes per tile of cp_ktab_tile() entries, 8 bytes per 4096 tiles or buckets, 64 bytes of counters
+ *              and one byte per unitig (none when d_why is given).  Result: 24 bytes per kept entry and 8 per bucket.
+ */
+enum { CP_PRUNE_UNITIGS, CP_PRUNE_ISLANDS, CP_PRUNE_TIPS, CP_PRUNE_BUBBLES, CP_PRUNE_REMOVED_KEYS,
+       CP_PRUNE_REMOVED_BASES, CP_PRUNE_KEPT_KEYS, CP_PRUNE_WIDTH };
+int     cp_kmer_sorted_unitig_prune(const cp_kmer_sorted *s, const cp_unitigs *u,
+                                    const int64_t *d_utg /* device [size], of the call that made u */, const cp_unitig_graph *g,
+                                    const int64_t *d_weight /* device [count] or NULL: d_kc */, const int64_t *limits /* host [3] */,
+                                    uint8_t *d_why /* device [count], overwritten, or NULL */, int64_t *tally /* host, or NULL */,
+                                    void *stream, cp_kmer_sorted **out /* or NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Global-threshold labels (ClassGS): replaces the per-read loop of src/ClassGS.c:228-248, the GenomeScope-style
  * baseline the reference compares ClassPro against, for a batch in the flat layout above.
  *
