@@ -1,7 +1,9 @@
 // gpu_tool.h -- what the command-line tools that use the GPU share (ClassGS, class2cns, class2ktab, kprof,
-// genome2class): how a failed library or HIP call ends the tool, a device buffer that only grows until it is given
-// back, and the accuracy totals read from the device.  Needs the HIP runtime, so the host-only tools (prof2class,
-// class2acc) do not include it.  class_batch.h builds the .class batches of class2cns and class2ktab on it.
+// genome2class, tab2prof, tabbin, tabtrack, tabcmp, and through tab_out.h tabop, tabhet, tabunitig, tabgraph, tabpath and
+// tabclean): how a failed library or HIP call ends the tool, a device buffer that only grows until it is given back,
+// and the accuracy totals read from the device.  Needs the HIP runtime, so the host-only tools (prof2class, class2acc)
+// do not include it.  class_batch.h builds the .class batches of class2cns and class2ktab on it, ktab_upload.h and
+// ktab_writer.h the way of a k-mer table onto the device and back, tab_out.h and unitig_dump.h what the table tools share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "host_io.h"

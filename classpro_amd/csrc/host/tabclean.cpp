@@ -36,28 +36,12 @@
 //   the lines of ktab_reader.h                                                    the table
 //   tabclean: <out_root>.ktab is the operand: the result needs a name of its own
 //   tabclean: Cannot open <path> for 'w'                                          <out_root>.ktab, <out_root>.hist
-#include <chrono>
-#include "gpu_tool.h"
-#include "ktab_upload.h"
+#include "tab_out.h"
+#include "unitig_dump.h"                   // print_unitig_line: tabunitig's line
 #include "ktab_range.h"                    // split_range: "<path>[:<lo>-<hi>]"
 
 static const char *USAGE = "[-v] [-i<int(0)>] [-t<int(2K)>] [-b<int(0)>] [-r<int(10)>] [-T<int(4)>]\n"
                            "                <table>[.ktab][:<lo>-<hi>] [<out_root>]";
-
-// tabunitig's line for the unitigs U with the tally of the call that made them
-static void graph_line(const cp_unitigs *U, const int64_t *tally)
-{ const int64_t count = cp_unitigs_count(U);
-  const int64_t *d_off;
-  if (cp_unitigs_arrays(U,nullptr,&d_off,nullptr,nullptr) != CP_OK) cp_die(CP_EINVAL,"cp_unitigs_arrays");
-  std::vector<int64_t> off((size_t)count+1,0), len((size_t)count);
-  if (count > 0) HCHK(hipMemcpy(off.data(),d_off,(size_t)(count+1)*8,hipMemcpyDeviceToHost));
-  for (int64_t u = 0; u < count; u++) len[(size_t)u] = off[(size_t)u+1]-off[(size_t)u];
-  const int64_t n50 = cp_unitig_n50(len.data(),count);
-  if (n50 < 0) cp_die((int)n50,"cp_unitig_n50");
-  printf("%s: %lld k-mers, %lld unitigs, %lld bases, %lld circular, longest %lld, N50 %lld\n",PROG,(long long)tally[CP_UTG_KEYS],
-         (long long)tally[CP_UTG_UNITIGS],(long long)tally[CP_UTG_BASES],(long long)tally[CP_UTG_CIRCULAR],
-         (long long)tally[CP_UTG_LONGEST],(long long)n50);
-}
 
 int main(int argc, char **argv)
 { PROG = "tabclean";
@@ -95,39 +79,20 @@ int main(int argc, char **argv)
 
   // the stub and the histogram: both are created before the GPU is touched, or neither is left behind
   std::string odir, oname, tab_path, hist_path;
+  Outputs outs;
   FILE *ft = nullptr, *fh = nullptr;
   if (build)
     { odir = path_to(pos[1]);
       oname = root_of(pos[1],"");
       tab_path = odir+"/"+oname+".ktab";
       hist_path = odir+"/"+oname+".hist";
-      struct stat so, si;                                              // the result may not replace the table it is made from
-      if (tab_path == A.stub || (stat(tab_path.c_str(),&so) == 0 && stat(A.stub.c_str(),&si) == 0
-                                 && so.st_dev == si.st_dev && so.st_ino == si.st_ino))
-        die("%s: %s is the operand: the result needs a name of its own\n",PROG,tab_path.c_str());
-      const bool tab_fresh = access(tab_path.c_str(),F_OK) != 0, hist_fresh = access(hist_path.c_str(),F_OK) != 0;
-      const int fdt = open(tab_path.c_str(),O_WRONLY|O_CREAT,0666);
-      if (fdt < 0) die("%s: Cannot open %s for 'w'\n",PROG,tab_path.c_str());
-      const int fdh = open(hist_path.c_str(),O_WRONLY|O_CREAT,0666);
-      auto give_up = [&](const std::string &path)                      // what was created here is removed again
-        { if (fdh >= 0) close(fdh);
-          close(fdt);
-          if (tab_fresh) unlink(tab_path.c_str());
-          if (fdh >= 0 && hist_fresh) unlink(hist_path.c_str());
-          die("%s: Cannot open %s for 'w'\n",PROG,path.c_str());
-        };
-      if (fdh < 0) give_up(hist_path);
-      if (ftruncate(fdt,0) != 0 || !(ft = fdopen(fdt,"wb"))) give_up(tab_path);
-      if (ftruncate(fdh,0) != 0 || !(fh = fdopen(fdh,"wb"))) give_up(hist_path);
+      die_if_operand(tab_path,A.stub,"is the operand");
+      ft = outs.create(tab_path);
+      fh = outs.create(hist_path);
     }
 
   // ---- the table up, then the rounds ----
-  HCHK(hipSetDevice(0));
-  cp_kmer_sorted *T;
-  { DevBuf<uint8_t> d_rec;
-    T = upload_ktab(A,d_rec);
-    d_rec.release();
-  }
+  cp_kmer_sorted *T = upload_table(A);
   DevBuf<int64_t> d_utg, d_at;
   int64_t keys_in = 0, done = 0, removed = 1;
   for (int r = 0; r < rounds && removed > 0; r++)
@@ -146,9 +111,9 @@ int main(int argc, char **argv)
       if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_unitig_links");
       rc = cp_kmer_sorted_unitig_prune(T,U,d_utg.p,G,nullptr,limits,nullptr,pt,nullptr,&R);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_unitig_prune");
-      const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
+      const double secs = since(t0);
       if (r == 0)
-        { graph_line(U,ut);
+        { print_unitig_line(U,ut);
           keys_in = ut[CP_UTG_KEYS];
         }
       printf("%s: round %d: %lld unitigs, %lld islands, %lld tips, %lld bubbles, %lld k-mers removed\n",PROG,r+1,
@@ -157,7 +122,7 @@ int main(int argc, char **argv)
       if (verbose) fprintf(stderr,"round %d: %lld entries; %.3f s wall\n",r+1,(long long)size,secs);
       removed = pt[CP_PRUNE_REMOVED_KEYS];
       done = r+1;
-      if (removed == 0) graph_line(U,ut);                      // the result's graph is this round's
+      if (removed == 0) print_unitig_line(U,ut);                      // the result's graph is this round's
       cp_unitig_graph_destroy(G);
       cp_unitigs_destroy(U);
       cp_kmer_sorted_destroy(T);
@@ -168,7 +133,7 @@ int main(int argc, char **argv)
       cp_unitigs *U = nullptr;
       const int rc = cp_kmer_sorted_unitigs(T,nullptr,ut,nullptr,nullptr,nullptr,nullptr,&U);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_unitigs");
-      graph_line(U,ut);
+      print_unitig_line(U,ut);
       cp_unitigs_destroy(U);
     }
   d_utg.release();

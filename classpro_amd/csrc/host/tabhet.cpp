@@ -34,9 +34,7 @@
 //   the lines of ktab_reader.h                                                    the table
 //   tabhet: <out_root>.ktab is the operand: the result needs a name of its own    -t
 //   tabhet: Cannot open <path> for 'w'                                            <out_root>.het, .ktab, .hist
-#include <chrono>
-#include "gpu_tool.h"
-#include "ktab_upload.h"
+#include "tab_out.h"
 #include "ktab_range.h"                    // split_range: "<path>[:<lo>-<hi>]"
 
 static const char *USAGE = "[-v] [-a] [-t] [-x<int(1000)>] [-y<int(1000)>] [-T<int(4)>]\n"
@@ -89,74 +87,52 @@ int main(int argc, char **argv)
   const int K = A.K;
 
   // every output is created before the GPU is touched, or none is left behind
-  struct Out { std::string path; FILE *f; bool fresh; };
-  std::vector<Out> outs;
-  std::string odir, oname;
+  Outputs outs;
+  std::string odir, oname, het_path, tab_path, hist_path;
+  FILE *fc = nullptr, *ft = nullptr, *fh = nullptr;
   if (pos.size() == 2)
     { odir = path_to(pos[1]);
       oname = root_of(pos[1],"");
-      std::vector<std::string> paths = { odir+"/"+oname+".het" };
+      het_path = odir+"/"+oname+".het";
+      tab_path = odir+"/"+oname+".ktab";
+      hist_path = odir+"/"+oname+".hist";
+      if (table) die_if_operand(tab_path,A.stub,"is the operand");
+      fc = outs.create(het_path);
       if (table)
-        { const std::string tab_path = odir+"/"+oname+".ktab";
-          struct stat so, si;
-          if (tab_path == A.stub || (stat(tab_path.c_str(),&so) == 0 && stat(A.stub.c_str(),&si) == 0
-                                     && so.st_dev == si.st_dev && so.st_ino == si.st_ino))
-            die("%s: %s is the operand: the result needs a name of its own\n",PROG,tab_path.c_str());
-          paths.push_back(tab_path);
-          paths.push_back(odir+"/"+oname+".hist");
-        }
-      for (const std::string &p : paths)
-        { const bool fresh = access(p.c_str(),F_OK) != 0;
-          const int fd = open(p.c_str(),O_WRONLY|O_CREAT,0666);
-          FILE *f = nullptr;
-          if (fd >= 0 && (ftruncate(fd,0) != 0 || !(f = fdopen(fd,"wb")))) close(fd);
-          if (!f)
-            { for (const Out &o : outs)                        // what was created here is removed again
-                { fclose(o.f);
-                  if (o.fresh) unlink(o.path.c_str());
-                }
-              if (fd >= 0 && fresh) unlink(p.c_str());
-              die("%s: Cannot open %s for 'w'\n",PROG,p.c_str());
-            }
-          outs.push_back(Out{ p, f, fresh });
+        { ft = outs.create(tab_path);
+          fh = outs.create(hist_path);
         }
     }
 
   // ---- the table up, then the pairing ----
-  HCHK(hipSetDevice(0));
-  cp_kmer_sorted *T, *R = nullptr;
-  { DevBuf<uint8_t> d_rec;
-    T = upload_ktab(A,d_rec);
-    d_rec.release();
-  }
+  cp_kmer_sorted *T = upload_table(A), *R = nullptr;
   std::vector<int64_t> mat((size_t)cells);
   int64_t tally[CP_HET_WIDTH];
   const auto t0 = std::chrono::steady_clock::now();
   int rc = cp_kmer_sorted_het_pairs(T,range,all ? 0 : 1,(int)xmax,(int)ymax,mat.data(),tally,nullptr,nullptr,table ? &R : nullptr);
   if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_het_pairs");
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
+  const double secs = since(t0);
   cp_kmer_sorted_destroy(T);
   printf("%s: %lld k-mers, %lld pairs, %lld unique pairs, %lld k-mers in more than one pair\n",PROG,(long long)tally[CP_HET_KEYS],
          (long long)tally[CP_HET_PAIRS],(long long)tally[CP_HET_UNIQUE],(long long)tally[CP_HET_MULTI]);
   fflush(stdout);
 
-  if (!outs.empty())
-    { FILE *fc = outs[0].f;
-      const int ny = (int)ymax+1;
+  if (fc)
+    { const int ny = (int)ymax+1;
       bool ok = fprintf(fc,"#a\tb\tpairs\n") > 0;
       for (int64_t c = 0; c < cells; c++)
         if (mat[(size_t)c])
           ok = fprintf(fc,"%lld\t%lld\t%lld\n",(long long)(c/ny),(long long)(c%ny),(long long)mat[(size_t)c]) > 0 && ok;
-      if (fclose(fc) != 0 || !ok) die("%s: Cannot write %s\n",PROG,outs[0].path.c_str());
+      if (fclose(fc) != 0 || !ok) die("%s: Cannot write %s\n",PROG,het_path.c_str());
     }
   if (table)
     { std::vector<int64_t> hist((size_t)CP_MAX_KMER_CNT);
       int64_t ilow, ihigh;
       rc = cp_kmer_sorted_hist(R,hist.data(),&ilow,&ihigh);
       if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_hist");
-      write_hist(outs[2].f,outs[2].path,K,ilow,ihigh,hist.data());
+      write_hist(fh,hist_path,K,ilow,ihigh,hist.data());
       KtabWriter W;
-      W.write(R,K,A.minval,nthreads,outs[1].f,outs[1].path,odir,oname);
+      W.write(R,K,A.minval,nthreads,ft,tab_path,odir,oname);
       W.release();
       cp_kmer_sorted_destroy(R);
     }

@@ -32,8 +32,7 @@
 //   tabop: K of <A stub> (<k>) and <B stub> (<k>) differ
 //   tabop: <out_root>.ktab is an operand: the result needs a name of its own
 //   tabop: Cannot open <path> for 'w'                                             <out_root>.ktab, <out_root>.hist
-#include "gpu_tool.h"
-#include "ktab_upload.h"
+#include "tab_out.h"
 #include "ktab_range.h"                    // split_range: "<path>[:<lo>-<hi>]"
 
 static const char *USAGE = "[-v] [-T<int(4)>] [-c<left|sum|min|max>]\n"
@@ -82,38 +81,23 @@ int main(int argc, char **argv)
 
   // the stub and the histogram: both are created before the GPU is touched, or neither is left behind
   std::string odir, oname, tab_path, hist_path;
+  Outputs outs;
   FILE *ft = nullptr, *fh = nullptr;
   if (build)
     { odir = path_to(pos[3]);
       oname = root_of(pos[3],"");
       tab_path = odir+"/"+oname+".ktab";
       hist_path = odir+"/"+oname+".hist";
-      for (const KtabReader *t : { &A, &B })                           // the result may not replace a table it is made from
-        { struct stat so, si;
-          if (tab_path == t->stub || (stat(tab_path.c_str(),&so) == 0 && stat(t->stub.c_str(),&si) == 0
-                                      && so.st_dev == si.st_dev && so.st_ino == si.st_ino))
-            die("%s: %s is an operand: the result needs a name of its own\n",PROG,tab_path.c_str());
-        }
-      const bool tab_fresh = access(tab_path.c_str(),F_OK) != 0, hist_fresh = access(hist_path.c_str(),F_OK) != 0;
-      const int fdt = open(tab_path.c_str(),O_WRONLY|O_CREAT,0666);
-      if (fdt < 0) die("%s: Cannot open %s for 'w'\n",PROG,tab_path.c_str());
-      const int fdh = open(hist_path.c_str(),O_WRONLY|O_CREAT,0666);
-      auto give_up = [&](const std::string &path)                      // what was created here is removed again
-        { if (fdh >= 0) close(fdh);
-          close(fdt);
-          if (tab_fresh) unlink(tab_path.c_str());
-          if (fdh >= 0 && hist_fresh) unlink(hist_path.c_str());
-          die("%s: Cannot open %s for 'w'\n",PROG,path.c_str());
-        };
-      if (fdh < 0) give_up(hist_path);
-      if (ftruncate(fdt,0) != 0 || !(ft = fdopen(fdt,"wb"))) give_up(tab_path);
-      if (ftruncate(fdh,0) != 0 || !(fh = fdopen(fdh,"wb"))) give_up(hist_path);
+      die_if_operand(tab_path,A.stub,"is an operand");
+      die_if_operand(tab_path,B.stub,"is an operand");
+      ft = outs.create(tab_path);
+      fh = outs.create(hist_path);
     }
 
   // ---- both tables up, then the merge ----
   HCHK(hipSetDevice(0));
   cp_kmer_sorted *TA, *TB, *R = nullptr;
-  { DevBuf<uint8_t> d_rec;
+  { DevBuf<uint8_t> d_rec;                                             // one buffer for both, so not upload_table
     TA = upload_ktab(A,d_rec);
     TB = upload_ktab(B,d_rec);
     d_rec.release();

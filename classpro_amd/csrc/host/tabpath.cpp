@@ -33,19 +33,12 @@
 //   tabpath: Cannot open <name> as a .db|.dam or .f{ast}[aq][.gz] file            the source
 //   tabpath: Cannot open <path> for 'w'                                           <out_root>.gaf, <out_root>.gfa
 #include <algorithm>
-#include <chrono>
-#include "gpu_tool.h"
+#include "tab_out.h"
+#include "unitig_dump.h"
 #include "read_source.h"
-#include "ktab_upload.h"
 #include "ktab_range.h"
 
 static const char *USAGE = "[-v] [-g] [-b<int(67108864)>] [-o<out_root>] <table>[.ktab][:<lo>-<hi>] <source>[.db|.dam|.f[ast][aq][.gz]]";
-static const int64_t SEQ_BUF = 1 << 24;    // bases held on the host at a time
-static const int64_t UTG_BUF = 1 << 20;    // unitigs whose count sums, components, coverage and link offsets are held at a time
-static const int64_t LNK_BUF = 1 << 22;    // links held on the host at a time
-
-static double since(std::chrono::steady_clock::time_point t0)
-{ return std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count(); }
 
 struct Batch
   { std::vector<std::string> headers;
@@ -54,16 +47,6 @@ struct Batch
     void clear() { headers.clear(); seq.clear(); soff.assign(1,0); }
     int n() const { return (int)soff.size()-1; }
   };
-
-// creates path for writing; *fresh = it did not exist before
-static FILE *create(const std::string &path, bool *fresh)
-{ *fresh = access(path.c_str(),F_OK) != 0;
-  FILE *f = nullptr;
-  const int fd = open(path.c_str(),O_WRONLY|O_CREAT,0666);
-  if (fd >= 0 && (ftruncate(fd,0) != 0 || !(f = fdopen(fd,"wb")))) close(fd);
-  if (!f && fd >= 0 && *fresh) unlink(path.c_str());
-  return f;
-}
 
 int main(int argc, char **argv)
 { PROG = "tabpath";
@@ -103,26 +86,14 @@ int main(int argc, char **argv)
   S.open();
 
   // the outputs are created before the GPU is touched
-  FILE *gaf = nullptr, *gfa = nullptr;
+  Outputs outs;
   const std::string gaf_path = out_root+".gaf", gfa_path = out_root+".gfa";
-  bool gaf_fresh = false, gfa_fresh = false;
-  if (!out_root.empty() && !(gaf = create(gaf_path,&gaf_fresh)))
-    die("%s: Cannot open %s for 'w'\n",PROG,gaf_path.c_str());
-  if (want_gfa && !(gfa = create(gfa_path,&gfa_fresh)))
-    { fclose(gaf);
-      if (gaf_fresh) unlink(gaf_path.c_str());
-      die("%s: Cannot open %s for 'w'\n",PROG,gfa_path.c_str());
-    }
+  FILE *gaf = out_root.empty() ? nullptr : outs.create(gaf_path), *gfa = want_gfa ? outs.create(gfa_path) : nullptr;
   std::vector<char> gbuf((size_t)1 << 20);
   if (gaf) setvbuf(gaf,gbuf.data(),_IOFBF,gbuf.size());
 
   // ---- the table up, then the unitigs, then their links ----
-  HCHK(hipSetDevice(0));
-  cp_kmer_sorted *T;
-  { DevBuf<uint8_t> d_rec;
-    T = upload_ktab(A,d_rec);
-    d_rec.release();
-  }
+  cp_kmer_sorted *T = upload_table(A);
   const int64_t size = cp_kmer_sorted_size(T);
   DevBuf<int64_t> d_utg, d_at;
   d_utg.need((size_t)size+1);
@@ -138,19 +109,9 @@ int main(int argc, char **argv)
   const double graph_secs = since(t0);
 
   const int64_t count = cp_unitigs_count(U), links = cp_unitig_graph_links(G);
-  const char *d_useq;
-  const int64_t *d_off, *d_kc, *d_loff, *d_link, *d_comp;
-  const uint8_t *d_flag;
-  if (cp_unitigs_arrays(U,&d_useq,&d_off,&d_kc,&d_flag) != CP_OK) cp_die(CP_EINVAL,"cp_unitigs_arrays");
-  if (cp_unitig_graph_arrays(G,&d_loff,&d_link,nullptr,&d_comp) != CP_OK) cp_die(CP_EINVAL,"cp_unitig_graph_arrays");
-  std::vector<int64_t> off((size_t)count+1,0), len((size_t)count);
-  if (count > 0) HCHK(hipMemcpy(off.data(),d_off,(size_t)(count+1)*8,hipMemcpyDeviceToHost));
-  for (int64_t u = 0; u < count; u++) len[(size_t)u] = off[(size_t)u+1]-off[(size_t)u];
-  const int64_t n50 = cp_unitig_n50(len.data(),count);
-  if (n50 < 0) cp_die((int)n50,"cp_unitig_n50");
-  printf("%s: %lld k-mers, %lld unitigs, %lld bases, %lld circular, longest %lld, N50 %lld\n",PROG,(long long)tally[CP_UTG_KEYS],
-         (long long)tally[CP_UTG_UNITIGS],(long long)tally[CP_UTG_BASES],(long long)tally[CP_UTG_CIRCULAR],
-         (long long)tally[CP_UTG_LONGEST],(long long)n50);
+  std::vector<int64_t> off, len;
+  unitig_lengths(U,off,len);
+  print_unitig_line(len,tally);
   DevBuf<int64_t> d_cov, d_sup;
   d_cov.need((size_t)count+1);
   d_sup.need((size_t)links+1);
@@ -251,51 +212,7 @@ int main(int argc, char **argv)
   d_at.release();
 
   if (gfa)                                                     // tabgraph's file with the two RC tags
-    { ok = fputs("H\tVN:Z:1.0\n",gfa) != EOF;
-      { std::vector<char> seq((size_t)SEQ_BUF);
-        std::vector<int64_t> kc((size_t)UTG_BUF), comp((size_t)UTG_BUF), cov((size_t)UTG_BUF);
-        int64_t have0 = 0, have1 = 0;                          // seq holds the bases [have0, have1)
-        for (int64_t u0 = 0; u0 < count; u0 += UTG_BUF)
-          { const int64_t nu = std::min(UTG_BUF,count-u0);
-            HCHK(hipMemcpy(kc.data(),d_kc+u0,(size_t)nu*8,hipMemcpyDeviceToHost));
-            HCHK(hipMemcpy(comp.data(),d_comp+u0,(size_t)nu*8,hipMemcpyDeviceToHost));
-            HCHK(hipMemcpy(cov.data(),d_cov.p+u0,(size_t)nu*8,hipMemcpyDeviceToHost));
-            for (int64_t u = u0; u < u0+nu; u++)
-              { ok = fprintf(gfa,"S\t%lld\t",(long long)u) > 0 && ok;
-                for (int64_t p = off[(size_t)u]; p < off[(size_t)u+1]; )
-                  { if (p >= have1)                            // the next range of bases, from p on
-                      { have0 = p;
-                        have1 = std::min(p+SEQ_BUF,off[(size_t)count]);
-                        HCHK(hipMemcpy(seq.data(),d_useq+have0,(size_t)(have1-have0),hipMemcpyDeviceToHost));
-                      }
-                    const int64_t e = std::min(have1,off[(size_t)u+1]);
-                    ok = fwrite(seq.data()+(p-have0),1,(size_t)(e-p),gfa) == (size_t)(e-p) && ok;
-                    p = e;
-                  }
-                ok = fprintf(gfa,"\tLN:i:%lld\tKC:i:%lld\tco:i:%lld\tRC:i:%lld\n",(long long)len[(size_t)u],(long long)kc[(size_t)(u-u0)],
-                             (long long)comp[(size_t)(u-u0)],(long long)cov[(size_t)(u-u0)]) > 0 && ok;
-              }
-          }
-      }
-      { std::vector<int64_t> loff((size_t)2*UTG_BUF+1), link((size_t)LNK_BUF), sup((size_t)LNK_BUF);
-        int64_t have0 = 0, have1 = 0;                          // link and sup hold the links [have0, have1)
-        for (int64_t u0 = 0; u0 < count; u0 += UTG_BUF)
-          { const int64_t nu = std::min(UTG_BUF,count-u0);
-            HCHK(hipMemcpy(loff.data(),d_loff+2*u0,(size_t)(2*nu+1)*8,hipMemcpyDeviceToHost));
-            for (int64_t x = 2*u0; x < 2*(u0+nu); x++)
-              for (int64_t k = loff[(size_t)(x-2*u0)]; k < loff[(size_t)(x-2*u0)+1] && k < links; k++)
-                { if (k >= have1)                              // the next range of links, from k on
-                    { have0 = k;
-                      have1 = std::min(k+LNK_BUF,links);
-                      HCHK(hipMemcpy(link.data(),d_link+have0,(size_t)(have1-have0)*8,hipMemcpyDeviceToHost));
-                      HCHK(hipMemcpy(sup.data(),d_sup.p+have0,(size_t)(have1-have0)*8,hipMemcpyDeviceToHost));
-                    }
-                  const int64_t y = link[(size_t)(k-have0)];
-                  ok = fprintf(gfa,"L\t%lld\t%c\t%lld\t%c\t%dM\tRC:i:%lld\n",(long long)(x >> 1),(x & 1) ? '-' : '+',(long long)(y >> 1),
-                               (y & 1) ? '-' : '+',K-1,(long long)sup[(size_t)(k-have0)]) > 0 && ok;
-                }
-          }
-      }
+    { ok = write_gfa(gfa,U,G,K,off,d_cov.p,d_sup.p);
       if (fclose(gfa) != 0 || !ok) die("%s: Cannot write %s\n",PROG,gfa_path.c_str());
     }
   cp_unitig_graph_destroy(G);

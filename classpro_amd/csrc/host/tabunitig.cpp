@@ -25,14 +25,11 @@
 //   tabunitig: Count range of <operand> needs 1 <= lo <= hi (<lo>-<hi>)
 //   the lines of ktab_reader.h                                                    the table
 //   tabunitig: Cannot open <path> for 'w'                                         <out_root>.unitigs.fa
-#include <chrono>
-#include "gpu_tool.h"
-#include "ktab_upload.h"
+#include "tab_out.h"
+#include "unitig_dump.h"
 #include "ktab_range.h"                    // split_range: "<path>[:<lo>-<hi>]"
 
 static const char *USAGE = "[-v] <table>[.ktab][:<lo>-<hi>] [<out_root>]";
-static const int64_t SEQ_BUF = 1 << 24;    // bases held on the host at a time
-static const int64_t UTG_BUF = 1 << 20;    // count sums and flags held on the host at a time
 
 int main(int argc, char **argv)
 { PROG = "tabunitig";
@@ -57,75 +54,31 @@ int main(int argc, char **argv)
   const int K = A.K;
 
   // the output is created before the GPU is touched
+  Outputs outs;
   FILE *fa = nullptr;
   std::string fa_path;
   if (pos.size() == 2)
     { fa_path = path_to(pos[1])+"/"+root_of(pos[1],"")+".unitigs.fa";
-      const bool fresh = access(fa_path.c_str(),F_OK) != 0;
-      const int fd = open(fa_path.c_str(),O_WRONLY|O_CREAT,0666);
-      if (fd >= 0 && (ftruncate(fd,0) != 0 || !(fa = fdopen(fd,"wb")))) close(fd);
-      if (!fa)
-        { if (fd >= 0 && fresh) unlink(fa_path.c_str());
-          die("%s: Cannot open %s for 'w'\n",PROG,fa_path.c_str());
-        }
+      fa = outs.create(fa_path);
     }
 
   // ---- the table up, then the graph ----
-  HCHK(hipSetDevice(0));
-  cp_kmer_sorted *T;
-  { DevBuf<uint8_t> d_rec;
-    T = upload_ktab(A,d_rec);
-    d_rec.release();
-  }
+  cp_kmer_sorted *T = upload_table(A);
   int64_t tally[CP_UTG_WIDTH];
   cp_unitigs *U = nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = cp_kmer_sorted_unitigs(T,range,tally,nullptr,nullptr,nullptr,nullptr,&U);
   if (rc != CP_OK) cp_die(rc,"cp_kmer_sorted_unitigs");
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now()-t0).count();
+  const double secs = since(t0);
   cp_kmer_sorted_destroy(T);
 
-  const int64_t count = cp_unitigs_count(U);
-  const char *d_seq;
-  const int64_t *d_off, *d_kc;
-  const uint8_t *d_flag;
-  if (cp_unitigs_arrays(U,&d_seq,&d_off,&d_kc,&d_flag) != CP_OK) cp_die(CP_EINVAL,"cp_unitigs_arrays");
-  std::vector<int64_t> off((size_t)count+1,0), len((size_t)count);
-  if (count > 0) HCHK(hipMemcpy(off.data(),d_off,(size_t)(count+1)*8,hipMemcpyDeviceToHost));
-  for (int64_t u = 0; u < count; u++) len[(size_t)u] = off[(size_t)u+1]-off[(size_t)u];
-  const int64_t n50 = cp_unitig_n50(len.data(),count);
-  if (n50 < 0) cp_die((int)n50,"cp_unitig_n50");
-  printf("%s: %lld k-mers, %lld unitigs, %lld bases, %lld circular, longest %lld, N50 %lld\n",PROG,(long long)tally[CP_UTG_KEYS],
-         (long long)tally[CP_UTG_UNITIGS],(long long)tally[CP_UTG_BASES],(long long)tally[CP_UTG_CIRCULAR],
-         (long long)tally[CP_UTG_LONGEST],(long long)n50);
+  std::vector<int64_t> off, len;
+  unitig_lengths(U,off,len);
+  print_unitig_line(len,tally);
   fflush(stdout);
 
   if (fa)
-    { std::vector<char> seq((size_t)SEQ_BUF);
-      std::vector<int64_t> kc((size_t)UTG_BUF);
-      std::vector<uint8_t> flag((size_t)UTG_BUF);
-      int64_t have0 = 0, have1 = 0;                            // seq holds the bases [have0, have1)
-      bool ok = true;
-      for (int64_t u0 = 0; u0 < count; u0 += UTG_BUF)
-        { const int64_t nu = std::min(UTG_BUF,count-u0);
-          HCHK(hipMemcpy(kc.data(),d_kc+u0,(size_t)nu*8,hipMemcpyDeviceToHost));
-          HCHK(hipMemcpy(flag.data(),d_flag+u0,(size_t)nu,hipMemcpyDeviceToHost));
-          for (int64_t u = u0; u < u0+nu; u++)
-            { ok = fprintf(fa,">%lld LN:i:%lld KC:i:%lld%s\n",(long long)u,(long long)len[(size_t)u],(long long)kc[(size_t)(u-u0)],
-                           (flag[(size_t)(u-u0)] & 1) ? " CL:Z:circular" : "") > 0 && ok;
-              for (int64_t p = off[(size_t)u]; p < off[(size_t)u+1]; )
-                { if (p >= have1)                              // the next range of bases, from p on
-                    { have0 = p;
-                      have1 = std::min(p+SEQ_BUF,off[(size_t)count]);
-                      HCHK(hipMemcpy(seq.data(),d_seq+have0,(size_t)(have1-have0),hipMemcpyDeviceToHost));
-                    }
-                  const int64_t e = std::min(have1,off[(size_t)u+1]);
-                  ok = fwrite(seq.data()+(p-have0),1,(size_t)(e-p),fa) == (size_t)(e-p) && ok;
-                  p = e;
-                }
-              ok = fputc('\n',fa) != EOF && ok;
-            }
-        }
+    { const bool ok = write_unitig_fasta(fa,U,off);
       if (fclose(fa) != 0 || !ok) die("%s: Cannot write %s\n",PROG,fa_path.c_str());
     }
   cp_unitigs_destroy(U);

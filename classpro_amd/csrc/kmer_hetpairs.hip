@@ -2,8 +2,8 @@
 // that differ from it, in some orientation, only at the centre base; the 2-D histogram of the two counts of such pairs
 // (the first step of Smudgeplot), the degree of every key, and the paired keys as a snapshot of their own.  Semantics:
 // include/classpro_amd.h, "Heterozygous pairs of sorted k-mers"; design: DESIGN.md 9.17.  Included by capi.hip after
-// kmer_cmphist.hip (kl_view, kl_find_group, so_view, so_store_kept, so_result_alloc, so_scan, CM_CX, CM_CY, cm_put,
-// ks_alloc, kc_wave_add, set_err and HIPCHK are in scope).  The operand is only read.
+// kmer_cmphist.hip (kl_view, kl_find_group, the ks_keep_ kernels and the so_derived_ helpers of kmer_setops.hip, CM_CX,
+// CM_CY, cm_put, ks_alloc, kc_wave_add, set_err and HIPCHK are in scope).  The operand is only read.
 //   key      one lane per entry.  X = hi << 63 | lo as 128 bits; rc(X) once per key: the 64 two-bit groups of the 128 bits
 //            reversed (a bit reversal and a swap inside every pair), shifted down to 2K bits and complemented.
 //   sibling  a candidate is min(sub(X, p, c), sub(rcX, K-1-p, 3-c)) for p = m = K/2 and, where K is even, p = K-1-m, and
@@ -20,16 +20,15 @@
 //   stage    CLASSPRO_HET_STAGE=1, the A/B form: a block stages its tile of KS_TILE consecutive entries in LDS (48 KiB) and
 //            searches a candidate that lies between the tile's first and last key there (cm_tile_kernel's partner search);
 //            only the others go to kl_find_group.  Same results; the build's default is HP_STAGE.
-//   result   tabop's compaction over tiles of KS_TILE consecutive entries: members per tile, the scan, the entries at their
-//            exact size by coalesced stores out of LDS (so_store_kept: the bucket counters too), the scan of the counters.
-//            The write pass clears bit 7 again, so after a call that succeeds a caller's d_deg holds plain degrees.
+//   result   the compaction by a predicate of kmer_setops.hip (ks_keep_count_kernel, ks_keep_write_kernel, so_derived_*)
+//            with "is a member" as the predicate.  The write pass's predicate clears bit 7 again, so after a call that
+//            succeeds a caller's d_deg holds plain degrees; that is why it runs even when no entry is a member.
 // All sums are integer atomics: nothing depends on grid, block size or scheduling.
 #define HP_PER_CU   6                      // persistent blocks of the pair pass per CU: what 24 KiB of corner leave resident
 #define HP_PER_CU_STAGED 2                 // ... and what 72 KiB of corner and staged tile leave
 #define HP_STAGE    0                      // the staged form (CLASSPRO_HET_STAGE; measured: DESIGN.md 9.17)
 #define HP_MEMBER   0x80u                  // bit 7 of a degree byte: a member of a unique pair (between the passes only)
 #define HP_DEG      0x7fu
-#define HP_PER_LANE (KS_TILE/KS_BLOCK)     // consecutive entries of a lane in the compaction
 
 struct hp_rule { unsigned long long cmin, cmax; };
 
@@ -209,45 +208,23 @@ __global__ void __launch_bounds__(KT_BLOCK) hp_pair_kernel(kl_view t, int K, hp_
 __device__ static inline bool hp_member(unsigned int d, bool unique)
 { return unique ? (d & HP_MEMBER) != 0 : (d & HP_DEG) != 0; }
 
-// tile_n[t] = the members among the entries [t*KS_TILE, (t+1)*KS_TILE)
-__global__ void __launch_bounds__(KS_BLOCK) hp_count_kernel(const uint8_t *deg, int64_t n, bool unique, int64_t *tile_n)
-{ __shared__ unsigned long long part[KS_BLOCK];
-  const int64_t i0 = (int64_t)blockIdx.x*KS_TILE;
-  unsigned long long mine = 0;
-  for (int s = threadIdx.x; s < KS_TILE; s += KS_BLOCK)
-    if (i0+s < n) mine += hp_member(deg[i0+s],unique);
-  const unsigned long long tot = ks_block_scan(mine,part);
-  if (threadIdx.x == KS_BLOCK-1) tile_n[blockIdx.x] = (int64_t)tot;
-}
+// the predicates of the compaction (ks_keep_count_kernel, ks_keep_write_kernel): entry i is a member; the write pass also
+// takes bit 7 out of its byte
+struct hp_keep
+  { const uint8_t *deg;
+    bool unique;
+    __device__ bool operator()(int64_t i) const { return hp_member(deg[i],unique); }
+  };
 
-// tile_n holds the inclusive sums: the members of a tile go to their places in order, and bit 7 leaves their bytes
-template <bool HI>
-__global__ void __launch_bounds__(KS_BLOCK) hp_write_kernel(so_view a, uint8_t *deg, bool unique, const int64_t *tile_n,
-                                                            unsigned long long *ohi, unsigned long long *olo,
-                                                            unsigned long long *ocn, int64_t on, unsigned long long *cnt_of,
-                                                            int64_t nb, int shift)
-{ __shared__ unsigned long long shi[HI ? KS_TILE : 1], slo[KS_TILE], scn[KS_TILE];
-  __shared__ unsigned long long part[KS_BLOCK];
-  const int64_t t = blockIdx.x, i0 = t*KS_TILE+(int64_t)threadIdx.x*HP_PER_LANE;
-  unsigned int bits = 0, mine = 0;
-  for (int k = 0; k < HP_PER_LANE; k++)
-    { if (i0+k >= a.n) break;
-      const unsigned int d = deg[i0+k];
-      if (hp_member(d,unique)) { bits |= 1u << k; mine++; }
-      if (d & HP_MEMBER) deg[i0+k] = (uint8_t)(d & HP_DEG);
+struct hp_keep_clear
+  { uint8_t *deg;
+    bool unique;
+    __device__ bool operator()(int64_t i) const
+    { const unsigned int d = deg[i];
+      if (d & HP_MEMBER) deg[i] = (uint8_t)(d & HP_DEG);
+      return hp_member(d,unique);
     }
-  int at = (int)(ks_block_scan((unsigned long long)mine,part)-(unsigned long long)mine);
-  for (int k = 0; k < HP_PER_LANE; k++)
-    { if (!((bits >> k) & 1u) || at >= KS_TILE) continue;
-      if (HI) shi[at] = a.hi[i0+k];
-      slo[at] = a.lo[i0+k];
-      scn[at] = a.cnt[i0+k];
-      at++;
-    }
-  __syncthreads();
-  const int nk = (int)min(part[KS_BLOCK-1],(unsigned long long)KS_TILE);
-  so_store_kept<HI>(shi,slo,scn,[](int i) { return i; },nk,t ? tile_n[t-1] : 0,ohi,olo,ocn,on,cnt_of,nb,shift,false);
-}
+  };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
@@ -259,9 +236,9 @@ static int hp_run(const cp_kmer_sorted *s, hp_rule r, bool unique, int xmax, int
   const kl_view t = kl_view_of(s);
   const bool lo_only = kl_lo_only(s), with_hi = 2*s->K > 63;
   const size_t cells = mat ? (size_t)(xmax+1)*(size_t)(ymax+1) : 0;
-  const int64_t ntile = (s->n+KS_TILE-1)/KS_TILE;
-  if (res && ntile > (int64_t)KS_CHUNK*KS_CHUNK) return set_err(CP_EINVAL,std::string(who)+": more than 2^24 tiles");    // the scan's bound
-  const int64_t nsum = std::max((ntile+KS_CHUNK-1)/KS_CHUNK,(s->nb+KS_CHUNK-1)/KS_CHUNK);
+  int64_t ntile, nsum;
+  int rc = so_derived_tiles(who,s->n,s->nb,res != nullptr,&ntile,&nsum);
+  if (rc != CP_OK) return rc;
   unsigned long long h_tally[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
   int64_t n_out = 0;
   int64_t *tile_n = nullptr;
@@ -269,7 +246,7 @@ static int hp_run(const cp_kmer_sorted *s, hp_rule r, bool unique, int xmax, int
   uint8_t *deg = d_deg;
   if (s->n > 0)
     { const size_t words = 8+cells+(res ? (size_t)(ntile+nsum) : 0);
-      int rc = ks_alloc(who,scratch,words*8+(d_deg ? 0 : (size_t)s->n),"the matrix, the tile counts and the degrees");
+      rc = ks_alloc(who,scratch,words*8+(d_deg ? 0 : (size_t)s->n),"the matrix, the tile counts and the degrees");
       if (rc != CP_OK) return rc;
       unsigned long long *d_tally = (unsigned long long *)*scratch, *d_mat = mat ? d_tally+8 : nullptr;
       tile_n = (int64_t *)(d_tally+8+cells);
@@ -294,11 +271,10 @@ static int hp_run(const cp_kmer_sorted *s, hp_rule r, bool unique, int xmax, int
           HIPCHK(hipGetLastError());
         }
       if (res)
-        { hp_count_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(deg,s->n,unique,tile_n);
+        { ks_keep_count_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(hp_keep{ deg, unique },s->n,tile_n);
           HIPCHK(hipGetLastError());
-          so_scan(tile_n,ntile,sum,st);
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(&n_out,tile_n+ntile-1,8,hipMemcpyDeviceToHost,st));
+          rc = so_derived_counted(tile_n,ntile,sum,st,n_out);
+          if (rc != CP_OK) return rc;
         }
       HIPCHK(hipMemcpyAsync(h_tally,d_tally,64,hipMemcpyDeviceToHost,st));
       if (mat) HIPCHK(hipMemcpyAsync(mat,d_mat,cells*8,hipMemcpyDeviceToHost,st));
@@ -306,20 +282,13 @@ static int hp_run(const cp_kmer_sorted *s, hp_rule r, bool unique, int xmax, int
   HIPCHK(hipStreamSynchronize(st));
   if (mat && s->n == 0) memset(mat,0,cells*8);
   if (res)
-    { int rc = so_result_alloc(who,res,n_out,st);
+    { so_dest o;
+      rc = so_derived_alloc(who,res,n_out,st,&o);
       if (rc != CP_OK) return rc;
       if (s->n > 0)                                        // also with no member: the pass takes bit 7 out of the bytes again
-        { const so_view va = so_view_of(s);
-          unsigned long long *hi = res->key, *lo = res->key+n_out, *cnt = res->key+2*n_out;
-          unsigned long long *cnt_of = (unsigned long long *)res->start+1;  // start[p+1] counts bucket p, then ends it
-          const int shift = 2*s->K-s->pbits;
-          if (with_hi) hp_write_kernel<true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,deg,unique,tile_n,hi,lo,cnt,n_out,cnt_of,s->nb,shift);
-          else hp_write_kernel<false><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,deg,unique,tile_n,hi,lo,cnt,n_out,cnt_of,s->nb,shift);
-          HIPCHK(hipGetLastError());
-          if (n_out > 0)
-            { so_scan(res->start+1,s->nb,sum,st);
-              HIPCHK(hipGetLastError());
-            }
+        { rc = so_derived_write(s,hp_keep_clear{ deg, unique },with_hi,ntile,tile_n,o,st);
+          if (rc == CP_OK && n_out > 0) rc = so_derived_starts(res,sum,st);
+          if (rc != CP_OK) return rc;
         }
       HIPCHK(hipStreamSynchronize(st));
     }
@@ -355,23 +324,8 @@ extern "C" int cp_kmer_sorted_het_pairs(const cp_kmer_sorted *s, const int64_t *
   if (const char *e = getenv("CLASSPRO_HET_STAGE")) stage = atoi(e) != 0;
   hipStream_t st = (hipStream_t)stream;
   cp_kmer_sorted *res = nullptr;
-  if (out)
-    { res = new (std::nothrow) cp_kmer_sorted();
-      if (!res) return set_err(CP_ENOMEM,std::string(who)+": out of memory");
-      res->K = s->K; res->ibyte = s->ibyte; res->pbits = s->pbits; res->nb = s->nb;
-    }
+  if (out && so_derived_new(who,s,&res) != CP_OK) return CP_ENOMEM;
   void *scratch = nullptr;
   const int rc = hp_run(s,r,unique != 0,xmax,ymax,use_corner,stage,mat,tally,d_deg,st,res,&scratch);
-  if (rc != CP_OK) (void)hipStreamSynchronize(st);
-  if (scratch) (void)hipFree(scratch);
-  if (rc != CP_OK)
-    { cp_kmer_sorted_destroy(res);
-      return rc;
-    }
-  if (res)
-    { res->ready = true;
-      res->filled = res->n;
-      *out = res;
-    }
-  return CP_OK;
+  return so_derived_finish(rc,st,scratch,res,out);
 }

@@ -1,15 +1,15 @@
 // kmer_prune.hip -- structural cleaning of the unitig graph of ONE sorted snapshot (tabclean): the islands, tips and simple
 // bubbles of the graph marked by a rule that looks at the input graph alone, and the snapshot without the k-mers of the
 // marked unitigs.  Semantics: include/classpro_amd.h, "Pruning the unitig graph"; design: DESIGN.md 9.22.  Included by
-// capi.hip after kmer_paths.hip (cp_unitigs, cp_unitig_graph, so_view, so_store_kept, so_result_alloc, so_scan, ks_alloc,
-// ks_block_scan, kc_wave_add, set_err and HIPCHK are in scope).  Everything passed in is only read.
+// capi.hip after kmer_paths.hip (cp_unitigs, cp_unitig_graph, ks_keep_write_kernel and the so_derived_ helpers of
+// kmer_setops.hip, ks_alloc, ks_block_scan, kc_wave_add, set_err and HIPCHK are in scope).  Everything passed in is only read.
 //   rule     one lane per unitig: why[u] = kn_why(u, graph) of kn_rule.h, whose loads come in groups; the islands, tips,
 //            bubbles and removed bases summed per wave, then one atomic per wave and counter.
 //   count    one block per tile of KS_TILE consecutive entries: an entry is kept when d_utg[i] >= 0 and the mark of that
 //            unitig (clamped) is 0; the kept entries of the tile, and the kept and removed keys summed per wave.
-//   write    so_scan over the tile counts, the result allocated at its exact size, then the kept entries of a tile go out of
-//            LDS to their places by coalesced stores (so_store_kept: the bucket counters too) and the same scan over the
-//            counters leaves the bucket starts -- hp_count_kernel and hp_write_kernel of kmer_hetpairs.hip with another flag.
+//   write    the compaction by a predicate of kmer_setops.hip (so_derived_*, ks_keep_write_kernel) with "the entry is kept"
+//            as the predicate.  The count pass stays this file's own: it also sums the kept and the removed keys, and it
+//            runs without tile counts when no result is wanted.
 // All sums are integer atomics: nothing depends on grid, block size or scheduling.
 #include "kn_rule.h"
 
@@ -57,32 +57,13 @@ __global__ void __launch_bounds__(KS_BLOCK) kn_count_kernel(const int64_t *utg, 
   if (threadIdx.x == KS_BLOCK-1) tile_n[blockIdx.x] = (int64_t)tot;
 }
 
-// tile_n holds the inclusive sums: the kept entries of a tile go to their places in order
-template <bool HI>
-__global__ void __launch_bounds__(KS_BLOCK) kn_write_kernel(so_view a, const int64_t *utg, const uint8_t *why, int64_t count,
-                                                            const int64_t *tile_n, unsigned long long *ohi, unsigned long long *olo,
-                                                            unsigned long long *ocn, int64_t on, unsigned long long *cnt_of,
-                                                            int64_t nb, int shift)
-{ __shared__ unsigned long long shi[HI ? KS_TILE : 1], slo[KS_TILE], scn[KS_TILE];
-  __shared__ unsigned long long part[KS_BLOCK];
-  const int64_t t = blockIdx.x, i0 = t*KS_TILE+(int64_t)threadIdx.x*HP_PER_LANE;
-  unsigned int bits = 0, mine = 0;
-  for (int k = 0; k < HP_PER_LANE; k++)
-    { if (i0+k >= a.n) break;
-      if (kn_state(utg,why,count,i0+k) == 1) { bits |= 1u << k; mine++; }
-    }
-  int at = (int)(ks_block_scan((unsigned long long)mine,part)-(unsigned long long)mine);
-  for (int k = 0; k < HP_PER_LANE; k++)
-    { if (!((bits >> k) & 1u) || at >= KS_TILE) continue;
-      if (HI) shi[at] = a.hi[i0+k];
-      slo[at] = a.lo[i0+k];
-      scn[at] = a.cnt[i0+k];
-      at++;
-    }
-  __syncthreads();
-  const int nk = (int)min(part[KS_BLOCK-1],(unsigned long long)KS_TILE);
-  so_store_kept<HI>(shi,slo,scn,[](int i) { return i; },nk,t ? tile_n[t-1] : 0,ohi,olo,ocn,on,cnt_of,nb,shift,false);
-}
+// the predicate of the write pass (ks_keep_write_kernel): entry i is kept
+struct kn_keep
+  { const int64_t *utg;
+    const uint8_t *why;
+    int64_t count;
+    __device__ bool operator()(int64_t i) const { return kn_state(utg,why,count,i) == 1; }
+  };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
@@ -92,9 +73,10 @@ static int kn_run(const cp_kmer_sorted *s, const cp_unitigs *u, const int64_t *d
                   const int64_t *d_weight, const int64_t *limits, uint8_t *d_why, int64_t *tally, hipStream_t st,
                   cp_kmer_sorted *res, void **scratch)
 { const char *who = "cp_kmer_sorted_unitig_prune";
-  const int64_t count = u->count, n = s->n, ntile = (n+KS_TILE-1)/KS_TILE;
-  if (res && ntile > (int64_t)KS_CHUNK*KS_CHUNK) return set_err(CP_EINVAL,std::string(who)+": more than 2^24 tiles");    // the scan's bound
-  const int64_t nsum = std::max((ntile+KS_CHUNK-1)/KS_CHUNK,(s->nb+KS_CHUNK-1)/KS_CHUNK);
+  const int64_t count = u->count, n = s->n;
+  int64_t ntile, nsum;
+  int rc = so_derived_tiles(who,n,s->nb,res != nullptr,&ntile,&nsum);
+  if (rc != CP_OK) return rc;
   unsigned long long h_ctl[KN_CTL];
   memset(h_ctl,0,sizeof(h_ctl));
   int64_t n_out = 0;
@@ -105,7 +87,7 @@ static int kn_run(const cp_kmer_sorted *s, const cp_unitigs *u, const int64_t *d
   if (count > 0)
     { // the control block, the tile counts and the words of the scan, a mark per unitig
       const size_t words = KN_CTL+(res ? (size_t)(ntile+nsum) : 0);
-      int rc = ks_alloc(who,scratch,words*8+(d_why ? 0 : (size_t)count),"the tile counts and the marks");
+      rc = ks_alloc(who,scratch,words*8+(d_why ? 0 : (size_t)count),"the tile counts and the marks");
       if (rc != CP_OK) return rc;
       unsigned long long *ctl = (unsigned long long *)*scratch;
       tile_n = res ? (int64_t *)(ctl+KN_CTL) : nullptr;
@@ -121,9 +103,8 @@ static int kn_run(const cp_kmer_sorted *s, const cp_unitigs *u, const int64_t *d
         { kn_count_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(d_utg,why,count,n,tile_n,ctl);
           HIPCHK(hipGetLastError());
           if (res)
-            { so_scan(tile_n,ntile,sum,st);
-              HIPCHK(hipGetLastError());
-              HIPCHK(hipMemcpyAsync(&n_out,tile_n+ntile-1,8,hipMemcpyDeviceToHost,st));
+            { rc = so_derived_counted(tile_n,ntile,sum,st,n_out);
+              if (rc != CP_OK) return rc;
             }
         }
       HIPCHK(hipMemcpyAsync(h_ctl,ctl,KN_CTL*8,hipMemcpyDeviceToHost,st));
@@ -131,18 +112,13 @@ static int kn_run(const cp_kmer_sorted *s, const cp_unitigs *u, const int64_t *d
   HIPCHK(hipStreamSynchronize(st));
   if (res)
     { if (n_out < 0 || n_out > n) return set_err(CP_EHIP,std::string(who)+": internal: the tile counts do not add up");
-      int rc = so_result_alloc(who,res,n_out,st);
+      so_dest o;
+      rc = so_derived_alloc(who,res,n_out,st,&o);
       if (rc != CP_OK) return rc;
       if (n_out > 0)
-        { const so_view va = so_view_of(s);
-          unsigned long long *hi = res->key, *lo = res->key+n_out, *cnt = res->key+2*n_out;
-          unsigned long long *cnt_of = (unsigned long long *)res->start+1;  // start[p+1] counts bucket p, then ends it
-          const int shift = 2*s->K-s->pbits;
-          if (2*s->K > 63) kn_write_kernel<true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,d_utg,why,count,tile_n,hi,lo,cnt,n_out,cnt_of,s->nb,shift);
-          else kn_write_kernel<false><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,d_utg,why,count,tile_n,hi,lo,cnt,n_out,cnt_of,s->nb,shift);
-          HIPCHK(hipGetLastError());
-          so_scan(res->start+1,s->nb,sum,st);
-          HIPCHK(hipGetLastError());
+        { rc = so_derived_write(s,kn_keep{ d_utg, why, count },2*s->K > 63,ntile,tile_n,o,st);
+          if (rc == CP_OK) rc = so_derived_starts(res,sum,st);
+          if (rc != CP_OK) return rc;
         }
       HIPCHK(hipStreamSynchronize(st));
     }
@@ -168,23 +144,8 @@ extern "C" int cp_kmer_sorted_unitig_prune(const cp_kmer_sorted *s, const cp_uni
   if (limits[0] < 0 || limits[1] < 0 || limits[2] < 0) return set_err(CP_EINVAL,std::string(who)+": a limit is negative");
   hipStream_t st = (hipStream_t)stream;
   cp_kmer_sorted *res = nullptr;
-  if (out)
-    { res = new (std::nothrow) cp_kmer_sorted();
-      if (!res) return set_err(CP_ENOMEM,std::string(who)+": out of memory");
-      res->K = s->K; res->ibyte = s->ibyte; res->pbits = s->pbits; res->nb = s->nb;
-    }
+  if (out && so_derived_new(who,s,&res) != CP_OK) return CP_ENOMEM;
   void *scratch = nullptr;
   const int rc = kn_run(s,u,d_utg,g,d_weight,limits,d_why,tally,st,res,&scratch);
-  if (rc != CP_OK) (void)hipStreamSynchronize(st);
-  if (scratch) (void)hipFree(scratch);
-  if (rc != CP_OK)
-    { cp_kmer_sorted_destroy(res);
-      return rc;
-    }
-  if (res)
-    { res->ready = true;
-      res->filled = res->n;
-      *out = res;
-    }
-  return CP_OK;
+  return so_derived_finish(rc,st,scratch,res,out);
 }

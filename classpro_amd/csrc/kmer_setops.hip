@@ -18,10 +18,16 @@
 //            and stores them with coalesced 8-byte stores.  A run of one bucket inside a tile adds its length to the
 //            bucket's counter by at most two 64-bit atomics (minus its first place, plus one past its last), and the
 //            same scan over the counters leaves the bucket starts.  No lane walks over empty buckets.
+//   derived  what every stage that makes a snapshot out of the kept entries of another shares, here once: the host steps
+//            (so_derived_*: the fresh result, the tile and scan sizes, the scan of the tile counts, the exact allocation,
+//            the scan of the bucket counters, the unwinding) and, for a per-entry predicate over ONE snapshot, the two
+//            kernels (ks_keep_count_kernel, ks_keep_write_kernel).  Used by kmer_hetpairs.hip, kmer_unitigs.hip (the
+//            count kernel) and kmer_prune.hip.
 // Every search has a constant bound and every index is clamped to its array.
 #define SO_CAP   (KS_TILE+1)                               // entries of a tile at most
 #define SO_PER   ((SO_CAP+KS_BLOCK-1)/KS_BLOCK)            // ranks per lane in the compaction
 #define SO_NONE  0xffffu
+#define HP_PER_LANE (KS_TILE/KS_BLOCK)                     // consecutive entries of a lane in the compaction by a predicate
 
 struct so_view { const unsigned long long *hi, *lo, *cnt; int64_t n; };
 
@@ -58,7 +64,7 @@ __global__ void __launch_bounds__(KT_BLOCK) so_cut_kernel(so_view a, so_view b, 
 
 // The kept entries of a tile from LDS to their places base.. of the result by coalesced 8-byte stores: entry i of the nk
 // is slot at(i) of (shi, slo, scn).  A run of one bucket adds its length to cnt_of[bucket] by at most two 64-bit atomics
-// (minus its first place, plus one past its last; per_entry: one atomic per entry instead).  Shared with kmer_hetpairs.hip.
+// (minus its first place, plus one past its last; per_entry: one atomic per entry instead).
 template <bool HI, class AT>
 __device__ static inline void so_store_kept(const unsigned long long *shi, const unsigned long long *slo,
                                             const unsigned long long *scn, AT at, int nk, int64_t base,
@@ -87,6 +93,47 @@ __device__ static inline void so_store_kept(const unsigned long long *shi, const
       else if (head) atomicAdd(&cnt_of[bk],0ull-(unsigned long long)g);      // the sums wrap to the run's length
       else if (tail) atomicAdd(&cnt_of[bk],(unsigned long long)g+1);
     }
+}
+
+// The compaction of ONE snapshot by a predicate (kmer_hetpairs.hip, kmer_unitigs.hip, kmer_prune.hip): KEEP is a small
+// struct passed by value whose operator()(int64_t i) says whether entry i is kept.
+// tile_n[t] = the kept entries among [t*KS_TILE, (t+1)*KS_TILE)
+template <class KEEP>
+__global__ void __launch_bounds__(KS_BLOCK) ks_keep_count_kernel(KEEP keep, int64_t n, int64_t *tile_n)
+{ __shared__ unsigned long long part[KS_BLOCK];
+  const int64_t i0 = (int64_t)blockIdx.x*KS_TILE;
+  unsigned long long mine = 0;
+  for (int s = threadIdx.x; s < KS_TILE; s += KS_BLOCK)
+    if (i0+s < n) mine += keep(i0+s);
+  const unsigned long long tot = ks_block_scan(mine,part);
+  if (threadIdx.x == KS_BLOCK-1) tile_n[blockIdx.x] = (int64_t)tot;
+}
+
+// tile_n holds the inclusive sums: the kept entries of a tile go to their places in order.  keep is asked once per entry.
+template <bool HI, class KEEP>
+__global__ void __launch_bounds__(KS_BLOCK) ks_keep_write_kernel(so_view a, KEEP keep, const int64_t *tile_n,
+                                                                 unsigned long long *ohi, unsigned long long *olo,
+                                                                 unsigned long long *ocn, int64_t on, unsigned long long *cnt_of,
+                                                                 int64_t nb, int shift)
+{ __shared__ unsigned long long shi[HI ? KS_TILE : 1], slo[KS_TILE], scn[KS_TILE];
+  __shared__ unsigned long long part[KS_BLOCK];
+  const int64_t t = blockIdx.x, i0 = t*KS_TILE+(int64_t)threadIdx.x*HP_PER_LANE;
+  unsigned int bits = 0, mine = 0;
+  for (int k = 0; k < HP_PER_LANE; k++)
+    { if (i0+k >= a.n) break;
+      if (keep(i0+k)) { bits |= 1u << k; mine++; }
+    }
+  int at = (int)(ks_block_scan((unsigned long long)mine,part)-(unsigned long long)mine);
+  for (int k = 0; k < HP_PER_LANE; k++)
+    { if (!((bits >> k) & 1u) || at >= KS_TILE) continue;
+      if (HI) shi[at] = a.hi[i0+k];
+      slo[at] = a.lo[i0+k];
+      scn[at] = a.cnt[i0+k];
+      at++;
+    }
+  __syncthreads();
+  const int nk = (int)min(part[KS_BLOCK-1],(unsigned long long)KS_TILE);
+  so_store_kept<HI>(shi,slo,scn,[](int i) { return i; },nk,t ? tile_n[t-1] : 0,ohi,olo,ocn,on,cnt_of,nb,shift,false);
 }
 
 // WRITE = false: tile_n[t] = the kept entries of tile t, tally += only in A, only in B, in both.
@@ -221,16 +268,93 @@ static int so_result_alloc(const char *who, cp_kmer_sorted *s, int64_t n_out, hi
   return rc;
 }
 
+// ---- a snapshot derived from one that exists: what cp_kmer_sorted_combine, cp_kmer_sorted_het_pairs and
+// cp_kmer_sorted_unitig_prune share on the host.  A caller counts the kept entries per tile into tile_n, calls
+// so_derived_counted, waits for the stream, calls so_derived_alloc, launches its write kernel and calls so_derived_starts.
+
+// where a write kernel puts the result: its three arrays, its entries, the bucket counters and the shift of ks_bucket
+struct so_dest { unsigned long long *hi, *lo, *cnt, *cnt_of; int64_t n, nb; int shift; };
+
+// a fresh result with the shape of the operand
+static int so_derived_new(const char *who, const cp_kmer_sorted *a, cp_kmer_sorted **res)
+{ cp_kmer_sorted *s = new (std::nothrow) cp_kmer_sorted();
+  if (!s) return set_err(CP_ENOMEM,std::string(who)+": out of memory");
+  s->K = a->K; s->ibyte = a->ibyte; s->pbits = a->pbits; s->nb = a->nb;
+  *res = s;
+  return CP_OK;
+}
+
+// the tiles of n entries and the words so_scan needs over them or over nb buckets: tile_n and sum are ntile+nsum words of
+// the caller's scratch, in that order.  bound: more tiles than the scan takes are refused.
+static int so_derived_tiles(const char *who, int64_t n, int64_t nb, bool bound, int64_t *ntile, int64_t *nsum)
+{ *ntile = (n+KS_TILE-1)/KS_TILE;
+  if (bound && *ntile > (int64_t)KS_CHUNK*KS_CHUNK) return set_err(CP_EINVAL,std::string(who)+": more than 2^24 tiles");
+  *nsum = std::max((*ntile+KS_CHUNK-1)/KS_CHUNK,(nb+KS_CHUNK-1)/KS_CHUNK);
+  return CP_OK;
+}
+
+// the tile counts to their inclusive sums; n_out is the last of them once the stream has been waited for
+static int so_derived_counted(int64_t *tile_n, int64_t ntile, unsigned long long *sum, hipStream_t st, int64_t &n_out)
+{ so_scan(tile_n,ntile,sum,st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&n_out,tile_n+ntile-1,8,hipMemcpyDeviceToHost,st));
+  return CP_OK;
+}
+
+// the result's memory at its exact size, and where its entries go
+static int so_derived_alloc(const char *who, cp_kmer_sorted *s, int64_t n_out, hipStream_t st, so_dest *o)
+{ const int rc = so_result_alloc(who,s,n_out,st);
+  if (rc != CP_OK) return rc;
+  *o = so_dest{ s->key, s->key+n_out, s->key+2*n_out, (unsigned long long *)s->start+1,  // start[p+1] counts bucket p, then ends it
+                n_out, s->nb, 2*s->K-s->pbits };
+  return CP_OK;
+}
+
+// the kept entries of every tile of a to their places, by a predicate
+template <class KEEP>
+static int so_derived_write(const cp_kmer_sorted *a, KEEP keep, bool with_hi, int64_t ntile, const int64_t *tile_n,
+                            const so_dest &o, hipStream_t st)
+{ const so_view va = so_view_of(a);
+  if (with_hi) ks_keep_write_kernel<true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,keep,tile_n,o.hi,o.lo,o.cnt,o.n,o.cnt_of,o.nb,o.shift);
+  else ks_keep_write_kernel<false><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,keep,tile_n,o.hi,o.lo,o.cnt,o.n,o.cnt_of,o.nb,o.shift);
+  HIPCHK(hipGetLastError());
+  return CP_OK;
+}
+
+// the bucket counters that the write kernel left to the bucket starts
+static int so_derived_starts(cp_kmer_sorted *s, unsigned long long *sum, hipStream_t st)
+{ so_scan(s->start+1,s->nb,sum,st);
+  HIPCHK(hipGetLastError());
+  return CP_OK;
+}
+
+// the end of the three calls: rc is what the passes returned.  The scratch goes; the result goes too when they failed,
+// otherwise it is ready and the caller's.
+static int so_derived_finish(int rc, hipStream_t st, void *scratch, cp_kmer_sorted *s, cp_kmer_sorted **out)
+{ if (rc != CP_OK) (void)hipStreamSynchronize(st);
+  if (scratch) (void)hipFree(scratch);
+  if (rc != CP_OK)
+    { cp_kmer_sorted_destroy(s);
+      return rc;
+    }
+  if (s)
+    { s->ready = true;
+      s->filled = s->n;
+      *out = s;
+    }
+  return CP_OK;
+}
+
 // the two passes; scratch and the result's memory are freed by the caller when this fails
 static int so_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b, const so_rule &r, bool with_hi, bool per_entry,
                       int64_t *tally,
                       hipStream_t st, cp_kmer_sorted *s, void **scratch)
 { const char *who = "cp_kmer_sorted_combine";
   const so_view va = so_view_of(a), vb = so_view_of(b);
-  const int64_t tot = a->n+b->n, ntile = (tot+KS_TILE-1)/KS_TILE;
-  if (ntile > (int64_t)KS_CHUNK*KS_CHUNK) return set_err(CP_EINVAL,std::string(who)+": more than 2^24 tiles");
-  const int64_t nsum = std::max((ntile+KS_CHUNK-1)/KS_CHUNK,(a->nb+KS_CHUNK-1)/KS_CHUNK);
-  int rc = ks_alloc(who,scratch,(size_t)(4+3*ntile+2+nsum)*8,"the cuts and the tile counts");
+  int64_t ntile, nsum;
+  int rc = so_derived_tiles(who,a->n+b->n,a->nb,true,&ntile,&nsum);
+  if (rc != CP_OK) return rc;
+  rc = ks_alloc(who,scratch,(size_t)(4+3*ntile+2+nsum)*8,"the cuts and the tile counts");
   if (rc != CP_OK) return rc;
   unsigned long long *d_tally = (unsigned long long *)*scratch, *sum = d_tally+4+3*ntile+2, h_tally[4] = { 0, 0, 0, 0 };
   int64_t *ci = (int64_t *)d_tally+4, *cj = ci+ntile+1, *tile_n = cj+ntile+1, n_out = 0;
@@ -248,9 +372,8 @@ static int so_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b, const so
                                                                        0,nullptr,0,0,false);
         }
       HIPCHK(hipGetLastError());
-      so_scan(tile_n,ntile,sum,st);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&n_out,tile_n+ntile-1,8,hipMemcpyDeviceToHost,st));
+      rc = so_derived_counted(tile_n,ntile,sum,st,n_out);
+      if (rc != CP_OK) return rc;
       HIPCHK(hipMemcpyAsync(h_tally,d_tally,24,hipMemcpyDeviceToHost,st));
     }
   HIPCHK(hipStreamSynchronize(st));
@@ -259,21 +382,19 @@ static int so_combine(const cp_kmer_sorted *a, const cp_kmer_sorted *b, const so
       tally[3] = n_out;
     }
   if (!s) return CP_OK;
-  rc = so_result_alloc(who,s,n_out,st);
+  so_dest o;
+  rc = so_derived_alloc(who,s,n_out,st,&o);
   if (rc != CP_OK) return rc;
   if (n_out > 0)
-    { unsigned long long *hi = s->key, *lo = s->key+n_out, *cnt = s->key+2*n_out;
-      unsigned long long *cnt_of = (unsigned long long *)s->start+1;       // start[p+1] counts bucket p, then ends it
-      const int shift = 2*s->K-s->pbits;
-      if (with_hi)
-        so_tile_kernel<true,true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,vb,r,ci,cj,tile_n,nullptr,hi,lo,cnt,n_out,cnt_of,s->nb,
-                                                                   shift,per_entry);
+    { if (with_hi)
+        so_tile_kernel<true,true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,vb,r,ci,cj,tile_n,nullptr,o.hi,o.lo,o.cnt,o.n,o.cnt_of,o.nb,
+                                                                   o.shift,per_entry);
       else
-        so_tile_kernel<false,true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,vb,r,ci,cj,tile_n,nullptr,hi,lo,cnt,n_out,cnt_of,s->nb,
-                                                                    shift,per_entry);
+        so_tile_kernel<false,true><<<(unsigned)ntile,KS_BLOCK,0,st>>>(va,vb,r,ci,cj,tile_n,nullptr,o.hi,o.lo,o.cnt,o.n,o.cnt_of,o.nb,
+                                                                    o.shift,per_entry);
       HIPCHK(hipGetLastError());
-      so_scan(s->start+1,s->nb,sum,st);
-      HIPCHK(hipGetLastError());
+      rc = so_derived_starts(s,sum,st);
+      if (rc != CP_OK) return rc;
     }
   HIPCHK(hipStreamSynchronize(st));
   return CP_OK;
@@ -300,29 +421,14 @@ extern "C" int cp_kmer_sorted_combine(const cp_kmer_sorted *a, const cp_kmer_sor
     }
   hipStream_t st = (hipStream_t)stream;
   cp_kmer_sorted *s = nullptr;
-  if (out)
-    { s = new (std::nothrow) cp_kmer_sorted();
-      if (!s) return set_err(CP_ENOMEM,"cp_kmer_sorted_combine: out of memory");
-      s->K = a->K; s->ibyte = a->ibyte; s->pbits = a->pbits; s->nb = a->nb;
-    }
+  if (out && so_derived_new("cp_kmer_sorted_combine",a,&s) != CP_OK) return CP_ENOMEM;
   bool with_hi = 2*a->K > 63;                              // below that hi[] is zero for every key
   if (const char *e = getenv("CLASSPRO_SETOP_HI")) with_hi = with_hi || atoi(e) != 0;   // A/B knob of scripts/setop_bench.py
   bool per_entry = false;                                  // one atomic per result entry instead of two per bucket run
   if (const char *e = getenv("CLASSPRO_SETOP_ATOMICS")) per_entry = strcmp(e,"entry") == 0;            // A/B knob as well
   void *scratch = nullptr;
   const int rc = so_combine(a,b,r,with_hi,per_entry,tally,st,s,&scratch);
-  if (rc != CP_OK) (void)hipStreamSynchronize(st);
-  if (scratch) (void)hipFree(scratch);
-  if (rc != CP_OK)
-    { cp_kmer_sorted_destroy(s);
-      return rc;
-    }
-  if (s)
-    { s->ready = true;
-      s->filled = s->n;
-      *out = s;
-    }
-  return CP_OK;
+  return so_derived_finish(rc,st,scratch,s,out);
 }
 
 extern "C" int cp_kmer_sorted_hist(const cp_kmer_sorted *s, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt)

@@ -1,8 +1,8 @@
 // kmer_unitigs.hip -- the unitigs of the de Bruijn graph that ONE sorted snapshot implies (tabunitig): which canonical
 // k-mers follow which, the maximal non-branching chains of that graph spelled as sequences, and where every key lies in
 // them.  Semantics: include/classpro_amd.h, "Unitigs of sorted k-mers"; design: DESIGN.md 9.19.  Included by capi.hip after
-// kmer_hetpairs.hip (kl_view, kl_find_group, hp_rule, hp_revcomp, so_scan, ks_alloc, ks_block_scan, the scan kernels of
-// kmer_sort.hip, kc_wave_add, set_err and HIPCHK are in scope).  The operand is only read.
+// kmer_hetpairs.hip (kl_view, kl_find_group, hp_rule, hp_revcomp, so_scan, ks_keep_count_kernel, ks_alloc, ks_block_scan,
+// the scan kernels of kmer_sort.hip, kc_wave_add, set_err and HIPCHK are in scope).  The operand is only read.
 //   state    entry i has the states 2i (spells the key X) and 2i+1 (spells rc(X)); flip(s) = s ^ 1.  A state is below 2^31.
 //   adj      one lane per entry.  rc(X) once; the successor c of a string w with reverse complement r is
 //            f = (w << 2 | c) under the 2K-bit mask, and its reverse complement is r >> 2 | (3-c) << 2K-2, so the canonical
@@ -196,16 +196,11 @@ __global__ void __launch_bounds__(KT_BLOCK) ug_choose_kernel(unsigned long long 
     }
 }
 
-// tile_n[t] = the kept heads among the entries [t*KS_TILE, (t+1)*KS_TILE)
-__global__ void __launch_bounds__(KS_BLOCK) ug_count_kernel(const uint8_t *head, int64_t n, int64_t *tile_n)
-{ __shared__ unsigned long long part[KS_BLOCK];
-  const int64_t i0 = (int64_t)blockIdx.x*KS_TILE;
-  unsigned long long mine = 0;
-  for (int s = threadIdx.x; s < KS_TILE; s += KS_BLOCK)
-    if (i0+s < n) mine += head[i0+s] != 0;
-  const unsigned long long tot = ks_block_scan(mine,part);
-  if (threadIdx.x == KS_BLOCK-1) tile_n[blockIdx.x] = (int64_t)tot;
-}
+// the predicate of ks_keep_count_kernel: entry i has a kept head
+struct ug_is_head
+  { const uint8_t *head;
+    __device__ bool operator()(int64_t i) const { return head[i] != 0; }
+  };
 
 // tile_n holds the inclusive sums.  Kept head of entry i: ord[i] = its unitig u, off[u+1] = its bases, flag[u]; the
 // longest and the closed ones into the tally
@@ -384,7 +379,7 @@ static int ug_run(const cp_kmer_sorted *s, hp_rule r, bool chains, bool spell, i
             }
           ug_choose_kernel<<<sgrid,KT_BLOCK,0,st>>>(word,prev,ns,head);
           HIPCHK(hipGetLastError());
-          ug_count_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(head,n,tile_n);
+          ks_keep_count_kernel<<<(unsigned)ntile,KS_BLOCK,0,st>>>(ug_is_head{ head },n,tile_n);
           HIPCHK(hipGetLastError());
           so_scan(tile_n,ntile,second,st);
           HIPCHK(hipGetLastError());

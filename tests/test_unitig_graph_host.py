@@ -14,7 +14,7 @@ import pytest
 import ktab_oracle as KO
 import unitig_graph_oracle as GO
 import unitig_oracle as UO
-from conftest import ROOT
+from conftest import ROOT, build_if_changed
 from test_gpu_ktab import mixed_reads
 from test_tabprof_host import NO_GPU, SPOILED, listing, spoil
 from test_unitig_host import clean, key, rcs, rnd
@@ -220,6 +220,23 @@ def test_symbols_are_declared_listed_and_exported(built):
     assert L.cp_unitig_graph_links(None) == 0
     assert L.cp_unitig_graph_arrays(None, None, None, None, None) == -1 and b"cp_unitig_graph_arrays" in L.cp_last_error()
     L.cp_unitig_graph_destroy(None)
+
+
+# ---- the windows of the FASTA and GFA writers on the host ----
+
+def test_windows_on_the_host():
+    """classpro_amd/csrc/host/unitig_window.h compiles for the host: tests/window_check.cpp runs its Window and its two
+    writers with a fetch from host arrays at windows of 1 to 4 elements -- a unitig that ends at a refill, starts at one,
+    spans two and three windows; 5 unitigs and 7 links at unitig windows of 1 and 2 and link windows of 1, 2 and 3, with and
+    without the RC tags; no unitig at all -- under AddressSanitizer and UBSan, byte for byte against a writer that holds
+    everything."""
+    src = os.path.join(ROOT, "tests", "window_check.cpp")
+    exe = os.path.join(ROOT, "tests", "_window_check")
+    inc = os.path.join(ROOT, "classpro_amd", "csrc")
+    build_if_changed(exe, ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + inc,
+                           "-o", exe, src], [src, os.path.join(inc, "host", "unitig_window.h")])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert (r.returncode, r.stdout, r.stderr) == (0, "ok\n", "")
 
 
 # ---- tabgraph's errors ----
