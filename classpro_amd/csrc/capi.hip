@@ -658,8 +658,9 @@ static int stage_classify_rel(cp_workspace *ws, run_ctx &c)
 static int stage_classify_unrel(cp_workspace *ws, run_ctx &c)
 { const int nreads = c.nreads;
   ENSURE(ws->b.ord,(size_t)c.totalI*4);
-  // size classes (kernels.hip: UNREL_SMALL_*): N <= 256 and up to 1024, two reads per wave each (four speculative update
-  // slots per read), larger: the sequential kernel; the rare classes on the auxiliary stream again
+  // size classes (kernels.hip: UNREL_SMALL_*, UNREL_BIG_G, UNREL_LPS): N <= 256, two reads per wave (eight speculative
+  // update slots of four lanes per read), and up to 1024, one read per wave (sixteen slots); larger: the sequential
+  // kernel; the rare classes on the auxiliary stream again
   CHK(launch_order_by_work(ws,as<int32_t>(ws->b.nintvl),nreads,0,as<int32_t>(ws->b.perm),c.st,c.d_prof_off));
   CHK(fork_aux(ws,c.st));
   hipLaunchKernelGGL(k_classify_unrel,dim3(nreads < 1024 ? nreads : 1024),dim3(WAVE),0,ws->aux,
@@ -1168,8 +1169,8 @@ extern "C" int cp_debug_emit_prof(unsigned long long *out8)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_emit_prof),8); }
 extern "C" int cp_debug_fw_prof(unsigned long long *out12)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_fw_prof),12); }
-extern "C" int cp_debug_unrel_prof(unsigned long long *out8)
-{ HIPCHK(hipDeviceSynchronize()); return prof_read(out8,HIP_SYMBOL(g_unrel_prof),8); }
+extern "C" int cp_debug_unrel_prof(unsigned long long *out12)
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_unrel_prof),12); }
 extern "C" int cp_debug_rel_prof(unsigned long long *out12)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_rel_prof),12); }
 extern "C" int cp_debug_phase_prof(unsigned long long *out36)

@@ -17,7 +17,7 @@
 //   k_find_wall         one wave per read: the walk's replay (dependency rounds, flags in LDS) and everything after it, wall.c:639-958
 //   k_find_rel          one wave per read, one lane per interval: wall.c:960-1051
 //   k_classify_rel_grp   8 reads per wave (1 for M > 112), 4 lanes per direction: class_rel.c:871-963
-//   k_classify_unrel_grp 2 reads per wave, speculative update slots committed in order: class_unrel.c:248-300
+//   k_classify_unrel_grp 2 reads per wave (1 for N > 256), speculative update slots of 4 lanes committed in order: class_unrel.c:248-300
 //   k_classify_rel / k_classify_unrel   sequential forms for reads with > 1024 intervals or > 65535 k-mers
 //   k_skellam_table     the table of logp_trans values (cp_types.h), filled once per cp_params
 //   k_seed_caps / k_find_seeds   the -s seed path, one wave per read (cp_seed_wave.h): seed.c:966-1032
@@ -868,7 +868,7 @@ __device__ __forceinline__ cp_intvl cp_soa_get(const cp_soa &S, int64_t at)
 #ifdef CP_PROF_WALK
 __device__ unsigned long long g_phase_max[12], g_phase_sum[12], g_phase_arg[12];
 __device__ unsigned long long g_live_prof[8];
-__device__ unsigned long long g_unrel_prof[8];          // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] of a round up to its first global load, [2] of the kernel; [3] waves; [4] of a round from there to the new classes (waiting for the loads and using them); [5] of the interval load before the rounds, [6] of the sort
+__device__ unsigned long long g_unrel_prof[12];         // k_classify_unrel_grp, main class: wave time [0] committing the slots, [1] of a round up to its first global load, [2] of the kernel; [3] waves; [4] of a round from there to the new classes (waiting for the loads and using them); [5] of the interval load before the rounds, [6] of the sort; rare class: [8] rounds of the first sweep, [9] of the second, [10] non-fixed intervals, [11] reads
 __device__ unsigned long long g_emit_prof[8];           // k_find_wall: reads whose E-interval list has at most 64 entries and the summed list lengths, [0],[1] before the un-wall, [2],[3] before the merge, [4],[5] before the components; k_classify_rel_grp: [6] repeated passes, [7] waves with a second DP (count | total << 32)
 // k_find_wall's hand-off from k_wall_tasks and its emission loop, slots of their own (g_emit_prof and g_live_prof are shared with
 // the list-length and round statistics): wave time [0] of the head, from entry until the replay's first chunk begins,
@@ -2978,13 +2978,25 @@ __device__ double rel_post2_quad(const cp_dev_params *P, const Rv &rv, int M, in
 #define REL_SMALL_G 8
 #endif
 // (REL_SMALL_MAXM: defined at the top of the file, k_find_wall needs it)
-// (unrel, later, with K = 64/G/8 speculative update slots per read: G = 4 4.28 ms per step, G = 2 4.07, G = 1 4.04)
+// (unrel, later, with K = 64/G/8 speculative update slots per read: G = 4 4.28 ms per step, G = 2 4.07, G = 1 4.04 --
+//  with eight lanes per slot a wave holds eight slots whatever G is, so G moved nothing.  With UNREL_LPS = 4 lanes per
+//  slot a wave holds sixteen: G = 2 gives a read eight slots per round, and the first sweep of a read of the bench
+//  (48 non-fixed intervals) takes about half the rounds: profiles/unrel_wide_rounds_ab.txt.)
 #ifndef UNREL_SMALL_G
 #define UNREL_SMALL_G 2
 #endif
+// lanes per speculative slot of k_classify_unrel_grp: 8 ({H,D} x {left,right} x {Skellam term, binomial term}) or 4 (a lane
+// takes both terms of its class and side)
+#ifndef UNREL_LPS
+#define UNREL_LPS 4
+#endif
+// order positions a round of the second sweep looks at, in units of the read's lanes (1 or 2: a lane tests that many)
+#ifndef UNREL_SWEEP2_WIN
+#define UNREL_SWEEP2_WIN 2
+#endif
 // (UNREL_SMALL_MAXN: defined at the top of the file, k_find_wall needs it)
 // the class above it holds a handful of reads per sub-batch, each a chain of several hundred updates: one read per wave
-// (eight speculative slots) -- with two, the stage's main kernel waited 0.5 ms for this one at its end
+// (sixteen speculative slots at four lanes each) -- with two, the stage's main kernel waited 0.5 ms for this one at its end
 #ifndef UNREL_BIG_G
 #define UNREL_BIG_G 1
 #endif
@@ -3180,15 +3192,21 @@ k_classify_rel_grp(const cp_dev_params *__restrict__ P, const int64_t *__restric
 }
 
 // ---------------------------------------------------------------------------------------------
-//  k_classify_unrel_grp<MINN,MAXN,G>: class_unrel.c:248-300, G reads per wave (64/G >= 8 lanes per
-//  read) for reads with MINN < N <= MAXN.
+//  k_classify_unrel_grp<MINN,MAXN,G,COMPACT,LPS>: class_unrel.c:248-300, G reads per wave (L = 64/G
+//  lanes per read, L/LPS speculative update slots of LPS lanes) for reads with MINN < N <= MAXN.
 //
 //  Interval fields (16-bit) sit in LDS; "nearest reliable interval of class s" (find_nn_u, a linear
 //  scan in the reference) is a bit scan over two LDS bitsets kept up to date as classes change.  The
 //  two sweeps stay sequential per read (every update reads its neighbours' current classes), but one
 //  wave advances G reads at once and inside an update the eight expensive terms -- {H,D} x
-//  {left,right} x {Skellam transition, binomial tail} (class_unrel.c:115-175) -- sit on eight lanes,
-//  the Skellam ones of all reads meeting at one convergent Bessel call.
+//  {left,right} x {Skellam transition, binomial tail} (class_unrel.c:115-175) -- sit on the slot's
+//  lanes: one each with LPS = 8, and with LPS = 4 (shipped) the two terms of a (class, side) on one
+//  lane, their two table entries in flight together.  The eight lanes of a slot computed the same
+//  LDS reads, bit scans, E and R terms and differed in one look-up each, and the two kinds sat on the
+//  two sides of a branch that diverged inside every wave: four lanes issue about the same
+//  instructions per round and a read gets twice the slots (eight for N <= 256, sixteen above), so
+//  the first sweep takes half the rounds (profiles/unrel_wide_rounds_ab.txt).  The terms outside a
+//  table meet at one convergent out-of-line call per kind.
 // ---------------------------------------------------------------------------------------------
 template <int MAXN, int G>
 struct unrel_grp_lds
@@ -3224,7 +3242,7 @@ __device__ __forceinline__ int bits_right(const uint64_t *bits, int idx, int nwo
 #ifndef UNREL_WAVES_PER_EU
 #define UNREL_WAVES_PER_EU 4
 #endif
-template <int MINN, int MAXN, int G, int COMPACT = 0>
+template <int MINN, int MAXN, int G, int COMPACT = 0, int LPS = UNREL_LPS>
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(UNREL_WAVES_PER_EU)))
 k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *__restrict__ intvl_all,
                      const int64_t *__restrict__ ioff, const int32_t *__restrict__ nintvl,
@@ -3235,13 +3253,16 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   // (the rare class on whole-path calls): the 48-byte records, the classes of classify_rel from the two-byte array.
   __shared__ unrel_grp_lds<MAXN,G> S;
   constexpr int L = WAVE/G;
-  static_assert(L >= 8 && (L % 8) == 0, "8 role lanes per read");
+  static_assert((LPS == 4 || LPS == 8) && L >= LPS, "4 or 8 role lanes per slot");
   const int lane = lane_id();
   const int g = lane/L, ql = lane%L, gbase = g*L;
-  // role of this lane inside its slot: class (H,D) x side (L,R) x kind (0: max(er,sf), 1: sf_er) -- see the rounds below
-  constexpr int K = L/8;
-  const int sub = ql >> 3, role = ql & 7, sbase = gbase+sub*8;
-  const int s2 = (role >> 2) & 1, side = (role >> 1) & 1, kind = role & 1;
+  // role of this lane inside its slot: class (H,D) x side (L,R), and with eight lanes per slot x kind (0: max(er,sf),
+  // 1: sf_er); with four a lane takes both kinds -- see the rounds below
+  constexpr int K = L/LPS;
+  constexpr bool BOTH = LPS == 4;
+  const int sub = ql/LPS, role = ql%LPS, sbase = gbase+sub*LPS;
+  const int cs = BOTH ? role : role >> 1, kind = BOTH ? 0 : role & 1;
+  const int s2 = (cs >> 1) & 1, side = cs & 1;
   const int s = s2 ? CP_DIPLO : CP_HAPLO;
   // What a round reads of *P is constant for the kernel, and between two rounds lie LDS atomics and stores, behind which
   // the compiler reads every field again: once per block, here.  log(lambda) of the three Poisson terms is constant too.
@@ -3359,7 +3380,7 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
 
   // The reference updates the non-fixed intervals one after the other (class_unrel.c:260-274), and an
   // update costs one Bessel recurrence of latency.  An update reads the neighbouring intervals' classes
-  // and the reliable-H / reliable-D sets, which most updates leave untouched, so the K = L/8 groups of 8
+  // and the reliable-H / reliable-D sets, which most updates leave untouched, so the K = L/LPS groups of LPS
   // lanes of a read take K consecutive updates at once (slots), which are then committed in order:
   // a slot is committed only if no earlier slot of the round changed the class of one of its neighbours
   // or either set; otherwise the round ends there and the next one starts from that update.  Where the
@@ -3376,14 +3397,16 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   // included: the intervals whose nearest member on one side is or was j).  An interval whose bit is clear in the second
   // sweep would get the class it has: it is skipped -- on reads like the bench's 95 % of that sweep
   // (tests/test_unrel_memo.py runs this rule against the two plain sweeps on the host).  A round of the second sweep
-  // looks at the next L order positions, gives its K slots the first K whose bit is set, and ends behind a slot that
-  // changes a class (what lies behind may have been skipped on the strength of a bit that slot has just set).
+  // looks at the next 2L order positions (a lane tests two: with one, a read of the bench, 48 non-fixed intervals on 32
+  // lanes, took two rounds for a sweep that has three or four updates to do), gives its K slots the first K whose bit is
+  // set, and ends behind a slot that changes a class (what lies behind may have been skipped on the strength of a bit
+  // that slot has just set).
   //
   // A ROUND'S GLOBAL LOADS ARE IN FLIGHT TOGETHER.  A round is one dependent chain, and at four waves per SIMD its length is
   // the kernel's time.  Every address of a round is known once the slot's LDS fields and bit scans are: the interval's
   // cold record (pe on every lane, peo_b / peo_e on the lane whose role asks for it), logfact of the two counts (shared
   // by the E term, the R term and the Poisson fallback), logfact of the R term's other four arguments, and the lane's
-  // Skellam or uerr table entry.  They are issued in that order with nothing waiting in between -- the estimate behind
+  // Skellam and uerr table entries.  They are issued in that order with nothing waiting in between -- the estimate behind
   // the uerr address (an FP64 division) is computed while the others are under way -- and the values are selected
   // afterwards exactly as class_unrel.c does.  A slot without an update forms no address.
   const uint64_t glm = (L == 64) ? ~0ull : ((1ull << L)-1);
@@ -3397,20 +3420,27 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
       { int mypos = it+sub;                                // order position of this slot's update
         int cover = (it+K < nnf) ? it+K : nnf;             // the round settles the positions [it, cover) if every slot commits
         if (pass == 1)
-          { const int p = it+ql;
-            bool dirty = false;
-            if (!done && p < nnf)
-              { const int k = S_ORD(p);
-                dirty = full_sweep2 || ((S.need[g][k >> 6] >> (k & 63)) & 1);     // (full_sweep2: the A/B and test knob CLASSPRO_UNREL_SWEEP2=full)
-              }
-            const uint64_t m = (__ballot(dirty) >> gbase) & glm;
-            uint64_t t = m;
-            for (int j = 0; j < sub; j++) t &= t-1;
-            mypos = t ? it+__ffsll((long long)t)-1 : nnf;
-            uint64_t t2 = m;
+          { uint64_t m[2] = { 0, 0 };                      // a lane tests two positions: the window is 2L positions, m[1]:m[0]
 #pragma unroll
-            for (int j = 0; j < K; j++) t2 &= t2-1;
-            cover = t2 ? it+__ffsll((long long)t2)-1 : ((it+L < nnf) ? it+L : nnf);
+            for (int h = 0; h < UNREL_SWEEP2_WIN; h++)
+              { const int p = it+h*L+ql;
+                bool dirty = false;
+                if (!done && p < nnf)
+                  { const int k = S_ORD(p);
+                    dirty = full_sweep2 || ((S.need[g][k >> 6] >> (k & 63)) & 1);     // (full_sweep2: the A/B and test knob CLASSPRO_UNREL_SWEEP2=full)
+                  }
+                m[h] = (__ballot(dirty) >> gbase) & glm;
+              }
+            const int c0 = __popcll(m[0]);
+            auto nth = [&](int n) -> int                   // the window's n-th dirty position (from 0), -1: fewer than that
+              { const bool hi = n >= c0;
+                uint64_t t = hi ? m[1] : m[0];
+                for (int j = hi ? n-c0 : n; j > 0; j--) t &= t-1;
+                return t ? (hi ? L : 0)+__ffsll((long long)t)-1 : -1;
+              };
+            const int mine = nth(sub), next = nth(K);
+            mypos = mine >= 0 ? it+mine : nnf;
+            cover = next >= 0 ? it+next : ((it+UNREL_SWEEP2_WIN*L < nnf) ? it+UNREL_SWEEP2_WIN*L : nnf);
           }
         const bool act = !done && mypos < nnf;             // this slot has an update to do
         bool on = act;
@@ -3434,10 +3464,11 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
         // The Skellam term and the binomial term are table look-ups (cp_types.h: skel, uerr; the recurrence / the
         // tail sum only outside the tables), so the second sweep simply evaluates them again: the per-interval memo
         // in HBM that used to carry them from the first sweep cost more than that.
-        bool do_sf = false, do_bin = false, in_tab = false, r_in = false;
-        int oa = 0, ob = 0, oc = 0;                        // outside the tables: (ce-cb, cov, d) of the Skellam term, (est, c) of the binomial one
+        bool do_sf = false, do_bin = false, sf_tab = false, bin_tab = false, r_in = false;
+        int oa = 0, ob = 0, oc = 0;                        // outside the tables: (ce-cb, cov, d) of the Skellam term,
+        int ua = 0, uc = 0;                                // (est, c) of the binomial one
         int kb = 0, ke = 0, nl = 0, nr = 0;                // the checked counts of the interval and of the R term
-        double er = -INFINITY, val = -INFINITY, pe = 0., lfb = 0., lfe = 0., lfnl = 0., lfdl = 0., lfnr = 0., lfdr = 0.;
+        double er = -INFINITY, vsf = -INFINITY, vbin = -INFINITY, pe = 0., lfb = 0., lfe = 0., lfnl = 0., lfdl = 0., lfnr = 0., lfdr = 0.;
         if (on)
           { const double *const rec = COMPACT ? &soa.b[io+idx].pe : &intvl[idx].pe;
             const double *const rec_er = side ? (COMPACT ? &soa.b[io+idx].peo_e : &intvl[idx].peo_e)
@@ -3460,10 +3491,10 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
                   lfnl = logfact[nl]; lfdl = logfact[nl-kb]; lfnr = logfact[nr]; lfdr = logfact[nr-ke];
                 }
             }
-            const double *at = nullptr;
+            const double *at_sf = nullptr, *at_bin = nullptr;
             const int Ib = S.b[g][idx], Ie = S.e[g][idx];
             const int l_rel = s2 ? lD : lH, r_rel = s2 ? rD : rH;
-            if (kind == 0)                                 // class_unrel.c:123-163, arguments only
+            if (BOTH || kind == 0)                         // class_unrel.c:123-163, arguments only
               { int tb = 0, te = 0, tcb = 0, tce = 0, tcov = 0;
                 if (side == 0 && l_rel != -1)
                   { do_sf = true; tb = S.e[g][l_rel]-1; te = Ib; tcb = S.cce[g][l_rel]; tce = Icb; tcov = tcb; }
@@ -3471,10 +3502,10 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
                   { do_sf = true; tb = Ie-1; te = S.b[g][r_rel]; tcb = Ice; tce = S.ccb[g][r_rel]; tcov = tce; }
                 if (do_sf)                                 // cp_logp_trans, its two steps apart
                   { oa = tce-tcb; ob = tcov & 0xffff; oc = te-tb < 0 ? tb-te : te-tb;
-                    at = cp_logp_trans_at(skel,skel_kmax,skel_cdmax,oc,tcb,tce,ob);
+                    at_sf = cp_logp_trans_at(skel,skel_kmax,skel_cdmax,oc,tcb,tce,ob);
                   }
               }
-            else
+            if (BOTH || kind == 1)
               { const int x = side ? Ie-1 : Ib;
                 const int c = side ? Ice : Icb;
                 // est_cov, class_unrel.c:27-51: this class's neighbours, else the other class's
@@ -3494,24 +3525,31 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
                 const int est = (e1 >= 0) ? e1 : (s2 ? covD : covH);
                 do_bin = est >= c;
                 if (do_bin)                                // cp_logp_uerr, its two steps apart
-                  { oa = est; ob = c;
-                    at = cp_logp_uerr_at(uerr,uerr_max,est,c);
+                  { ua = est; uc = c;
+                    at_bin = cp_logp_uerr_at(uerr,uerr_max,est,c);
                   }
               }
-            in_tab = at != nullptr;
-            if (in_tab) val = *at;
+            sf_tab = at_sf != nullptr; bin_tab = at_bin != nullptr;
+            if (sf_tab)  vsf = *at_sf;                     // (with four lanes per slot: both of them in flight together)
+            if (bin_tab) vbin = *at_bin;
           }
-        if (do_sf && !in_tab)
-          val = cp_logp_trans_calc(P,oa,(double)ob*oc);
-        if (do_bin && !in_tab)
-          val = cp_logp_uerr_calc(P,oa,ob);
+        if (do_sf && !sf_tab)
+          vsf = cp_logp_trans_calc(P,oa,(double)ob*oc);
+        if (do_bin && !bin_tab)
+          vbin = cp_logp_uerr_calc(P,ua,uc);
         if (on)
-          { if (kind == 0)
-              val = (er > val) ? er : val;
-            double v1 = __shfl_down(val,1);
-            double sidev = (val > v1) ? val : v1;              // MAX(MAX(er,sf),sf_er) on lanes with kind 0
-            double vr = __shfl_down(sidev,2);
-            double logp_l = sidev, logp_r = vr;                // meaningful on role lanes 0 (H) and 4 (D)
+          { double sidev;                                      // MAX(MAX(er,sf),sf_er): class_unrel.c:150,163
+            if constexpr (BOTH)
+              { const double a = (er > vsf) ? er : vsf;
+                sidev = (a > vbin) ? a : vbin;
+              }
+            else
+              { const double val = (kind == 0) ? ((er > vsf) ? er : vsf) : vbin;
+                const double v1 = __shfl_down(val,1);
+                sidev = (val > v1) ? val : v1;                 // (on the lanes with kind 0)
+              }
+            double vr = __shfl_down(sidev,LPS/4);
+            double logp_l = sidev, logp_r = vr;                // meaningful on the slot's lanes 0 (H) and LPS/2 (D)
             if (logp_l == -INFINITY && logp_r == -INFINITY)    // class_unrel.c:165-173 (cp_logp_poisson on what is loaded)
               { logp_l = cp_logp_poisson_vals(kb,s2 ? llD : llH,s2 ? covD : covH,lfb);
                 logp_r = cp_logp_poisson_vals(ke,s2 ? llD : llH,s2 ? covD : covH,lfe);
@@ -3519,7 +3557,7 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
             else if (logp_l == -INFINITY) logp_l = logp_r;
             else if (logp_r == -INFINITY) logp_r = logp_l;
             const double logp_s = logp_l+logp_r;
-            const double vH = __shfl(logp_s,sbase), vD = __shfl(logp_s,sbase+4);
+            const double vH = __shfl(logp_s,sbase), vD = __shfl(logp_s,sbase+LPS/2);
             // E and R are table look-ups (class_unrel.c:53-113)
             const double po = cp_logp_poisson_vals(kb,llE,covE,lfb)+cp_logp_poisson_vals(ke,llE,covE,lfe)+CP_E_PO_BASE;
             const double vE = (pe > po) ? pe : po;
@@ -3550,15 +3588,21 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
             setc = hd && S.isrel[g][idx];                      // idx leaves / joins the reliable-H or the reliable-D set
           }
         const uint64_t m_hd = __ballot(hd), m_setc = __ballot(setc);
-        const int osl = gbase+8*(role & (K-1));                // lane `role` of a slot looks at slot `role`
-        const int oidx = __shfl(idx,osl);
-        const bool cl = role < sub && (((m_setc >> osl) & 1) || (((m_hd >> osl) & 1) && (oidx == idx-1 || oidx == idx+1)));
-        constexpr uint64_t LEADS = 0x0101010101010101ull & ((L == 64) ? ~0ull : ((1ull << L)-1));
+        bool cl = false;                                       // lane `role` of a slot looks at the slots role, role+LPS, ... below its own
+#pragma unroll
+        for (int c = 0; c < (K+LPS-1)/LPS; c++)
+          { const int o = role+c*LPS;
+            const int osl = gbase+LPS*(o & (K-1));             // (o >= K: no slot, and not below `sub` either)
+            const int oidx = __shfl(idx,osl);
+            cl |= o < sub && (((m_setc >> osl) & 1) || (((m_hd >> osl) & 1) && (oidx == idx-1 || oidx == idx+1)));
+          }
+        constexpr uint64_t LEADS = (LPS == 8 ? 0x0101010101010101ull : 0x1111111111111111ull) & ((L == 64) ? ~0ull : ((1ull << L)-1));
+        constexpr uint64_t LOWS  = (LPS == 8 ? 0x7f7f7f7f7f7f7f7full : 0x7777777777777777ull);             // a slot's lanes but its last
         const uint64_t clm = (__ballot(cl) >> gbase) & glm;
-        const uint64_t cb = ((clm | ((clm & 0x7f7f7f7f7f7f7f7full)+0x7f7f7f7f7f7f7f7full)) >> 7) & LEADS;   // bit 8j: slot j clashes
-        const uint64_t ub = (__ballot(lead && upd) >> gbase) & glm;                                         // bit 8j: slot j has an update
+        const uint64_t cb = ((clm | ((clm & LOWS)+LOWS)) >> (LPS-1)) & LEADS;                               // bit LPS*j: slot j clashes
+        const uint64_t ub = (__ballot(lead && upd) >> gbase) & glm;                                         // bit LPS*j: slot j has an update
         const uint64_t stop = (~ub & LEADS) | cb;
-        const int js = stop ? __ffsll((long long)stop)-1 : L;  // (in lanes: 8 x the slot)
+        const int js = stop ? __ffsll((long long)stop)-1 : L;  // (in lanes: LPS x the slot)
         const uint64_t hb = ((m_hd >> gbase) & glm) & (js < 64 ? (1ull << js)-1 : ~0ull);
         const bool hstop = pass == 1 && hb != 0;               // positions behind it were skipped on bits this change may have set
         const int jh = hstop ? __ffsll((long long)hb)-1 : 0;
@@ -3605,6 +3649,9 @@ k_classify_unrel_grp(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *
   if (ql == 0 && N > 0 && MINN == 0)                       // rounds of the first / second sweep, non-fixed intervals, reads (main class)
     { atomicAdd(&g_phase_sum[9],(unsigned long long)prof_rounds[0]); atomicAdd(&g_phase_max[9],(unsigned long long)prof_rounds[1]);
       atomicAdd(&g_phase_sum[10],(unsigned long long)nnf); atomicAdd(&g_phase_sum[11],1ull); }
+  if (ql == 0 && N > 0 && MINN > 0)                        // the same of the rare class
+    { atomicAdd(&g_unrel_prof[8],(unsigned long long)prof_rounds[0]); atomicAdd(&g_unrel_prof[9],(unsigned long long)prof_rounds[1]);
+      atomicAdd(&g_unrel_prof[10],(unsigned long long)nnf); atomicAdd(&g_unrel_prof[11],1ull); }
   if (lane == 0 && MINN == 0)
     { atomicAdd(&g_unrel_prof[0],ur_commit); atomicAdd(&g_unrel_prof[1],ur_pre); atomicAdd(&g_unrel_prof[4],ur_use);
       atomicAdd(&g_unrel_prof[5],ur_load); atomicAdd(&g_unrel_prof[6],ur_sort);

@@ -27,7 +27,7 @@ clf = Classifier(40, 20000, hc, dc)
 ph = (C.c_ulonglong * 36)()
 lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
-ur = (C.c_ulonglong * 8)()
+ur = (C.c_ulonglong * 12)()
 rp = (C.c_ulonglong * 12)()
 fw = (C.c_ulonglong * 12)()
 clf.classify(b)
@@ -57,8 +57,10 @@ print("k_find_wall, emission loop, ticks per read: boundaries %.1f, cp_make_inte
       % (fw[4] / b.nreads, fw[5] / b.nreads, fw[6] / b.nreads, fw[7] / b.nreads))
 print("E-interval lists of at most 64 (the wave-parallel forms): before the un-wall %d reads (mean length %.1f), before the merge %d (%.1f), before the components %d (%.1f)"
       % (em[0], em[1] / b.nreads, em[2], em[3] / b.nreads, em[4], em[5] / b.nreads))
-print("classify_unrel (main class): %.1f non-fixed intervals per read, %.1f speculation rounds in the first sweep (four slots per round), %.1f in the second"
+print("classify_unrel (main class): %.1f non-fixed intervals per read, %.1f speculation rounds in the first sweep (eight slots per round: UNREL_SMALL_G = 2 reads per wave, UNREL_LPS = 4 lanes per slot), %.1f in the second"
       % (ph[12 + 10] / max(1, ph[12 + 11]), ph[12 + 9] / max(1, ph[12 + 11]), ph[9] / max(1, ph[12 + 11])))
+print("classify_unrel (rare class, sixteen slots per round): %d reads, %.1f non-fixed intervals per read, %.1f rounds in the first sweep, %.1f in the second"
+      % (ur[11], ur[10] / max(1, ur[11]), ur[8] / max(1, ur[11]), ur[9] / max(1, ur[11])))
 nw, tot = max(1, ur[3]), max(1, ur[2])
 print("classify_unrel (main class): %d waves, %.1f ticks per wave" % (ur[3], ur[2] / nw))
 for name, v in (("interval load before the rounds", ur[5]), ("sort of the non-fixed intervals", ur[6]),
