@@ -1124,9 +1124,9 @@ extern "C" int cp_debug_seed_get(int *out4, int *recs)
 }
 #endif
 #if defined(CP_SEED_PROF) || defined(CP_PROF_WALK)
-// diagnostic builds only: n <= 12 words of a device profile array to the host, then (reset) zeroed on the device
+// diagnostic builds only: n <= 13 words of a device profile array to the host, then (reset) zeroed on the device
 static int prof_read(unsigned long long *out, const void *sym, size_t n, bool reset = true)
-{ static const unsigned long long z[12] = {0};
+{ static const unsigned long long z[13] = {0};
   HIPCHK(hipMemcpyFromSymbol(out,sym,n*sizeof(unsigned long long)));
   if (reset) HIPCHK(hipMemcpyToSymbol(sym,z,n*sizeof(unsigned long long)));
   return CP_OK;
@@ -1171,8 +1171,8 @@ extern "C" int cp_debug_fw_prof(unsigned long long *out12)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_fw_prof),12); }
 extern "C" int cp_debug_unrel_prof(unsigned long long *out12)
 { HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_unrel_prof),12); }
-extern "C" int cp_debug_rel_prof(unsigned long long *out12)
-{ HIPCHK(hipDeviceSynchronize()); return prof_read(out12,HIP_SYMBOL(g_rel_prof),12); }
+extern "C" int cp_debug_rel_prof(unsigned long long *out13)
+{ HIPCHK(hipDeviceSynchronize()); return prof_read(out13,HIP_SYMBOL(g_rel_prof),13); }
 extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 { HIPCHK(hipDeviceSynchronize());
   CHK(prof_read(out36,HIP_SYMBOL(g_phase_max),12));

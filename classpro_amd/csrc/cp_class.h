@@ -201,20 +201,24 @@ CP_HD void cp_rel_only_r_cell(int s, int i, C *c, uint32_t standin = 0)
 // View gives the hot fields of the interval standing in for path index k: view(k) -> cp_riv.
 // `prev` = the four cells of the previous interval (C, or a padded record derived from it: Cell).
 // C = cp_cell: the anchors of cp_dh_ratio are looked up through `view`; C = cp_cell_anc: they come with the cell.
-template <class View, class Cell, class C>
-CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv &I, int F, const int *COV,
-                              int max_s, double max_logp, const Cell *prev, const View &view, C *out)
+// In two parts for the callers that fetch the predecessor's cell themselves: no predecessor (cp_rel_target_none), and the
+// cell from the predecessor's (cp_rel_target_from: of `pr` everything but dp and dhr is read).
+template <class C>
+CP_HD void cp_rel_target_none(double max_logp, C *out)
 { C c;
   c.dp = max_logp;
   c.dhr = -INFINITY;
-  if (max_s == CP_N_STATE)
-    { for (int k = 0; k < 4; k++) { c.pos[k] = 0; c.cnt[k] = 0; }
-      c.lastH = c.lastD = c.lastHbD = c.lastDbH = CP_NONE;
-      cp_anc_reset(c);
-      *out = c;
-      return;
-    }
-  const C pr = prev[max_s];
+  for (int k = 0; k < 4; k++) { c.pos[k] = 0; c.cnt[k] = 0; }
+  c.lastH = c.lastD = c.lastHbD = c.lastDbH = CP_NONE;
+  cp_anc_reset(c);
+  *out = c;
+}
+template <class View, class C>
+CP_HD void cp_rel_target_from(const cp_dev_params *P, int t, int i, const cp_riv &I, int F, const int *COV,
+                              double max_logp, const C &pr, const View &view, C *out)
+{ C c;
+  c.dp = max_logp;
+  c.dhr = -INFINITY;
   const int end_pos = cp_end_pos(I,F), end_cnt = cp_end_cnt(I,F);
   c.lastH = pr.lastH; c.lastD = pr.lastD; c.lastHbD = pr.lastHbD; c.lastDbH = pr.lastDbH;
   cp_anc_copy(c,pr);
@@ -264,6 +268,74 @@ CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv
     c.dp = -INFINITY;
   *out = c;
 }
+template <class View, class Cell, class C>
+CP_HD void cp_rel_target_cell(const cp_dev_params *P, int t, int i, const cp_riv &I, int F, const int *COV,
+                              int max_s, double max_logp, const Cell *prev, const View &view, C *out)
+{ if (max_s == CP_N_STATE)
+    { cp_rel_target_none(max_logp,out);
+      return;
+    }
+  const C pr = prev[max_s];
+  cp_rel_target_from(P,t,i,I,F,COV,max_logp,pr,view,out);
+}
+
+// The DP cell of the main class of k_classify_rel_grp (eight reads per wave) as it lies in LDS: 64 bytes in four 16-byte
+// pieces, each read and written as one 128-bit access, with what is used together in one piece:
+//   CP_PC_SCORE  dp, dhr                                          written every step; read back by the traceback only (the
+//                                                                 lane that owns a cell keeps both in registers)
+//   CP_PC_POS    pos[R], pos[H], pos[D], the four anchor indices  (one signed byte each: lastH, lastD, lastHbD, lastDbH)
+//   CP_PC_ANC    the anchors' four (end_pos, end_cnt) pairs
+//   CP_PC_CNT    cnt[R] | cnt[H] << 16, cnt[D], two words unused
+// The last three are what a new cell takes from its best predecessor's.  pos[E] and cnt[E] are never read and not kept; the
+// counts are 16-bit values (cnt_t) and the indices interval numbers below 128 or CP_NONE.
+struct alignas(16) cp_cell_piece { uint32_t w[4]; };
+enum { CP_PC_SCORE = 0, CP_PC_POS = 1, CP_PC_ANC = 2, CP_PC_CNT = 3, CP_PC_N = 4 };
+CP_HD void cp_cell_pack_score(double dp, double dhr, cp_cell_piece &p)
+{ const uint64_t a = cp_asuint64(dp), b = cp_asuint64(dhr);
+  p.w[0] = (uint32_t)a; p.w[1] = (uint32_t)(a >> 32); p.w[2] = (uint32_t)b; p.w[3] = (uint32_t)(b >> 32);
+}
+CP_HD double cp_cell_dp(const cp_cell_piece &p)  { return cp_asdouble((uint64_t)p.w[0] | ((uint64_t)p.w[1] << 32)); }
+CP_HD double cp_cell_dhr(const cp_cell_piece &p) { return cp_asdouble((uint64_t)p.w[2] | ((uint64_t)p.w[3] << 32)); }
+CP_HD void cp_cell_pack(const cp_cell_anc &c, cp_cell_piece (&p)[CP_PC_N])
+{ cp_cell_pack_score(c.dp,c.dhr,p[CP_PC_SCORE]);
+  for (int k = 0; k < 3; k++) p[CP_PC_POS].w[k] = (uint32_t)c.pos[k+1];
+  p[CP_PC_POS].w[3] = ((uint32_t)c.lastH & 0xff) | (((uint32_t)c.lastD & 0xff) << 8) | (((uint32_t)c.lastHbD & 0xff) << 16) | (((uint32_t)c.lastDbH & 0xff) << 24);
+  for (int k = 0; k < 4; k++) p[CP_PC_ANC].w[k] = c.anc[k];
+  p[CP_PC_CNT].w[0] = ((uint32_t)c.cnt[CP_REPEAT] & 0xffff) | (((uint32_t)c.cnt[CP_HAPLO] & 0xffff) << 16);
+  p[CP_PC_CNT].w[1] = (uint32_t)c.cnt[CP_DIPLO] & 0xffff;
+  p[CP_PC_CNT].w[2] = p[CP_PC_CNT].w[3] = 0;
+}
+// everything but dp and dhr (what cp_rel_target_from reads of a predecessor)
+CP_HD void cp_cell_unpack_path(const cp_cell_piece &pos, const cp_cell_piece &anc, const cp_cell_piece &cnt, cp_cell_anc &c)
+{ c.pos[0] = 0; c.cnt[0] = 0;
+  for (int k = 0; k < 3; k++) c.pos[k+1] = (int)pos.w[k];
+  c.lastH = (int8_t)(pos.w[3] & 0xff); c.lastD = (int8_t)((pos.w[3] >> 8) & 0xff);
+  c.lastHbD = (int8_t)((pos.w[3] >> 16) & 0xff); c.lastDbH = (int8_t)(pos.w[3] >> 24);
+  for (int k = 0; k < 4; k++) c.anc[k] = anc.w[k];
+  c.cnt[CP_REPEAT] = (int)(cnt.w[0] & 0xffff); c.cnt[CP_HAPLO] = (int)(cnt.w[0] >> 16); c.cnt[CP_DIPLO] = (int)(cnt.w[1] & 0xffff);
+}
+CP_HD void cp_cell_unpack(const cp_cell_piece (&p)[CP_PC_N], cp_cell_anc &c)
+{ c.dp = cp_cell_dp(p[CP_PC_SCORE]); c.dhr = cp_cell_dhr(p[CP_PC_SCORE]);
+  cp_cell_unpack_path(p[CP_PC_POS],p[CP_PC_ANC],p[CP_PC_CNT],c);
+}
+// Where piece p of the cell of (read g of the wave's eight, direction d, state s) lies in the wave's cells: a byte offset
+// into CP_REL_CELLS_BYTES.  The lanes of a wave are (g, d, s) = (lane / 8, (lane / 4) & 1, lane & 3), and a quad q = 2 g + d
+// reads the cells of its own four states only, any of them on any lane (the best predecessor).  A 128-bit LDS read is
+// served in four groups of sixteen lanes -- the quads {0,3,5,6}, {1,2,4,7} and the same plus 8 -- over sixteen 16-byte slots,
+// (offset / 16) mod 16; a 128-bit write in eight groups of eight consecutive lanes over eight slots, (offset / 16) mod 8.
+// Piece by piece (one instruction moves the same piece on every lane), the sixteen cells of a read group sit on sixteen
+// different slots whatever states its lanes pick, and the eight cells of a write group on eight: `col` differs among the
+// quads of a read group, and in its low bit between the two quads of a read (tests/test_rel_cell_layout.py enumerates it).
+#define CP_REL_CELLS_BYTES 4096                          // 8 reads x 2 directions x 4 states x 64 bytes, a single buffer
+CP_HD constexpr int cp_rel_cell_off(int g, int d, int s, int p)
+{ const int q = g*2+d, hi = (q >> 2) & 1;
+  const int col = (hi << 1) | ((q & 1) ^ hi);
+  const int row = ((q >> 1) & 1) | ((q >> 3) << 1);      // tells apart the four quads of one col
+  return p*(CP_REL_CELLS_BYTES/CP_PC_N)+(row*4+col)*64+s*16;
+}
+// the main class's LDS record of a wave: the cells, a back-pointer byte per (read, direction, interval) and the "absolutely
+// repeat" bits (kernels.hip: rel_grp_lds<MAXM,8>, which asserts this size)
+CP_HD constexpr int cp_rel_record_bytes(int maxm) { return CP_REL_CELLS_BYTES+8*2*maxm+8*2*((maxm+31)/32)*4; }
 
 struct cp_aos_view                   // path index -> hot fields, through the `eff` indirection
   { const cp_intvl *rintvl; const int *eff;

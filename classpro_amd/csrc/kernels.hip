@@ -2307,7 +2307,9 @@ k_classify_unrel(const cp_dev_params *__restrict__ P, int nreads, cp_intvl *__re
 //  both assignments live in LDS; HBM is touched for pe (once per step), the tables and the results.  Main class: DP cells,
 //  back-pointers and assignments live in LDS; the interval of a step is its record in global memory, fetched one step ahead
 //  (in the order of the pass), the cells carry what cp_dh_ratio needs of their anchors, and the transition matrix of a step
-//  stays in the registers of the quad: three waves per SIMD (profiles/rel_grp_occupancy_ab.txt).
+//  stays in the registers of the quad: three waves per SIMD (profiles/rel_grp_occupancy_ab.txt).  A lane keeps what the next
+//  step's transitions need of its own cell in registers; LDS holds the cells for the quad's predecessor fetch and the
+//  traceback, as 16-byte pieces laid out free of bank conflicts (profiles/rel_grp_lds_ab.txt).
 // ---------------------------------------------------------------------------------------------
 // LDS record of a wave (G reads), general form (the rare class, G = 1; the main class has its own below):
 //   * `eff` (index of the interval whose data stands in for path index k) and the "absolutely repeat" flag rpos share
@@ -2354,41 +2356,49 @@ struct rel_grp_lds
     __device__ __forceinline__ int8_t *asgn(int g, int d) { return reinterpret_cast<int8_t *>(parent[g][d]); }
   };
 
-// The record of the main class (eight reads per wave): cells, back-pointers and the "absolutely repeat" flags only, 9 216
+// The record of the main class (eight reads per wave): cells, back-pointers and the "absolutely repeat" flags only, 6 144
 // bytes with MAXM = 112.  The interval rows are not here: the step's interval is streamed from the read's records in
 // global memory one step ahead (rel_rec), and the only random access to the rows -- the anchors of cp_dh_ratio -- is gone
-// because the cells carry the (end_pos, end_cnt) pair of their four anchors (cp_cell_anc: 56 bytes instead of 40).  The
-// transition matrix is not here either: it stays in the registers of the quad that computed it (rel_grp_pass).
+// because the cells carry the (end_pos, end_cnt) pair of their four anchors (cp_cell_anc).  The transition matrix is not
+// here either: it stays in the registers of the quad that computed it (rel_grp_pass).
+// The cells are 64 bytes in four 16-byte pieces (cp_class.h: cp_cell_piece, cp_rel_cell_off), laid out piece by piece so
+// that every 128-bit read or write of a piece is free of bank conflicts whichever predecessors the lanes pick (as 56-byte
+// records in (read, direction, buffer, state) order 42 % of the kernel's LDS cycles were conflict cycles:
+// profiles/rel_grp_lds_ab.txt).  One buffer: a step's cells replace the step before's in place.  The lanes that read a
+// cell -- its quad's, for their best predecessor -- are lanes of the wave that writes it; a wave's LDS operations execute in
+// the order they are issued, and in a step every lane's fetch of its predecessor is issued before any lane's store (the
+// fetch is on both sides of the step's only branch, the store behind it).  The traceback reads the last step's cells.
+// (Of CP_PC_CNT the fetch uses 8 bytes and the compiler makes it a 64-bit read: two groups of 32 lanes, where the quads sit
+// two to a slot -- 4 LDS cycles, what the 128-bit form costs.  The table look-ups, at lane-dependent indices, conflict as
+// chance has it; they are what is left of SQ_LDS_BANK_CONFLICT.)
 template <int MAXM>
-struct rel_grp_lds<MAXM,8>
+struct alignas(16) rel_grp_lds<MAXM,8>
   { static_assert(MAXM <= 128,"one-byte anchor indices");
     static_assert(GRP_MAX_PLEN <= 0xffff,"cp_cell_anc keeps interval ends as 16-bit values");
-    typedef int8_t idx_t;
     typedef cp_cell_anc dp_cell;
-    struct alignas(8) cell_t
-      { double dp, dhr; int32_t pos_[3]; uint32_t anc_[4]; uint16_t cnt_[3]; idx_t last_[4];
-        __device__ __forceinline__ operator cp_cell_anc() const
-        { cp_cell_anc c; c.dp = dp; c.dhr = dhr;
-          c.pos[0] = 0; c.cnt[0] = 0;
-          for (int k = 0; k < 3; k++) { c.pos[k+1] = pos_[k]; c.cnt[k+1] = cnt_[k]; }
-          c.lastH = last_[0]; c.lastD = last_[1]; c.lastHbD = last_[2]; c.lastDbH = last_[3];
-          for (int k = 0; k < 4; k++) c.anc[k] = anc_[k];
-          return c;
-        }
-        __device__ __forceinline__ void set(const cp_cell_anc &c)
-        { dp = c.dp; dhr = c.dhr;
-          for (int k = 0; k < 3; k++) { pos_[k] = c.pos[k+1]; cnt_[k] = (uint16_t)c.cnt[k+1]; }
-          last_[0] = (idx_t)c.lastH; last_[1] = (idx_t)c.lastD; last_[2] = (idx_t)c.lastHbD; last_[3] = (idx_t)c.lastDbH;
-          for (int k = 0; k < 4; k++) anc_[k] = c.anc[k];
-        }
-      };
     static constexpr int RW = (MAXM+31)/32;
+    cp_cell_piece cells[CP_REL_CELLS_BYTES/16];   // piece p of (read g, direction d, state s): at cp_rel_cell_off(g,d,s,p)
     uint8_t  parent[8][2][MAXM];         // back-pointers of the 4 cells of an interval, 2 bits each; then the assignment
     uint32_t rpos[8][2][RW];             // "absolutely repeat" flags, a bit per interval
-    cell_t   cell[8][2][2][4];           // [read][direction][buffer][state]
     __device__ __forceinline__ int8_t *asgn(int g, int d) { return reinterpret_cast<int8_t *>(parent[g][d]); }
     __device__ __forceinline__ bool is_rpos(int g, int d, int k) const { return (rpos[g][d][k >> 5] >> (k & 31)) & 1; }
+    // the cells of a (read, direction): CP_PC_SCORE of state 0; piece p of state s is quad(g,d)[p*PIECE+s]
+    static constexpr int PIECE = CP_REL_CELLS_BYTES/CP_PC_N/16;
+    __device__ __forceinline__ cp_cell_piece *quad(int g, int d) { return cells+cp_rel_cell_off(g,d,0,0)/16; }
+    static __device__ __forceinline__ void store(cp_cell_piece *q, int s, const cp_cell_anc &c)
+    { cp_cell_piece p[CP_PC_N];
+      cp_cell_pack(c,p);
+      for (int k = 0; k < CP_PC_N; k++) q[k*PIECE+s] = p[k];
+    }
+    // what a new cell takes from the cell of state s: everything but dp and dhr
+    static __device__ __forceinline__ void load_path(const cp_cell_piece *q, int s, cp_cell_anc &c)
+    { const cp_cell_piece pos = q[CP_PC_POS*PIECE+s], anc = q[CP_PC_ANC*PIECE+s], cnt = q[CP_PC_CNT*PIECE+s];
+      cp_cell_unpack_path(pos,anc,cnt,c);
+    }
   };
+static_assert(sizeof(rel_grp_lds<REL_SMALL_MAXM,8>) == cp_rel_record_bytes(REL_SMALL_MAXM),"the record: cells, back-pointers, flags");
+static_assert(cp_rel_cell_off(0,0,1,0) == cp_rel_cell_off(0,0,0,0)+16 && cp_rel_cell_off(0,0,0,1) == cp_rel_cell_off(0,0,0,0)+16*rel_grp_lds<REL_SMALL_MAXM,8>::PIECE,
+              "rel_grp_lds<MAXM,8>::quad: states 16 bytes apart, pieces PIECE slots apart");
 
 // Reliable interval i of a read from its records in global memory: the 24-byte compact records of a whole-path call, or
 // the 48-byte record copies of the stage API
@@ -2402,6 +2412,27 @@ struct rel_rec
       return r;
     }
     __device__ __forceinline__ double pe(int i) const { return COMPACT ? rrec[i].pe : rintvl[i].pe; }
+    // The same in two halves for a record fetched ahead of its use: raw(i) only loads -- the compact record's words as they
+    // lie, its two 16-bit counts in one -- and unpack() is called where the record is used.  With the counts taken apart
+    // behind the load, the wait for the load stood there too, at the head of the step that was to overlap it.
+    struct raw_t { int32_t b, e; uint32_t cc; double pe; };
+    __device__ __forceinline__ raw_t raw(int i) const
+    { raw_t w;
+      if (COMPACT)
+        { const cp_rrec *q = rrec+i;
+          w.b = q->b; w.e = q->e; __builtin_memcpy(&w.cc,&q->ccb,4); w.pe = q->pe;
+          static_assert(offsetof(cp_rrec,cce) == offsetof(cp_rrec,ccb)+2,"ccb | cce << 16 is one word of the record");
+        }
+      else
+        { const cp_riv r = cp_riv_of(rintvl[i]);
+          w.b = r.b; w.e = r.e; w.cc = (uint32_t)r.ccb | ((uint32_t)r.cce << 16); w.pe = r.pe;
+        }
+      return w;
+    }
+    static __device__ __forceinline__ cp_riv unpack(const raw_t &w)
+    { cp_riv r; r.b = w.b; r.e = w.e; r.ccb = (int)(w.cc & 0xffff); r.cce = (int)(w.cc >> 16); r.pe = w.pe;
+      return r;
+    }
   };
 
 template <int MAXM, int G>
@@ -2434,7 +2465,9 @@ __device__ __forceinline__ bool rel_is_rpos(const rel_grp_lds<MAXM,G> &S, int g,
 // libm tables of a block in LDS (cp_libm.h): the DP step's chain is exp -> sum -> log, and from global memory each of the
 // two look-ups was a cache miss in the middle of it (k_classify_rel_grp 2.2 -> 3.2 ms per sub-batch when ocml's table-free
 // routines gave way to glibc's; with the tables on chip the look-up is an LDS read).
-struct rel_libm_lds { uint64_t exp_tab[256]; double log_tab[256]; };
+// 16-byte aligned: a look-up takes a pair, exp_tab[2j], exp_tab[2j+1] or log_tab[2i], log_tab[2i+1], and with the alignment
+// known the pair is one 128-bit read (4 LDS cycles a wave) where it was a two-address 64-bit one (16).
+struct alignas(16) rel_libm_lds { uint64_t exp_tab[256]; double log_tab[256]; };
 // A block of this kernel is WPB waves that share nothing but those tables: "sync" is the order of one wave's own LDS
 // operations (the hardware keeps it; the compiler is told by the fence), never a barrier across the block's waves.
 template <int WPB>
@@ -2446,17 +2479,22 @@ __device__ __forceinline__ void grp_sync()
 // -DCP_PROF_WALK (scripts/walk_profile.py): wave time of the main class of k_classify_rel_grp in 100 MHz ticks, lane 0 of every wave.
 //   [0] a step from its start to the return of its loads, [1] from there to the normalised tr values, [2] the state phase,
 //   [3] the syncs (with the stores in front of them), [4] the traceback, [5] cp_rel_post1, [6] cp_rel_post2, [7] the fw / bw
-//   compare, [8] a group of reads as a whole, [9] groups, [10] the init of a pass, [11] the final write.
-// Every stamp waits for the wave's outstanding memory operations first, so the phases do not overlap as they do unstamped.
+//   compare, [8] a group of reads as a whole, [9] groups, [10] the init of a pass, [11] the final write, [12] the part of
+//   [0] up to the point where the addresses of the step's table loads are known (the head: what the lane needs of its cell).
+// Every stamp waits for the wave's outstanding memory operations first, so the phases do not overlap as they do unstamped
+// ([12] waits for the LDS and scalar operations only: the record fetched one step ahead stays in flight, as in the product).
 #ifdef CP_PROF_WALK
-__device__ unsigned long long g_rel_prof[12];
+__device__ unsigned long long g_rel_prof[13];
 #define RP_DECL(n) unsigned long long rp_acc[n] = { 0 }, rp_t = wall_clock64()
 #define RP_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = wall_clock64(); \
                          rp_acc[k] += t_-rp_t; rp_t = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define RP_STAMP_LGKM(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xc07f); const unsigned long long t_ = wall_clock64(); \
+                              rp_acc[k] += t_-rp_t; rp_t = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define RP_FLUSH(on,lo,hi,off) do { if ((on) && lane_id() == 0) for (int k_ = lo; k_ <= hi; k_++) atomicAdd(&g_rel_prof[k_],rp_acc[k_-(off)]); } while (0)
 #else
 #define RP_DECL(n) ((void)0)
 #define RP_STAMP(k) ((void)0)
+#define RP_STAMP_LGKM(k) ((void)0)
 #define RP_FLUSH(on,lo,hi,off) ((void)0)
 #endif
 // lanes per direction of a read's 64/G lanes (rel_grp_pass)
@@ -2498,7 +2536,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   // target state s in the state phase: no lane of the wave idles in either phase, and everything that costs the same per
   // wave-instruction whatever the lanes do (the state phase, the syncs, psum, the loop) serves eight reads.
   static_assert(G <= 2 || G == 8,"lane layouts: 16 lanes per direction (G <= 2) or 4 (G = 8)");
-  RP_DECL(11);
+  RP_DECL(13);
   constexpr int L = WAVE/G, LD = REL_LD(G);
   const int lane = lane_id();
   const int g = lane/L, ql = lane%L;
@@ -2520,6 +2558,15 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
     { int x = __shfl_xor(maxM,o); maxM = x > maxM ? x : maxM; }
 
   int i = F ? 0 : M-1;
+  // (LD = 4) The lane is the only writer of the cell of its state, and what the transition phase of step k needs of that cell
+  // it has computed itself in the state phase of step k-1: dp, dhr, the H and D positions and the three counts stay in its
+  // registers (set by the init of a pass, untouched while the lane's step is off), so a step begins without an LDS read
+  // and the addresses of its table loads follow from these and the record fetched one step ahead.  The cell still goes to
+  // LDS every step: the other lanes of the quad fetch it as their best predecessor.
+  double own_dp = -INFINITY, own_dhr = -INFINITY;
+  int own_pos_h = 0, own_pos_d = 0, own_cnt_r = 0, own_cnt_h = 0, own_cnt_d = 0;
+  cp_cell_piece *quad = nullptr;                           // (LD = 4) the cells of the lane's (read, direction)
+  if constexpr (LD == 4) quad = S.quad(g,d);
   uint32_t standin = 0;                                    // (LD = 4) cp_anc_pair of the interval that stands in for i: i itself
                                                            // unless the steps since were "only R reachable" ones
   if constexpr (LD == 4)
@@ -2534,7 +2581,9 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
     const double psum = quad_sum1(e0);                     // :582-586, the four terms from the quad's registers
     if (in_grp)
       { c.dp = cp_log_t(e0/psum,lt);
-        S.cell[g][d][0][ld].set(c);
+        S.store(quad,ld,c);
+        own_dp = c.dp; own_dhr = c.dhr; own_pos_h = c.pos[CP_HAPLO]; own_pos_d = c.pos[CP_DIPLO];
+        own_cnt_r = c.cnt[CP_REPEAT]; own_cnt_h = c.cnt[CP_HAPLO]; own_cnt_d = c.cnt[CP_DIPLO];
         if (ld == 0)
           { S.parent[g][d][i] = 0xe4;                      // each state its own parent: 3,2,1,0
             for (int w = 0; w < rel_grp_lds<MAXM,G>::RW; w++) S.rpos[g][d][w] = 0;
@@ -2576,9 +2625,9 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   const double D_e = (li_e >= 0 && li_e <= CP_MAX_KMER_CNT) ? P->logint[li_e] : cp_log((double)li_e);
   int cur = 0;
   double pe_next = 0.;                                     // pe of the next interval (E lanes), one step ahead
-  cp_riv I_next; I_next.b = I_next.e = I_next.ccb = I_next.cce = 0; I_next.pe = 0.;    // (LD = 4) the whole record, one step ahead
+  typename Rec::raw_t I_next = typename Rec::raw_t();      // (LD = 4) the whole record, one step ahead, as loaded (rel_rec)
   if constexpr (LD == 4)
-    { if (in_grp && M > 1) I_next = rv(F ? 1 : M-2); }
+    { if (in_grp && M > 1) I_next = rec.raw(F ? 1 : M-2); }
   else
   if (in_grp && (LD == 4 || t_tab == CP_ERROR) && M > 1)
     pe_next = REL_PE(F ? 1 : M-2);
@@ -2598,14 +2647,17 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
         int e0 = 0, e1 = 0, rk = 0, rn = 0, r2 = 0;
         int hb = 0, hcb = 0, hce = 0, db = 0, dcb = 0, te = 0, tce = 0;
         if (on)
-          { I = I_next;                                    // fetched one step ahead
+          { I = Rec::unpack(I_next);                       // fetched one step ahead
+            // (the record's fields are taken out before the next one is fetched: while I_next's registers were still read
+            //  behind the load, the load went to other registers and the copy into I_next -- with a wait for the load in
+            //  front of it -- stood at the head of the step)
+            __asm__ volatile("" : "+v"(I.b), "+v"(I.e), "+v"(I.ccb), "+v"(I.cce), "+v"(I.pe));
             if (k+1 < M)
-              I_next = rv(F ? k+1 : M-2-k);                // (one address per direction: its four lanes load it)
-            const auto &pr = S.cell[g][d][cur][s];
-            dp_own = pr.dp;
+              I_next = rec.raw(F ? k+1 : M-2-k);           // (one address per direction: its four lanes load it)
+            dp_own = own_dp;                               // the cell of the lane's state, from its registers
             live = dp_own != -INFINITY;
             if (live)
-              { const int beg_pos = cp_beg_pos(I,F), beg_cnt = cp_beg_cnt(I,F), prc = pr.cnt_[CP_REPEAT-1];
+              { const int beg_pos = cp_beg_pos(I,F), beg_cnt = cp_beg_cnt(I,F), prc = own_cnt_r;
                 e0 = cp_check_cnt(I.ccb); e1 = cp_check_cnt(I.cce);
                 if (beg_cnt < prc)                         // logp_r, class_rel.c:172-211
                   { r_tab = true;
@@ -2614,11 +2666,11 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
                 const int max_cc = I.ccb > I.cce ? I.ccb : I.cce;
                 r_cap = max_cc >= COV[CP_REPEAT] || max_cc >= prc;
                 te = beg_pos; tce = beg_cnt;               // logp_h / logp_d, class_rel.c:213-270
-                const bool h_own = pr.dhr == -INFINITY;    // H from the last H anchor; otherwise from the last D anchor, scaled
-                hb  = cp_pred(h_own ? pr.pos_[CP_HAPLO-1] : pr.pos_[CP_DIPLO-1],F);
-                hcb = h_own ? pr.cnt_[CP_HAPLO-1] : pr.cnt_[CP_DIPLO-1];
-                hce = h_own ? beg_cnt : (int)(pr.dhr*beg_cnt);
-                db  = cp_pred(pr.pos_[CP_DIPLO-1],F); dcb = pr.cnt_[CP_DIPLO-1];
+                const bool h_own = own_dhr == -INFINITY;   // H from the last H anchor; otherwise from the last D anchor, scaled
+                hb  = cp_pred(h_own ? own_pos_h : own_pos_d,F);
+                hcb = h_own ? own_cnt_h : own_cnt_d;
+                hce = h_own ? beg_cnt : (int)(own_dhr*beg_cnt);
+                db  = cp_pred(own_pos_d,F); dcb = own_cnt_d;
               }
           }
         // the look-up of cp_exp_logp_trans (cp_math.h) for H and D, index by index: what lies outside the table, or a
@@ -2628,6 +2680,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
         const long long hcd = (long long)(hcb & 0xffff)*hd, dcd = (long long)(dcb & 0xffff)*dd;
         const bool h_in = live && eskel && hk <= skel_kmax && hcd <= skel_cdmax;
         const bool d_in = live && eskel && dk <= skel_kmax && dcd <= skel_cdmax;
+        RP_STAMP_LGKM(12);
         { const double A = P->logfact[e0], B = P->logfact[e1];                    // all seven loads of the lane together
           const double RA = P->logfact[rn], RB = P->logfact[rk], RC = P->logfact[r2];
           const double TH = etab[h_in ? hcd*(skel_kmax+1)+hk : 0], TD = etab[d_in ? dcd*(skel_kmax+1)+dk : 0];
@@ -2787,12 +2840,45 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
       if (st_lane)
         { dp_cell c;
           int pv = l16;
+          if constexpr (LD == 4)
+            { // One fetch serves both kinds of step: the new cell is made from the path fields of a cell of the step before,
+              // the lane's own on an "only R reachable" step (with its dp and dhr, which the lane holds), otherwise its best
+              // predecessor's (whose dp and dhr are not read).  One buffer: see rel_grp_lds<MAXM,8>.
+              double max_logp = col_logp;
+              int max_s = col_s;
+              if (!only_r && equal && (l16 == CP_HAPLO || l16 == CP_DIPLO))           // :382-386, then :391 again for this target
+                { const double mn = tr_hh < tr_dd ? tr_hh : tr_dd;
+                  max_logp = -INFINITY; max_s = CP_N_STATE;
+                  for (int x = 0; x < 4; x++)
+                    { const double w = (x == l16) ? mn : col[x];
+                      const double logp = dp[x]+w;
+                      if (max_logp < logp) { max_logp = logp; max_s = x; }
+                    }
+                }
+              const int from = only_r ? l16 : max_s;
+              dp_cell pr;
+              pr.dp = dp_own; pr.dhr = own_dhr;            // (the lane's own: an "only R reachable" step carries them over)
+              if (from != CP_N_STATE) S.load_path(quad,from,pr);
+              if (only_r)
+                { c = pr;
+                  cp_rel_only_r_cell(l16,i,&c,standin);
+                  if (l16 == 0) S.rpos[g][d][i >> 5] |= 1u << (i & 31);
+                }
+              else
+                { pv = (max_s == CP_N_STATE) ? l16 : max_s;
+                  standin = cp_anc_pair(I,F);
+                  if (max_s == CP_N_STATE) cp_rel_target_none(max_logp,&c);
+                  else cp_rel_target_from(P,l16,i,I,F,COV,max_logp,pr,view,&c);
+                }
+              S.store(quad,l16,c);
+              own_dp = c.dp; own_dhr = c.dhr; own_pos_h = c.pos[CP_HAPLO]; own_pos_d = c.pos[CP_DIPLO];
+              own_cnt_r = c.cnt[CP_REPEAT]; own_cnt_h = c.cnt[CP_HAPLO]; own_cnt_d = c.cnt[CP_DIPLO];
+            }
+          else
+          {
           if (only_r)
             { c = (dp_cell)S.cell[g][d][cur][l16];
-              cp_rel_only_r_cell(l16,i,&c,standin);
-              if constexpr (LD == 4)
-                { if (l16 == 0) S.rpos[g][d][i >> 5] |= 1u << (i & 31); }
-              else
+              cp_rel_only_r_cell(l16,i,&c);
               if (l16 == 0)
                 S.eff[g][d][i] = (typename rel_grp_lds<MAXM,G>::eff_t)(S.eff[g][d][i_pred] | rel_grp_lds<MAXM,G>::RPOS);
             }
@@ -2800,23 +2886,22 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
             { double max_logp = col_logp;
               int max_s = col_s;
               if (equal && (l16 == CP_HAPLO || l16 == CP_DIPLO))                      // :382-386, then :391 again for this target
-                { const double a = (LD == 4) ? tr_hh : tr[CP_HAPLO*4+CP_HAPLO], bb = (LD == 4) ? tr_dd : tr[CP_DIPLO*4+CP_DIPLO];
+                { const double a = tr[CP_HAPLO*4+CP_HAPLO], bb = tr[CP_DIPLO*4+CP_DIPLO];
                   const double mn = a < bb ? a : bb;
                   max_logp = -INFINITY; max_s = CP_N_STATE;
                   for (int x = 0; x < 4; x++)
-                    { const double w = (x == l16) ? mn : (LD == 4 ? col[x] : tr[x*4+l16]);
+                    { const double w = (x == l16) ? mn : tr[x*4+l16];
                       const double logp = dp[x]+w;
                       if (max_logp < logp) { max_logp = logp; max_s = x; }
                     }
                 }
               pv = (max_s == CP_N_STATE) ? l16 : max_s;
-              if constexpr (LD == 4) standin = cp_anc_pair(I,F);
-              else
               if (l16 == 0)
                 S.eff[g][d][i] = (typename rel_grp_lds<MAXM,G>::eff_t)i;
               cp_rel_target_cell(P,l16,i,I,F,COV,max_s,max_logp,&S.cell[g][d][cur][0],view,&c);
             }
           S.cell[g][d][cur^1][l16].set(c);
+          }
           const int l0 = lane-l16;                         // pack the four back-pointers into one byte
           const int pk = pv | (__shfl(pv,l0+1) << 2) | (__shfl(pv,l0+2) << 4) | (__shfl(pv,l0+3) << 6);
           if (l16 == 0)
@@ -2833,10 +2918,14 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
     { double max_logp = -INFINITY;
       int st = CP_ERROR;
       for (int x = 0; x < 4; x++)
-        if (max_logp < S.cell[g][d][fin][x].dp)
-          { max_logp = S.cell[g][d][fin][x].dp;
-            st = x;
-          }
+        { double dpx;
+          if constexpr (LD == 4) dpx = cp_cell_dp(quad[x]);
+          else dpx = S.cell[g][d][fin][x].dp;
+          if (max_logp < dpx)
+            { max_logp = dpx;
+              st = x;
+            }
+        }
       // (the assignment of interval k replaces its back-pointer byte, which has just been read)
       int8_t *as = S.asgn(g,d);
       if (F)
@@ -2856,6 +2945,7 @@ __device__ void rel_grp_pass(const cp_dev_params *P, rel_grp_lds<MAXM,G> &S, con
   RP_STAMP(4);
   RP_FLUSH(G == 8,0,4,0);
   RP_FLUSH(G == 8,10,10,0);
+  RP_FLUSH(G == 8,12,12,0);
 }
 
 // The coverage heuristics behind a pass (cp_rel_post1 / cp_rel_post2 of cp_class.h, class_rel.c:629-735) for the main
@@ -3016,6 +3106,8 @@ __device__ double rel_post2_quad(const cp_dev_params *P, const Rv &rv, int M, in
 // The block shapes are within the run-to-run spread of each other: two stays.  The third wave per SIMD is the gain; the
 // new record at two waves per SIMD is slower than the old one (the quad's DPP moves and the record's loads are in the chain
 // where LDS reads were).
+// Since the cells are 64-byte records in one buffer the wave's record is 6.1 KB and a two-wave block 16 KB (96 KB for a CU's
+// six blocks); occupancy is set by the registers (168: three waves per SIMD), not by LDS.
 #ifndef REL_SMALL_WPB
 #define REL_SMALL_WPB 2
 #endif
@@ -3027,6 +3119,9 @@ __device__ double rel_post2_quad(const cp_dev_params *P, const Rv &rv, int M, in
 //  nothing spilled.  With the 9.2-KB record LDS allows 3: 168 registers, one 8-byte value spilled with the compact records
 //  and three in the stage API's form -- loop-invariant pointers, stored before the loop over read groups and loaded in the
 //  preheaders of the tails' loops behind the DP of a group; nothing is spilled inside the DP loop.
+//  With the lane's own cell carried in registers across the step: still 168, ten dwords spilled with the compact records and
+//  fourteen in the stage API's form, stored before the loop over read groups and loaded in the init of a pass, the preheader
+//  of the step loop and the tails; none inside the step loop.
 //  The rare class (G = 1: 19.5 KB of LDS per wave) stays at 2.)
 #ifndef REL_WAVES_PER_EU
 #define REL_WAVES_PER_EU 3

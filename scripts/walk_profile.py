@@ -28,7 +28,7 @@ ph = (C.c_ulonglong * 36)()
 lv = (C.c_ulonglong * 8)()
 em = (C.c_ulonglong * 8)()
 ur = (C.c_ulonglong * 12)()
-rp = (C.c_ulonglong * 12)()
+rp = (C.c_ulonglong * 13)()
 fw = (C.c_ulonglong * 12)()
 clf.classify(b)
 lib().cp_debug_unrel_prof(ur)
@@ -72,10 +72,12 @@ print("classify_rel: %d of %d (read, direction) passes are repeated with adjuste
 if rp[9]:
     names = ["step: start to the return of its loads", "step: from there to the tr values", "step: state phase", "step: syncs",
              "traceback", "cp_rel_post1", "cp_rel_post2", "fw / bw compare"]
-    order = [10, 0, 1, 2, 3, 4, 5, 6, 7, 11]
+    order = [10, 0, 12, 1, 2, 3, 4, 5, 6, 7, 11]
     label = dict(zip(range(8), names)); label[10] = "init of a pass"; label[11] = "final write"
+    label[12] = "  of which the head, up to the load addresses"
     print("classify_rel (main class): %d groups of eight reads, %.1f ticks per group (stamped: every stamp drains the wave's memory operations)" % (rp[9], rp[8] / rp[9]))
     for k in order:
-        print("    %-42s %9.1f ticks per group  %5.1f %%" % (label[k], rp[k] / rp[9], 100.0 * rp[k] / rp[8]))
+        v = rp[0] + rp[12] if k == 0 else rp[k]            # (the stamp of [12] splits what [0] was)
+        print("    %-42s %9.1f ticks per group  %5.1f %%" % (label[k], v / rp[9], 100.0 * v / rp[8]))
 print("reads %d: memo on chip %d, flags on chip to the end %d, sent their flags to the arrays after the replay (more off-list SELF walls than slots) %d, flags on chip after the walk %d" %
       (b.nreads, lv[4], lv[5], lv[6], lv[7]))
