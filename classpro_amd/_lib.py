@@ -30,6 +30,7 @@ SYMBOLS = [
     "cp_kmer_sorted_combine", "cp_kmer_sorted_hist",
     "cp_kmer_sorted_read_hits", "cp_bin_call",
     "cp_kmer_sorted_read_runs", "cp_run_blocks",
+    "cp_kmer_sorted_read_fixes", "cp_apply_fixes",
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
     "cp_kmer_sorted_het_pairs",
     "cp_kmer_sorted_unitigs", "cp_unitigs_count", "cp_unitigs_bases", "cp_unitigs_arrays", "cp_unitigs_destroy", "cp_unitig_n50",
@@ -184,6 +185,8 @@ def lib():
     L.cp_kmer_sorted_read_runs.argtypes = [vp, vp, i32, vp, C.c_uint, C.c_uint, vp, vp, i32, i64, vp, i64, vp, C.POINTER(i64), vp]
     L.cp_run_blocks.argtypes = [vp, i64, i64, vp, C.POINTER(i64)]
     L.cp_run_blocks.restype = i64
+    L.cp_kmer_sorted_read_fixes.argtypes = [vp, i32, vp, i32, vp, vp, i32, i64, vp, i64, vp, C.POINTER(i64), vp, vp]
+    L.cp_apply_fixes.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i64, vp, C.POINTER(i64), vp]
     L.cp_kmer_sorted_compare_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.cp_kmer_qv.argtypes = [i32, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.cp_kmer_sorted_het_pairs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]

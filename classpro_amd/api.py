@@ -854,6 +854,79 @@ class SortedKmers:
         tail = buf.view(torch.int32)[:, 6:]
         return run_off, {"first": buf[:, 0], "last": buf[:, 1], "n": buf[:, 2], "read": tail[:, 0], "state": tail[:, 1]}
 
+    FIX_NONE, FIX_ONE, FIX_MANY, FIX_OPEN, FIX_NOCAND, FIX_CLASH = range(6)              # the status of a gap
+    FIX_TALLY = ("none", "one", "many", "open", "nocand", "clash")
+
+    @staticmethod
+    def _flat_batch(batch):
+        if isinstance(batch, Batch):
+            return batch.seq, batch.seq_off, batch.nreads, batch.total_bases
+        seq, seq_off = batch
+        n = seq_off.numel() - 1
+        return seq, seq_off, n, int(seq_off[-1].item()) if n > 0 else 0
+
+    def read_fixes(self, batch, max_indel=1, canonical=True, count_range=None, capacity=None):
+        """cp_kmer_sorted_read_fixes ("Fixing reads from a k-mer table" in include/classpro_amd.h): the gaps of a `Batch` or
+        of a tuple of device tensors (seq uint8, seq_off int64 [n+1]) -- the runs of k-mer positions whose key this
+        snapshot does not hold, or holds with a count outside `count_range` = (lo, hi), either end None for open -- each
+        with the one edit of at most `max_indel` inserted or removed bases that closes it, where there is exactly one.
+        Returns (fix_off, fixes, tally): fix_off an int64 device tensor [n+1], the gaps of read r being records
+        fix_off[r] .. fix_off[r+1]; fixes a dict of device tensors "first", "last" (int64), "read" (int32), "status", "del",
+        "nins", "nacc" (uint8), "ins" (uint8 [., 8]) and "records" (int64 [., 4], the records as `apply_fixes` takes them;
+        the others are views of it); tally a dict of FIX_TALLY, the gaps by status.  One call with a guessed capacity
+        (`capacity` records when given, else one per 16 bases), one more at the exact size when that was too small."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        seq, seq_off, n, total = self._flat_batch(batch)
+        rng = None
+        if count_range is not None:
+            lo, hi = count_range
+            rng = (C.c_int64 * 2)(1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi))
+        fix_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=self.device)
+        tally = torch.zeros(6, dtype=torch.int64, device=self.device)
+        capacity = max(1024, total // 16) if capacity is None else max(int(capacity), 0)
+        count = C.c_int64()
+        with torch.cuda.device(self.device):
+            for _ in range(2):
+                buf = torch.empty((capacity, 4), dtype=torch.int64, device=self.device)
+                rc = self.L.cp_kmer_sorted_read_fixes(self.s, 1 if canonical else 0, rng, int(max_indel), seq.data_ptr(),
+                                                      seq_off.data_ptr(), n, total, buf.data_ptr() if capacity else None,
+                                                      capacity, fix_off.data_ptr(), C.byref(count), tally.data_ptr(),
+                                                      _stream_of(self.device))
+                if rc != CP_EOVERFLOW:                     # count is exact: once more at that size
+                    break
+                capacity = count.value
+            check(rc)
+        buf = buf[:count.value]
+        b8 = buf.view(torch.uint8)
+        fixes = {"first": buf[:, 0], "last": buf[:, 1], "read": buf.view(torch.int32)[:, 4], "status": b8[:, 20], "del": b8[:, 21],
+                 "nins": b8[:, 22], "nacc": b8[:, 23], "ins": b8[:, 24:32], "records": buf}
+        return fix_off, fixes, dict(zip(self.FIX_TALLY, tally.cpu().tolist()))
+
+    def apply_fixes(self, batch, fix_off, fixes):
+        """cp_apply_fixes: the batch with the fixes of status FIX_ONE applied and nothing else.  `fix_off` and `fixes` are
+        what `read_fixes` of this batch returned (`fixes` the dict, or its "records" tensor).  Returns (seq, seq_off) as
+        device tensors, uint8 and int64 [n+1]: a batch that every call here takes."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        seq, seq_off, n, total = self._flat_batch(batch)
+        rec = fixes["records"] if isinstance(fixes, dict) else fixes
+        if rec.dtype != torch.int64 or rec.dim() != 2 or rec.shape[1] != 4 or not rec.is_contiguous() or rec.device != self.device:
+            raise ValueError("fixes must be the contiguous int64 records [., 4] of read_fixes on the snapshot's device")
+        if fix_off.dtype != torch.int64 or fix_off.numel() != max(n, 0) + 1 or not fix_off.is_contiguous() or fix_off.device != self.device:
+            raise ValueError("fix_off must be a contiguous int64 tensor [n+1] on the snapshot's device")
+        if n > 0 and int(fix_off[-1].item()) > rec.shape[0]:
+            raise ValueError("fix_off counts more records than fixes holds")
+        capacity = total + 4 * rec.shape[0]
+        out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        out_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=self.device)
+        count = C.c_int64()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_apply_fixes(seq.data_ptr(), seq_off.data_ptr(), n, total, self.K, rec.data_ptr() if rec.shape[0] else None,
+                                        fix_off.data_ptr(), out.data_ptr(), capacity, out_off.data_ptr(), C.byref(count),
+                                        _stream_of(self.device)))
+        return out[:count.value], out_off
+
     PATH_TALLY = ("positions", "present", "absent", "other", "segments", "joined", "walks")
 
     def read_paths(self, U, batch, coverage=None, support=None, capacity=None):

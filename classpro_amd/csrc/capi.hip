@@ -1199,6 +1199,9 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // runs of k-mer states along reads and the blocks of a read's runs (tabtrack): kmer_runs.hip
 #include "kmer_runs.hip"
 
+// gaps of absent k-mers turned into edits of the reads, and the edits applied (tabfix): kmer_fixes.hip
+#include "kmer_fixes.hip"
+
 // set algebra on sorted snapshots and the histogram of one (tabop): kmer_setops.hip
 #include "kmer_setops.hip"
 

@@ -708,6 +708,108 @@ int     cp_kmer_sorted_read_runs(const cp_kmer_sorted *a, const cp_kmer_sorted *
 int64_t cp_run_blocks(const cp_kmer_run *runs, int64_t nruns, int64_t min_n, cp_kmer_run *blocks, int64_t *dropped);
 
 /* ------------------------------------------------------------------------------------------
+ * Fixing reads from a k-mer table (tabfix): error correction against solid k-mers.  The runs of absent k-mers of "Runs of
+ * k-mer states along reads" are the errors of a read, about K positions per substitution; here such a run is turned into
+ * the ONE edit of the read that makes every k-mer around it present, where there is exactly one, and the edits are applied
+ * on the device.  The rule is this library's own.  Everything is in integers and is a function of the read and the
+ * snapshot alone.
+ *
+ *   Positions  a sequence s of n bases has P = n-K+1 k-mer positions, position p covering the bases [p, p+K).  The state of
+ *              a position is the one cp_kmer_sorted_read_runs gives with one table (b == NULL): present (CP_RUN_A),
+ *              CP_RUN_NONE or CP_RUN_OTHER, with the same `canonical` switch and the same count range a_min a_max (HOST
+ *              `range`, NULL: [1, INT64_MAX]).
+ *   Gap        a maximal run [i, j] of NONE positions.  It is CLOSED when i >= 1, j <= P-2 and both neighbouring positions
+ *              are present, and OPEN otherwise: at an end of the sequence, or beside an OTHER position.  For a closed gap
+ *              L = j-i+1, e = i+K-1, f = j, g = f-e+1 = L-K+1 and t = -g.  Base e is the first base a left-to-right
+ *              reading cannot explain, base f the last base a right-to-left reading cannot explain: one substitution gives
+ *              L = K and e == f, an insertion of g bases gives L = K+g-1, a lost base L = K-1, and a change inside a
+ *              repeat a shorter gap still (t > 0), because the k-mers that lie inside the repeat do not see it.
+ *   Candidates with D = max_indel in [0, 4], every candidate (del, ins) replaces s[e, e+del) by the string ins.  In this order:
+ *                g >= 1   (d, "") for d = g .. D: the read had an insertion.  When g == 1 also (1, c) for the three bases
+ *                         c != s[e], in the order A C G T: a substitution.
+ *                g <= 0   (d, "") for d = 1 .. D.  When D >= 1, (0, c) for the four bases c in the order A C G T: the read
+ *                         lost a base.  Then (0, s[e-d, e)) for d = 2 .. min(D, t): the read lost a copy of a tandem unit.
+ *              A candidate with e+del > n does not exist.  There are at most 2D+3 candidates for one gap, and all of them
+ *              give different strings.
+ *   Accepted   let c be the sequence after the edit.  The checked positions q run from e-K+1 = i to e+|ins|-1, for a pure
+ *              removal from i to e-1, both ends clipped to [0, len(c)-K]: K-1+|ins| k-mers at most.  The candidate is
+ *              accepted when that range is not empty and every k-mer in it is present under the same presence rule (a
+ *              k-mer with a byte other than A C G T is not present).
+ *   Status     CP_FIX_NONE candidates were tried and none was accepted; CP_FIX_ONE exactly one was accepted, it is the fix;
+ *              CP_FIX_MANY more than one was accepted, the gap is left alone; CP_FIX_OPEN the gap is open and was not
+ *              tried; CP_FIX_NOCAND a closed gap with no candidate (g > D and g != 1, or D == 0 and g <= 0);
+ *              CP_FIX_CLASH, below.
+ *   Clash      a ONE fix becomes CLASH in two cases, both taken on the statuses before any clash is decided: e < e'+del'
+ *              for the gap just before it in the same sequence when that gap is ONE, and e+del > e'' for the gap just
+ *              after it when that gap is ONE.  Both partners go.  Gaps that are not neighbours cannot overlap: the next
+ *              gap begins at i'' >= j+2, so e'' >= j+K+1; its j'' >= j+2, so the next but one has e''' >= j+K+3; and
+ *              e+del <= j+K-1+D <= j+K+3 with D <= 4.
+ *   So         the applied edits of a sequence are disjoint and ascending, and after ONE edit every k-mer outside its checked
+ *              window is the same string as before.  An edit takes the positions [i, max(e+del, e)-1] of the sequence away and
+ *              puts its window, all present, in their place; the window reads the bases [i, e+del+K-2].  Where every applied
+ *              fix stands alone -- the next gap begins behind e+del-1 and the next applied fix has e'' >= e+del+K-1 -- the
+ *              NONE positions of the corrected sequence number exactly the NONE positions before less the sum of L over the
+ *              applied gaps.  Where fixes stand closer (two errors within about K bases) the windows were checked without
+ *              the neighbour's edit, and a removal of more than g+1 bases takes positions of the next gap with it: the
+ *              identity is no theorem there.  The result does not depend on batching, read order, grid or chunk sizes.
+ *   Scope      one error per gap.  Two errors closer than K give one gap with g >= 2 and stay; a deletion of two or more
+ *              bases outside a repeat stays (4^d candidates).  Where repeats reach K, gaps stay ambiguous.
+ *
+ * cp_kmer_sorted_read_fixes: one record per gap of the batch (the flat layout above), a cp_kmer_fix of 32 bytes.
+ *   Record     `first` = i and `last` = j as in a cp_kmer_run, `read` the read's index in the batch, `status`, `nacc` the
+ *              number of accepted candidates; `del`, `nins` and `ins` (upper-case bases, zero padded) are the edit when the
+ *              status is ONE or CLASH and zero otherwise.  The records correspond one to one, offsets included, with the
+ *              NONE runs of cp_kmer_sorted_read_runs(s, NULL, ..., skip 0, emit 1 << CP_RUN_NONE).
+ *   Output     d_fix_off[r] .. d_fix_off[r+1] are the records of read r, ascending in `first`; all nreads+1 offsets are
+ *              overwritten and *total (HOST) = d_fix_off[nreads].  Reads shorter than K, empty reads and nreads == 0 give
+ *              no records and are no error.  d_tally, a DEVICE int64 [CP_FIX_WIDTH] or NULL, is ADDED TO: one cell per
+ *              status.
+ *   Capacity   d_fixes holds `capacity` records.  With *total > capacity the call returns CP_EOVERFLOW; d_fix_off and
+ *              *total are exact all the same.  A fix needs the records of its neighbours, so a call that overflows writes
+ *              no record at all and adds nothing to d_tally.  d_fixes == NULL with capacity == 0 is the counting call.
+ *   Passes     the state bytes, block summaries, scan and write pass of the runs; then one wave per gap tries the
+ *              candidates, lane l looking up the k-mer at checked position i+l; then two passes of one lane
+ *              per record apply the clash rule, the first deciding from what the second alone stores.  Lookups are those of "Sorted k-mers as input": clamped ranges, at most 64 probes.
+ *   Errors     all before any launch: CP_EINVAL for a NULL s or total, an unready snapshot, a snapshot of K < 5 (a candidate
+ *              reads the five bases s[e-4 .. e]), a range with min < 1 or max < min, max_indel outside [0, 4], a negative nreads, total_bases or capacity, a null device pointer
+ *              where there is work (as in cp_kmer_sorted_read_runs).  Scratch as there, but allocated and freed
+ *              outside the stream's order; CP_ENOMEM with the byte count in the message and nothing queued before it.
+ *              A batch with more than 2^24 gaps is CP_EINVAL once their number is known, with *total set and no record
+ *              written: that is what cp_apply_fixes takes in one call, so what one call gives the other takes.
+ *              The snapshot and the batch are only read.  Synchronises `stream`.
+ *
+ * cp_apply_fixes: the batch with the records of status CP_FIX_ONE applied and nothing else, as a batch of the same layout.
+ *   K          the k of the snapshot that made the records: e = first+K-1.
+ *   Output     d_out_off [nreads+1] is overwritten with the new offsets and *out_total (HOST) = d_out_off[nreads];
+ *              d_out[d_out_off[r] .. d_out_off[r+1]) is read r with its edits.  With *out_total > out_capacity the call
+ *              returns CP_EOVERFLOW with exact offsets and total and d_out untouched.  total_bases + 4 * records always
+ *              suffices.
+ *   Clamped    everything read from d_fixes is checked: a record is an edit only when its status is ONE, del and nins are at
+ *              most 4, its `read` is the read whose records hold it, 0 <= first, e < n and e+del <= n; anything else is
+ *              treated as "no edit".  Offsets read from d_fix_off are clamped to [0, d_fix_off[nreads]], every store is
+ *              checked against the read's new extent and out_capacity.  Records that are not ascending in `first` give
+ *              unspecified bases, but no content of the records makes a lane read or write outside the arrays.
+ *   Passes     the signed length change per record, its scan over all records, the offsets, then a copy in which a lane owns
+ *              64 consecutive input bases: it finds their read, the last edit at or before them by a binary search in the
+ *              read's records, and walks.  No lane is serial over a sequence: a contig of many blocks is copied by many.
+ *   Errors     CP_EINVAL before any launch for K outside [5, 63], negative sizes, a NULL out_total, null device pointers
+ *              where there is work; the number of records (d_fix_off[nreads]) is read first, and at most 2^24 records are
+ *              taken per call.  Scratch of 8 bytes per record, CP_ENOMEM with the byte count in the message.  The batch and
+ *              the records are only read.  Synchronises `stream`.
+ */
+enum { CP_FIX_NONE = 0, CP_FIX_ONE = 1, CP_FIX_MANY = 2, CP_FIX_OPEN = 3, CP_FIX_NOCAND = 4, CP_FIX_CLASH = 5, CP_FIX_WIDTH = 6 };
+typedef struct cp_kmer_fix { int64_t first, last; int32_t read; uint8_t status, del, nins, nacc; char ins[8]; } cp_kmer_fix;
+int     cp_kmer_sorted_read_fixes(const cp_kmer_sorted *s, int canonical, const int64_t *range /* host [2], or NULL */,
+                                  int max_indel, const char *d_seq, const int64_t *d_seq_off, int nreads, int64_t total_bases,
+                                  cp_kmer_fix *d_fixes /* device [capacity], or NULL */, int64_t capacity,
+                                  int64_t *d_fix_off /* device [nreads+1], overwritten */, int64_t *total /* host */,
+                                  int64_t *d_tally /* device [CP_FIX_WIDTH], added to, or NULL */, void *stream);
+int     cp_apply_fixes(const char *d_seq, const int64_t *d_seq_off, int nreads, int64_t total_bases, int K,
+                       const cp_kmer_fix *d_fixes, const int64_t *d_fix_off /* device [nreads+1] */,
+                       char *d_out /* device [out_capacity] */, int64_t out_capacity,
+                       int64_t *d_out_off /* device [nreads+1], overwritten */, int64_t *out_total /* host */, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Count comparison of sorted k-mers (tabcmp): the joint distribution of the counts that two snapshots give one key -- the
  * matrix of KAT's comp and the spectra-cn of Merqury (the read-count spectrum split by the copy number in an assembly) --
  * by the streaming merge of "Set algebra on sorted k-mers", and the k-mer QV that follows from it.  Everything on the
