@@ -33,6 +33,8 @@ SYMBOLS = [
     "cp_kmer_sorted_read_fixes", "cp_apply_fixes",
     "cp_kmer_sorted_compare_hist", "cp_kmer_qv",
     "cp_kmer_sorted_het_pairs",
+    "cp_kmer_counts_add_keys", "cp_kmer_sorted_het_sites", "cp_kmer_sorted_read_links", "cp_phase_forest",
+    "cp_kmer_sorted_phase_split",
     "cp_kmer_sorted_unitigs", "cp_unitigs_count", "cp_unitigs_bases", "cp_unitigs_arrays", "cp_unitigs_destroy", "cp_unitig_n50",
     "cp_kmer_sorted_unitig_links", "cp_unitig_graph_links", "cp_unitig_graph_arrays", "cp_unitig_graph_destroy",
     "cp_kmer_sorted_read_paths", "cp_count_nonzero",
@@ -190,6 +192,11 @@ def lib():
     L.cp_kmer_sorted_compare_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.cp_kmer_qv.argtypes = [i32, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.cp_kmer_sorted_het_pairs.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(vp)]
+    L.cp_kmer_counts_add_keys.argtypes = [vp, vp, vp, i64, vp]
+    L.cp_kmer_sorted_het_sites.argtypes = [vp, vp, vp, C.POINTER(i64), vp, vp]
+    L.cp_kmer_sorted_read_links.argtypes = [vp, vp, i32, vp, vp, i32, i64, vp, i64, C.POINTER(i64), vp, vp]
+    L.cp_phase_forest.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+    L.cp_kmer_sorted_phase_split.argtypes = [vp, vp, vp, vp, i64, i32, vp, C.POINTER(vp)]
     L.cp_kmer_sorted_unitigs.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
     L.cp_unitigs_count.argtypes = [vp]
     L.cp_unitigs_count.restype = i64

@@ -496,6 +496,21 @@ class KmerCounts:
         check(self.L.cp_kmer_counts_add(self.t, b.seq.data_ptr(), b.seq_off.data_ptr(), b.nreads, b.total_bases,
                                         self._stream()))
 
+    def add_keys(self, lo, hi=None):
+        """cp_kmer_counts_add_keys: adds the explicit keys hi << 63 | lo, +1 each, given as flat int64 (or uint64) tensors
+        of equal length; hi=None: every hi is 0.  Raises ClassProError (CP_EINVAL) on a filtered table, and -- after the
+        pass, with the other keys added -- for a key that does not fit 2K bits or whose lo is negative."""
+        lo = lo.to(self.device).contiguous()
+        if lo.dim() != 1 or lo.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("lo must be a flat int64 tensor")
+        if hi is not None:
+            hi = hi.to(self.device).contiguous()
+            if hi.shape != lo.shape or hi.dtype not in (torch.int64, torch.uint64):
+                raise ValueError("hi must be a flat int64 tensor as long as lo")
+        n = lo.numel()
+        check(self.L.cp_kmer_counts_add_keys(self.t, hi.data_ptr() if hi is not None and n else None, lo.data_ptr() if n else None,
+                                             n, self._stream()))
+
     def mark_tensors(self, seq, seq_off):
         """The mark pass of a filtered table over a batch given as device tensors (as `add_tensors`)."""
         n = seq_off.numel() - 1
@@ -1058,6 +1073,105 @@ class SortedKmers:
             res.append(out)
         return tuple(res)
 
+    def _derived(self, handle):
+        out = SortedKmers.__new__(SortedKmers)
+        out.L, out.device, out.K = self.L, self.device, self.K
+        out._adopt(handle)
+        return out
+
+    def het_sites(self, mates=False):
+        """cp_kmer_sorted_het_sites ("Phasing heterozygous sites from reads" in include/classpro_amd.h): the entries of this
+        snapshot of heterozygous k-mers paired into sites.  Returns (mark, nsites, tally): mark an int32 device tensor
+        [len], site << 1 | allele for a mated entry and -1 otherwise; tally a dict with "mated" and "unmated".  mates=True
+        appends mate, an int64 device tensor [len]."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        mark = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        mate = torch.empty(self.n, dtype=torch.int64, device=self.device) if mates else None
+        ns, tally = C.c_int64(), (C.c_int64 * 2)()
+        with torch.cuda.device(self.device):
+            check(self.L.cp_kmer_sorted_het_sites(self.s, mate.data_ptr() if mates and self.n else None,
+                                                  mark.data_ptr() if self.n else None, C.byref(ns), tally, _stream_of(self.device)))
+        res = (mark, ns.value, {"mated": tally[0], "unmated": tally[1]})
+        return res + (mate,) if mates else res
+
+    LINK_TALLY = ("markers", "links", "self")
+
+    def read_links(self, batch, mark, capacity=None, canonical=True, tally=None):
+        """cp_kmer_sorted_read_links: the links of a `Batch` or of a tuple of device tensors (seq uint8, seq_off int64
+        [n+1]) under `mark` (of `het_sites`), in batch order.  Returns (links, tally): links an int64 device tensor of the
+        keys min(s,s') << 32 | max(s,s') << 1 | (a ^ a'); tally an int64 device tensor [3], order LINK_TALLY, which is
+        added to -- pass a previous one to go on.  capacity=None: a counting call, then the call at the exact size; with a
+        capacity that is too small ClassProError (CP_EOVERFLOW) is raised and the tally is untouched."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        seq, seq_off, n, total = self._flat_batch(batch)
+        if mark.dtype != torch.int32 or mark.numel() != self.n or not mark.is_contiguous() or mark.device != self.device:
+            raise ValueError("mark must be the contiguous int32 tensor [len] of het_sites on the snapshot's device")
+        if tally is None:
+            tally = torch.zeros(3, dtype=torch.int64, device=self.device)
+        count = C.c_int64()
+        args = (self.s, mark.data_ptr() if self.n else None, 1 if canonical else 0, seq.data_ptr(), seq_off.data_ptr(), n, total)
+        with torch.cuda.device(self.device):
+            if capacity is None:
+                rc = self.L.cp_kmer_sorted_read_links(*args, None, 0, C.byref(count), None, _stream_of(self.device))
+                if rc != CP_EOVERFLOW:
+                    check(rc)
+                capacity = count.value
+            capacity = max(int(capacity), 0)
+            buf = torch.empty(max(capacity, 1), dtype=torch.int64, device=self.device)
+            check(self.L.cp_kmer_sorted_read_links(*args, buf.data_ptr() if capacity else None, capacity, C.byref(count),
+                                                   tally.data_ptr(), _stream_of(self.device)))
+        return buf[:count.value], tally
+
+    def phase_split(self, mark, block, side):
+        """cp_kmer_sorted_phase_split: the two marker tables (A, B) of this snapshot under `mark` (of `het_sites`) and
+        `block`, `side` (of `phase_forest`): new `SortedKmers` that keep no reference to this one."""
+        if self.s is None:
+            raise ValueError("SortedKmers is closed")
+        if mark.dtype != torch.int32 or mark.numel() != self.n or block.dtype != torch.int64 or side.dtype != torch.uint8 \
+                or block.numel() != side.numel():
+            raise ValueError("mark int32 [len], block int64 [nsites] and side uint8 [nsites] are wanted")
+        mark, block, side = mark.contiguous(), block.contiguous(), side.contiguous()
+        ns, out = block.numel(), []
+        with torch.cuda.device(self.device):
+            for which in (0, 1):
+                h = C.c_void_p()
+                check(self.L.cp_kmer_sorted_phase_split(self.s, mark.data_ptr() if self.n else None, block.data_ptr() if ns else None,
+                                                        side.data_ptr() if ns else None, ns, which, _stream_of(self.device),
+                                                        C.byref(h)))
+                out.append(self._derived(h))
+        return tuple(out)
+
+    def phase(self, batches, count_range=None, min_support=2, canonical=True):
+        """The driver of "Phasing heterozygous sites from reads": P = the unique heterozygous pairs of this snapshot under
+        `count_range` (`het_pairs`), its sites, the links of every batch of `batches` (an iterable of what `read_links`
+        takes) accumulated in a `KmerCounts` of K = 32, the forest and the split.  Returns a dict: "P", "A", "B"
+        (`SortedKmers`), "mark", "block", "side" (device tensors), "nsites", and the tallies "sites" (mated, unmated),
+        "links" (LINK_TALLY) and "forest" (PHASE_TALLY).  The phase of one block relative to another is arbitrary."""
+        P = self.het_pairs(xmax=1, ymax=1, unique=True, count_range=count_range, table=True)[2]
+        acc = edges = None
+        try:
+            mark, ns, sites = P.het_sites()
+            acc = KmerCounts(32, device=self.device)
+            tally = torch.zeros(3, dtype=torch.int64, device=self.device)
+            for b in batches:
+                links, tally = P.read_links(b, mark, canonical=canonical, tally=tally)
+                acc.add_keys(links)
+            edges = acc.sorted(1)
+            block, side, forest = phase_forest(edges, ns, min_support)
+            A, B = P.phase_split(mark, block, side)
+        except Exception:
+            P.close()
+            raise
+        finally:
+            if edges is not None:
+                edges.close()
+            if acc is not None:
+                acc.close()
+        return {"P": P, "A": A, "B": B, "mark": mark, "block": block, "side": side, "nsites": ns, "sites": sites,
+                "links": dict(zip(self.LINK_TALLY, tally.cpu().tolist())), "forest": forest}
+
     def unitigs(self, count_range=None, adjacency=False, where=False, sequences=True, links=False, components=False):
         """cp_kmer_sorted_unitigs ("Unitigs of sorted k-mers" in include/classpro_amd.h): the unitigs of the de Bruijn
         graph of the keys of this snapshot.  Returns a `Unitigs`: len() unitigs, `.seq` (uint8, upper-case A C G T), `.off`
@@ -1332,6 +1446,26 @@ def run_blocks(runs, min_n=1):
     nb = check(lib().cp_run_blocks(arr.ctypes.data if len(arr) else out.ctypes.data, len(arr), int(min_n), out.ctypes.data,
                                    C.byref(dropped)))
     return [tuple(int(x) for x in b) for b in out[:nb].tolist()], dropped.value
+
+
+PHASE_TALLY = ("edges", "kept", "tied", "weak", "forest", "conflicts", "blocks", "single", "largest", "rounds", "bad")
+
+
+def phase_forest(edges, nsites, min_support=2):
+    """cp_phase_forest ("Phasing heterozygous sites from reads" in include/classpro_amd.h): `edges` is the `SortedKmers` of a
+    `KmerCounts` of K = 32 that holds the link keys (`KmerCounts.add_keys`, `sorted(1)`).  Returns (block, side, tally):
+    block an int64 and side a uint8 device tensor [nsites], tally a dict of PHASE_TALLY."""
+    if edges.s is None:
+        raise ValueError("SortedKmers is closed")
+    nsites = int(nsites)
+    room = nsites if 0 < nsites < 1 << 31 else 0           # anything else is the library's to refuse
+    block = torch.empty(room, dtype=torch.int64, device=edges.device)
+    side = torch.empty(room, dtype=torch.uint8, device=edges.device)
+    tally = (C.c_int64 * len(PHASE_TALLY))()
+    with torch.cuda.device(edges.device):
+        check(edges.L.cp_phase_forest(edges.s, nsites, int(min_support), block.data_ptr() if room else None,
+                                      side.data_ptr() if room else None, tally, _stream_of(edges.device)))
+    return block, side, dict(zip(PHASE_TALLY, tally))
 
 
 def kmer_qv(K, a_only, a_total):

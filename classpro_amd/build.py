@@ -27,6 +27,7 @@ TGRF = os.path.join(_HERE, "tabgraph")         # links and components of that gr
 TPTH = os.path.join(_HERE, "tabpath")          # reads threaded through that graph, as GAF (csrc/host/tabpath.cpp; uses the GPU)
 TCLN = os.path.join(_HERE, "tabclean")         # tips, bubbles and islands of that graph removed (csrc/host/tabclean.cpp; uses the GPU)
 TFIX = os.path.join(_HERE, "tabfix")             # read errors a table can name, fixed on the device (csrc/host/tabfix.cpp; uses the GPU)
+TPHS = os.path.join(_HERE, "tabphase")         # heterozygous pairs phased from reads into two marker tables (csrc/host/tabphase.cpp; uses the GPU)
 TOOLS = {"prof2class": "prof2class.cpp", "class2acc": "class2acc.cpp"}   # host-only evaluation tools
 # -ffp-contract=off: the decision path compares doubles against thresholds and truncates them to
 # ints (class_rel.c:449,483); fused multiply-adds would change those values.
@@ -67,7 +68,7 @@ def _run(cmd, verbose):
 
 def build(force=False, verbose=False):
     # the HIP objects: library, command line, synthetic-set generator
-    outs, side, key = [OUT, CLI, CNS, GS, KPROF, G2C, C2K, T2P, TOP, TBIN, TTRK, TCMP, THET, TUTG, TGRF, TPTH, TCLN, TFIX, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
+    outs, side, key = [OUT, CLI, CNS, GS, KPROF, G2C, C2K, T2P, TOP, TBIN, TTRK, TCMP, THET, TUTG, TGRF, TPTH, TCLN, TFIX, TPHS, SYNTH], os.path.join(_HERE, ".build.srchash"), _src_key(FLAGS)
     if not _fresh(outs, side, key, force):
         if os.path.exists(side):
             os.remove(side)
@@ -80,7 +81,7 @@ def build(force=False, verbose=False):
                                   ("tabcmp.cpp", TCMP, False), ("tabhet.cpp", THET, False),
                                   ("tabunitig.cpp", TUTG, False), ("tabgraph.cpp", TGRF, False),
                                   ("tabpath.cpp", TPTH, False), ("tabclean.cpp", TCLN, False),
-                                  ("tabfix.cpp", TFIX, False)):
+                                  ("tabfix.cpp", TFIX, False), ("tabphase.cpp", TPHS, False)):
             _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", os.path.join(CSRC, "host", src), "-o", out,
                   "-L" + _HERE, "-lclasspro_amd", "-lz"] + ["-lpthread"] * pthread + ["-Wl,-rpath,$ORIGIN"], verbose)
         _run([hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",

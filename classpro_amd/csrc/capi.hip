@@ -1211,6 +1211,9 @@ extern "C" int cp_debug_phase_prof(unsigned long long *out36)
 // heterozygous k-mer pairs of one sorted snapshot (tabhet): kmer_hetpairs.hip
 #include "kmer_hetpairs.hip"
 
+// heterozygous sites of such pairs phased from reads: marks, links, forest and split (tabphase): kmer_phase.hip
+#include "kmer_phase.hip"
+
 // unitigs of the de Bruijn graph of one sorted snapshot (tabunitig): kmer_unitigs.hip
 #include "kmer_unitigs.hip"
 

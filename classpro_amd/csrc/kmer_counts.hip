@@ -37,6 +37,7 @@ struct kc_ctl                                                                 //
     unsigned int err, pad;
     unsigned long long n_mark;            // filtered table: valid k-mer positions of the mark passes
     unsigned long long n_single;          // filtered table: positions of the count passes whose key is not in the table
+    unsigned long long n_badkey;          // cp_kmer_counts_add_keys: keys of the last call that are no keys of K bases
   };
 
 // adds the wave's sum of v to *dst (one atomic per wave; every lane of the wave must call)
@@ -72,6 +73,39 @@ __global__ void __launch_bounds__(KT_BLOCK) kc_add_kernel(kc_slot *tab, unsigned
   kc_wave_add(&ctl->n_occ,nocc);
   kc_wave_add(&ctl->n_add,nadd);
   if (!REPLAY) kc_wave_add(&ctl->n_skip,nskip);
+}
+
+// The add pass over n EXPLICIT keys (cp_kmer_counts_add_keys), +1 each: the "positions" of the failure bitmap are the key
+// indices, so failed inserts, growth and replay are those of kc_add_kernel.  A key that does not fit 2K bits or whose lo
+// has bit 63 set is left out and counted; hi null: every hi is 0.
+template <bool REPLAY>
+__global__ void __launch_bounds__(KT_BLOCK) kc_add_keys_kernel(kc_slot *tab, unsigned long long mask,
+                                                               const unsigned long long *khi, const unsigned long long *klo,
+                                                               int64_t n, int K, const unsigned int *fail_in,
+                                                               unsigned int *fail_out, kc_ctl *ctl)
+{ unsigned long long nfail = 0, nocc = 0, nadd = 0, nbad = 0;
+  for (int64_t j = (int64_t)blockIdx.x*blockDim.x+threadIdx.x; j < n; j += (int64_t)gridDim.x*blockDim.x)
+    { if (REPLAY && !((fail_in[j >> 5] >> (j & 31)) & 1u)) continue;
+      const unsigned long long hi = khi ? khi[j] : 0, lo = klo[j];
+      if (lo > KT_M63 || ((((kt_u128)hi) << 63) >> (2*K)) != 0 || (2*K < 63 && (lo >> (2*K)) != 0))
+        { nbad++;
+          continue;
+        }
+      bool claimed = false;
+      kc_slot *e = kt_find_or_claim(tab,mask,hi,lo,&claimed);
+      nocc += claimed;
+      if (!e)
+        { atomicOr(&fail_out[j >> 5],1u << (j & 31));
+          nfail++;
+          continue;
+        }
+      atomicAdd(&e->cnt,1ull);
+      nadd++;
+    }
+  kc_wave_add(&ctl->n_fail,nfail);
+  kc_wave_add(&ctl->n_occ,nocc);
+  kc_wave_add(&ctl->n_add,nadd);
+  if (!REPLAY) kc_wave_add(&ctl->n_badkey,nbad);
 }
 
 // The filter of a filtered table: `wmask`+1 64-bit words.  The word and the four bit positions of a key come from a hash
@@ -461,6 +495,30 @@ extern "C" int cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const in
         kc_add_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,d_seq,d_seq_off,nreads,total_bases,t->K,fail_in,
                                                      fail_out,t->ctl);
     });
+}
+
+extern "C" int cp_kmer_counts_add_keys(cp_kmer_counts *t, const uint64_t *d_hi, const uint64_t *d_lo, int64_t n, void *stream)
+{ const char *who = "cp_kmer_counts_add_keys";
+  if (!t || n < 0) return set_err(CP_EINVAL,std::string(who)+": bad argument");
+  if (t->filter) return set_err(CP_EINVAL,std::string(who)+": a filtered table takes its keys from marked batches only");
+  if (n == 0) return CP_OK;
+  if (!d_lo) return set_err(CP_EINVAL,std::string(who)+": null device pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = kt_grid((unsigned long long)n);
+  const unsigned long long *khi = (const unsigned long long *)d_hi, *klo = (const unsigned long long *)d_lo;
+  HIPCHK(hipMemsetAsync(&t->ctl->n_badkey,0,sizeof(unsigned long long),st));
+  const int rc = kt_add(t,n,st,&t->unsized,[&](bool replay, const unsigned int *fail_in, unsigned int *fail_out)
+    { if (replay) kc_add_keys_kernel<true><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,khi,klo,n,t->K,fail_in,fail_out,t->ctl);
+      else kc_add_keys_kernel<false><<<grid,KT_BLOCK,0,st>>>(t->tab,t->slots-1,khi,klo,n,t->K,fail_in,fail_out,t->ctl);
+    });
+  if (rc != CP_OK) return rc;
+  if (t->h_ctl->n_badkey)                                  // kt_add has read the control block back
+    { char m[200];
+      snprintf(m,sizeof(m),"%s: %llu of the %lld keys are no keys of %d bases (they were left out, the others added)",who,
+               t->h_ctl->n_badkey,(long long)n,t->K);
+      return set_err(CP_EINVAL,m);
+    }
+  return CP_OK;
 }
 
 extern "C" int cp_kmer_counts_mark(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,

@@ -899,6 +899,97 @@ int     cp_kmer_sorted_het_pairs(const cp_kmer_sorted *s, const int64_t *range /
                                  void *stream, cp_kmer_sorted **out /* or NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Phasing heterozygous sites from reads (tabphase): the two members of a unique heterozygous pair are the two alleles of a
+ * SITE; reads that carry two sites say whether the smaller k-mers of the two lie on one haplotype or on two; a maximum
+ * spanning forest over those votes gives every site a block and a side, and the k-mers split into two marker tables A and
+ * B that need no parents.  The definitions are this library's own.  Everything is in integers and nothing depends on grid,
+ * block size, batching, read order or scheduling.
+ *
+ *   Sites      P is a ready snapshot of canonical keys; its counts are not looked at.  Siblings and deg are those of
+ *              "Heterozygous pairs of sorted k-mers", taken inside P with no range.  mate[i] is the ordinal of entry i's only
+ *              sibling when deg(i) = 1 and that sibling's degree is 1, otherwise -1.  A mated entry is the LOW member when
+ *              i < mate[i]; site(i) = the number of low members below min(i, mate[i]), so site ids are dense, 0 .. S-1;
+ *              allele(i) is 0 for the low member and 1 for the high one; mark[i] = site << 1 | allele (int32) for a mated
+ *              entry, -1 otherwise.  On the result of cp_kmer_sorted_het_pairs(unique = 1, out) every entry is mated: a
+ *              second sibling inside P would be a second sibling in the table.  S < 2^30, otherwise CP_EINVAL: a mark is a
+ *              non-negative int32.
+ *   Markers    a k-mer position of a read is a marker (site, allele) when its key -- chosen as in cp_kmer_sorted_profiles,
+ *              by `canonical` -- is in P and that entry is mated.  Every other position is transparent: absent keys,
+ *              unmated entries and k-mers holding a byte other than upper-case A C G T, exactly as for the switches of
+ *              cp_bin_call.
+ *   Links      take the markers of one read in order.  Every adjacent pair (s,a), (s',a') with s != s' is a link with the
+ *              key min(s,s') << 32 | max(s,s') << 1 | (a ^ a'), a 63-bit number; a pair with s == s' is counted as `self`
+ *              and gives no link.  The links of a batch are emitted in batch order -- reads ascending, positions ascending
+ *              -- so the array itself is deterministic.  A marker is never compared across a read boundary.
+ *   Edges      after all reads every site pair s < t has cis, the occurrences of the key (s,t,0), and trans, those of
+ *              (s,t,1).  With w = max, l = min and margin = w - l an edge is WEAK when w < min_support, otherwise TIED when
+ *              margin == 0, otherwise KEPT with sign = (trans > cis).
+ *   Forest     kept edge e comes before f when min(margin_e, 65535) > min(margin_f, 65535), or these are equal and
+ *              (s_e, t_e) is lexicographically smaller: a strict total order, held by one 64-bit word (the clamped margin in
+ *              the top 16 bits, then 2^48-1 minus an ordinal that ascends with (s,t)).  F is the maximum spanning forest
+ *              under that order -- Kruskal taking the edges from first to last and adding an edge when it joins two trees.
+ *              F is unique.
+ *   Blocks     block[s] is the smallest site of s's tree; side[s] is the XOR of the signs along F's path from block[s] to s,
+ *              0 for the block's own site.  A site without a kept edge is SINGLE: block[s] = s, side[s] = 0.  A kept edge
+ *              with sign != side[s] ^ side[t] is a CONFLICT; it is never in F.
+ *   Split      entry i of P goes to table A when it is mated, its site is not SINGLE and side[site] ^ allele == 0, to B
+ *              when that value is 1.  Both are ordinary snapshots that keep the entries' own counts, bucket starts rebuilt.
+ *   Between    the phase of one block relative to another is arbitrary -- no method that sees only reads can know it.  A
+ *   blocks     and B mean something INSIDE a block, which is what the blocks and switches of "Runs of k-mer states" need.
+ *
+ * cp_kmer_counts_add_keys adds n explicit keys hi << 63 | lo to a count table, +1 each (d_hi NULL: every hi is 0); failed
+ * inserts, growth and replay work as for bases.  CP_EINVAL for a filtered table.  A key that does not fit 2K bits or whose
+ * lo exceeds 2^63-1 is found on the device: it is left out and counted, the other keys of the call ARE added, and the call
+ * returns CP_EINVAL after the pass -- the table is not repaired.  Synchronises.  The links are accumulated in a table of
+ * K = 32, whose cp_kmer_counts_sort(t, 1) hands the edges over ascending, cis and trans of a pair adjacent.
+ *
+ * cp_kmer_sorted_het_sites fills d_mark (int32 [size]) and, when given, d_mate (int64 [size]); *nsites = S; tally (host
+ * [2], or NULL) = mated and unmated entries.  CP_EINVAL for a NULL p or nsites, an unready snapshot, a NULL d_mark where
+ * there are entries.  Scratch: 8 bytes per entry (16 without d_mate) and 8 per tile.  Synchronises.
+ *
+ * cp_kmer_sorted_read_links emits the links of a batch.  Capacity, the counting call (d_links NULL, capacity 0) and
+ * CP_EOVERFLOW with the exact *total work as in cp_kmer_sorted_read_runs; a call that overflows writes no link and adds
+ * nothing to the tally.  d_tally (device int64 [3], or NULL) is ADDED TO: markers, links, self.  Errors before any launch:
+ * CP_EINVAL for a NULL p or total, an unready snapshot, negative sizes, null pointers where there is work.  Scratch, by
+ * plain allocation: 16 bytes per marker -- the first pass has room for one marker per 64 bases and is repeated once at the
+ * exact size when the batch holds more -- 16 bytes per block of 8192 positions and 8 per 256 markers.  Synchronises.
+ * Knob, read per call from the environment, for tests: CLASSPRO_PHASE_GUESS=<n> gives the first staging array room for n
+ * markers (at least 1) instead of one per 64 bases, so that the repeated pass can be forced.  It changes no result.
+ *
+ * cp_phase_forest takes the sorted link keys with their counts.  The two counts of a pair are read from adjacent entries; a
+ * pair with only one of its keys present has the other count 0.  A key with a bit above 62, with s >= t or with
+ * t >= nsites is ignored and counted, per key, in CP_PH_BAD; nothing read from the arrays leads outside an array.  tally
+ * (host [CP_PH_WIDTH], or NULL): EDGES the site pairs, KEPT, TIED, WEAK, FOREST the edges of F, CONFLICTS, BLOCKS the trees
+ * of two or more sites, SINGLE, LARGEST the sites of the largest block (0 without a block), ROUNDS the Boruvka rounds that
+ * joined trees, BAD.  Errors before any launch: CP_EINVAL for a NULL or unready snapshot or one whose K is not 32,
+ * min_support < 1, nsites outside [0, 2^31), 2^48 keys or more, a NULL d_block or d_side with nsites > 0.  Scratch: 9 bytes
+ * per key and 24 per site.  Synchronises.
+ *
+ * cp_kmer_sorted_phase_split builds table A (which = 0) or B (which = 1).  It takes nsites, the length of d_block and
+ * d_side: whether a site is SINGLE is read from d_block (no other site names it and it names itself), which needs a byte
+ * per site.  A mark that names a site >= nsites keeps its entry out.  CP_EINVAL for a NULL p or out, an unready snapshot,
+ * which outside {0, 1}, nsites outside [0, 2^31), null pointers where there is work.  The result is the caller's.
+ */
+enum { CP_PH_EDGES = 0, CP_PH_KEPT = 1, CP_PH_TIED = 2, CP_PH_WEAK = 3, CP_PH_FOREST = 4, CP_PH_CONFLICTS = 5, CP_PH_BLOCKS = 6,
+       CP_PH_SINGLE = 7, CP_PH_LARGEST = 8, CP_PH_ROUNDS = 9, CP_PH_BAD = 10, CP_PH_WIDTH = 11 };
+int     cp_kmer_counts_add_keys(cp_kmer_counts *t, const uint64_t *d_hi /* or NULL: all zero */, const uint64_t *d_lo,
+                                int64_t n, void *stream);
+int     cp_kmer_sorted_het_sites(const cp_kmer_sorted *p, int64_t *d_mate /* int64 [size], or NULL */,
+                                 int32_t *d_mark /* int32 [size] */, int64_t *nsites /* host */,
+                                 int64_t *tally /* host [2]: mated, unmated; or NULL */, void *stream);
+int     cp_kmer_sorted_read_links(const cp_kmer_sorted *p, const int32_t *d_mark, int canonical, const char *d_seq,
+                                  const int64_t *d_seq_off, int nreads, int64_t total_bases,
+                                  uint64_t *d_links /* uint64 [capacity], or NULL */, int64_t capacity,
+                                  int64_t *total /* host */, int64_t *d_tally /* device int64 [3], added to; or NULL */,
+                                  void *stream);
+int     cp_phase_forest(const cp_kmer_sorted *edges, int64_t nsites, int64_t min_support,
+                        int64_t *d_block /* int64 [nsites] */, uint8_t *d_side /* uint8 [nsites] */,
+                        int64_t *tally /* host [CP_PH_WIDTH], or NULL */, void *stream);
+int     cp_kmer_sorted_phase_split(const cp_kmer_sorted *p, const int32_t *d_mark, const int64_t *d_block,
+                                   const uint8_t *d_side, int64_t nsites, int which /* 0: A, 1: B */, void *stream,
+                                   cp_kmer_sorted **out);
+
+/* ------------------------------------------------------------------------------------------
  * Unitigs of sorted k-mers (tabunitig): the de Bruijn graph that ONE snapshot of canonical k-mers implies -- which k-mers
  * follow which -- and its compaction: the maximal non-branching chains spelled as sequences, what BCALM and GGCAT produce
  * and what every de Bruijn assembler builds on.  The definitions are this library's own.  Everything is in integers and
