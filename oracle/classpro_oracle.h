@@ -15,10 +15,13 @@
  *     own text: the GSL-free line ranges of wall.c are compiled into oracle/_ref (oracle/Makefile `ref`,
  *     oracle/ref_driver.c), golden vectors tests/golden/wall.npz and labels.npz, live legs in
  *     tests/test_oracle_wall.py.
- *   - calc_init_thres (wall.c:167-243) and the -M fit (wall.c:11-115) are **parity unpinned**: they reach
- *     load_himodel -> GSL (wall.c:9-115), GSL is absent from this image and its tarball is a missing blob, and no
- *     stand-in header was written.  The threshold table is pinned by exact integer arithmetic instead
+ *   - calc_init_thres (wall.c:167-243) with the default error model is PINNED against the reference's own text:
+ *     calc_init_thres(NULL) never reaches load_himodel / polynomialfit, so wall.c without its GSL include and
+ *     polynomialfit builds the program oracle/_ref/ref_thres (oracle/ref_thres.c, oracle/Makefile `ref`); golden
+ *     tests/golden/thres.npz, tests/test_oracle_thres.py.  The table is also checked by exact integer arithmetic
  *     (tests/test_first_principles.py).
+ *   - only the -M quadratic fit (load_himodel -> polynomialfit, wall.c:11-115) needs GSL and is **parity unpinned**:
+ *     GSL is absent from this image, its tarball is a missing blob, and no stand-in header was written.
  */
 #ifndef CLASSPRO_ORACLE_H
 #define CLASSPRO_ORACLE_H

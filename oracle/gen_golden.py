@@ -17,7 +17,14 @@ Vectors (inputs + the reference's outputs; data only, no reference source):
                 reads on which the reference's own exit(1) fires ("# E-intvls >= plen") carry status 1 and no records
   labels.npz    whole reads through reference text ONLY (context.c -> wall.c slice -> class_rel.c -> class_unrel.c ->
                 paint, ClassPro.c:229-271): label strings and the final interval classes
-Both also hold the threshold tables handed to find_wall (calc_init_thres itself needs GSL: DESIGN 3.2).
+  thres.npz     calc_init_thres(NULL) itself (wall.c:167-243, default error model; oracle/_ref/ref_thres): the whole
+                count-threshold table at (H,D) = (93,187), CMAX = 255, pe / HC_ERATE bit patterns, CMAX for D = 1..188
+  cov_edges.npz what wall.npz and labels.npz hold together, for four parameter sets at the ends of that table (CMAX 255,
+                184, 16, 9): generator, adversarial, tail-run and tiny reads plus threshold-edge reads (tests/cov_edges.py
+                holds the conditions on the file)
+wall.npz, labels.npz and cov_edges.npz also hold the threshold tables handed to find_wall: the reference's own for the
+default error model (only the -M quadratic fit needs GSL and has no reference build: DESIGN 3.2; that set gets the
+oracle's fit).
 """
 import os
 import sys
@@ -27,7 +34,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:] = [q for q in sys.path if os.path.abspath(q or ".") != os.path.join(ROOT, "oracle")]
 sys.path.insert(0, ROOT)
-from oracle.oracle import Oracle, Ref, INTVL_DTYPE, ref_available, ref_wall_available  # noqa: E402
+from oracle.oracle import Oracle, Ref, RefExit, INTVL_DTYPE, ref_available, ref_wall_available  # noqa: E402
 from classpro_amd import synth, fastk  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
@@ -302,18 +309,23 @@ def wall_label_cases(which):
 
 
 def _tables(psets):
-    """Per parameter set the threshold tables find_wall gets (from the oracle; checked entry by entry with exact integer
-    arithmetic in tests/test_first_principles.py) -- stored so the tests can see that the product uses the same ones."""
+    """Per parameter set the threshold tables find_wall gets -- stored so the tests can see that the product uses the
+    same ones.  Default error model: the REFERENCE's own calc_init_thres(NULL) (Ref.thres, oracle/ref_thres.c).  The -M
+    set: the oracle's load + fit (the quadratic fit is the one part that needs GSL)."""
     td = tempfile.mkdtemp()
-    O = [Oracle(K, rl, h, d, model=(model_path(td) if m else None)) for K, rl, h, d, m in psets]
+    O = [Oracle(K, rl, h, d, model=model_path(td)) if m else None for K, rl, h, d, m in psets]
+    T = [dict(cthres=o.cthres(), pe=o.pe(), lmax=o.lmax(), cmax=o.scalars()[2], hc_erate=o.scalars()[3]) if o is not None
+         else Ref.thres(h, d) for (K, rl, h, d, m), o in zip(psets, O)]
     return O, dict(psets=np.array(psets, np.int32),
-                   cthres=np.stack([o.cthres() for o in O]), pe=np.stack([o.pe() for o in O]),
-                   lmax=np.stack([o.lmax() for o in O]),
-                   cmax=np.array([o.scalars()[2] for o in O], np.int32), hc_erate=np.array([o.scalars()[3] for o in O]))
+                   cthres=np.stack([t["cthres"] for t in T]), pe=np.stack([t["pe"] for t in T]),
+                   lmax=np.stack([t["lmax"] for t in T]),
+                   cmax=np.array([t["cmax"] for t in T], np.int32), hc_erate=np.array([t["hc_erate"] for t in T]))
 
 
 def _refs(psets, O):
-    return [Ref(rl, h, d).wall_setup_from(o) for (K, rl, h, d, m), o in zip(psets, O)]
+    """Ref instances whose find_wall is handed the reference's own table (the oracle's for the -M set)."""
+    return [Ref(rl, h, d).wall_setup_from(o) if m else Ref(rl, h, d).wall_setup_reference()
+            for (K, rl, h, d, m), o in zip(psets, O)]
 
 
 def wall():
@@ -372,12 +384,197 @@ def labels():
     print("labels.npz: %d reads, %d exit(1), %d bases labelled" % (len(cases), sum(status), sum(map(len, labs))))
 
 
+THRES_HD = (93, 187)                         # CMAX = 255, the widest table the reference builds (D = 188: exit(1))
+
+
+def thres():
+    """thres.npz: the reference's calc_init_thres(NULL) itself.  An entry cthres[t][l][cout][s][e] depends on (pe[t][l],
+    cout) alone, so the table at CMAX = 255 holds the table of every smaller CMAX as its prefix cout < CMAX; cmax_of_d is
+    read from the executable for every D in 1..188 (-1: the reference's exit(1))."""
+    t = Ref.thres(*THRES_HD)
+    assert t["cmax"] == 255
+    cmax_of_d = np.full(189, -1, np.int32)                # index D; [0] unused
+    for d in range(1, 189):
+        try:
+            td = Ref.thres(max(1, d // 2), d)
+        except RefExit as e:
+            assert "Too high REPEAT coverage" in e.message, e.message
+            continue
+        cmax_of_d[d] = td["cmax"]
+        c = td["cmax"]                                    # the prefix property, on the reference itself
+        assert np.array_equal(td["cthres"][:, :, :c], t["cthres"][:, :, :c]) and not td["cthres"][:, :, c:].any()
+        assert np.array_equal(td["pe"].view(np.uint64), t["pe"].view(np.uint64)) and td["hc_erate"] == t["hc_erate"]
+    assert cmax_of_d[188] == -1 and cmax_of_d[187] == 255 and (cmax_of_d[1:188] > 0).all()
+    np.savez_compressed(os.path.join(OUT, "thres.npz"), hd=np.array(THRES_HD, np.int32), cthres=t["cthres"],
+                        pe_bits=t["pe"].view(np.uint64), hc_erate_bits=np.array([t["hc_erate"]]).view(np.uint64),
+                        lmax=t["lmax"], cmax=np.array(t["cmax"], np.int32), cmax_of_d=cmax_of_d)
+    print("thres.npz: %d table bytes at (%d,%d), %d non-zero; D -> CMAX for D = 1..188 (%d exit(1))"
+          % (t["cthres"].size, THRES_HD[0], THRES_HD[1], int((t["cthres"] != 0).sum()), int((cmax_of_d[1:] < 0).sum())))
+
+
+# ---- cov_edges.npz: the coverage extremes -------------------------------------------------------------------------
+
+def _edge_param_sets():
+    """(K, -r, H, D): CMAX = 255 (the last table column), 184, 16 and 9 (almost every count >= CMAX)."""
+    return [(40, 20000, 93, 187), (40, 20000, 64, 128), (40, 20000, 2, 5), (21, 20000, 1, 2)]
+
+
+# (t, l), l <= lmax[t]; a DS or TS context wins over HP (wall.c:626-634) only with l >= 2
+EDGE_TL = [(0, 1), (0, 2), (0, 7), (0, 13), (0, 20), (1, 2), (1, 4), (1, 7), (1, 10), (2, 2), (2, 3), (2, 6)]
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from cov_edges import KIND_SYNTH, KIND_ADV, KIND_TAIL, KIND_EDGE, KIND_TINY, MIN_RETURN, MIN_DIFFER, class_floor, edge_shares  # noqa: E402
+
+
+def _generator_reads(si, K, h, d, cmax):
+    """(a): reads of the project's own generators at coverage d, and a few tiny reads with jumping counts around the set's
+    own levels (the kind on which the reference's exit(1), "# E-intvls >= plen", fires)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from adversarial import adversarial_reads, tail_run_reads
+    ds = synth.make_dataset(genome_len=20000 if d >= 100 else 120000, cov=d, read_len=5000, K=K, seed=7, het=0.004,
+                            max_len=6000)
+    out = [(KIND_SYNTH, s_, p_) for s_, p_ in list(zip(ds["seqs"], ds["profiles"]))[:12]]
+    S, P = adversarial_reads(71 + si, n=60, K=K)
+    out += [(KIND_ADV, s_, p_) for s_, p_ in [(s_, p_) for s_, p_ in zip(S, P) if len(s_) < 2000][:14]]
+    S, P = tail_run_reads(81 + si, n=10, K=K)
+    out += [(KIND_TAIL, s_, p_) for s_, p_ in zip(S, P)]
+    rng = np.random.default_rng(950 + si)
+    AL = np.frombuffer(b"ACGT", np.uint8)
+    for it in range(30):
+        plen = int(rng.integers(1, 12)); rlen = plen + K - 1
+        seq = [bytes(AL[rng.integers(0, 4, rlen)]), b"A" * rlen, (b"AC" * rlen)[:rlen]][it % 3]
+        out.append((KIND_TINY, seq, rng.choice([1, 2, 5, h, d, 2 * d, cmax - 1, cmax, 300], plen).astype(np.uint16)))
+    return out
+
+
+def _edge_site(R, seq, K, t, l, lmax, pe, wtype):
+    """Positions i of seq's profile at which find_wall (wall.c:623-634) picks the context (t, l) for a wall of type wtype
+    (0 = DROP: ctx = lctx[i+K-2], 1 = GAIN: ctx = rctx[i])."""
+    lc, rc = R.seq_context(seq)
+    plen = len(seq) - K + 1
+    ctx = (lc[K - 2:K - 2 + plen] if wtype == 0 else rc[:plen]).astype(np.int64)
+    ll = np.minimum(ctx, np.asarray(lmax)[None, :])
+    p = np.asarray(pe)[np.arange(3)[None, :], ll]
+    bt = np.argmax(p, axis=1)                                # first maximum, as the reference's strict `maxpe < pe`
+    ok = (bt == t) & (ll[np.arange(plen), bt] == l)
+    ok[0] = False
+    return np.nonzero(ok)[0]
+
+
+def _edge_reads(R, K, T, rng):
+    """(b): per (t, l) one random read of about 700 k-mers with one planted run of l units of type t, the profile flat at
+    cout on one side of the run's wall position and at cin on the other; cin at the reference's cthres entry (INIT and
+    FINAL) and that entry +- 1.  SELF: a DROP a few k-mers before the read's end, so that the error interval it opens is
+    closed by the end of the read (wall.c:356-359) -- elsewhere a lone drop has no partner and SELF never reaches past the
+    table; OTHERS: a GAIN in the middle of the read.  cout from {3, 5, CMAX-2 .. CMAX+1} (cout >= CMAX has no entry: the
+    last column's is used for cin)."""
+    AL = np.frombuffer(b"ACGT", np.uint8)
+    cmax = T["cmax"]
+    out, meta = [], []
+    for t, l in EDGE_TL:
+        ulen = t + 1
+        for e in (0, 1):
+            for attempt in range(200):
+                s = rng.integers(0, 4, 700 + K - 1)
+                unit = rng.permutation(4)[:ulen]
+                p0 = 380 + K
+                run = np.resize(unit, ulen * (l + attempt % 3))      # the context value counts from the run's second unit
+                s[p0:p0 + len(run)] = run
+                s[p0 - 1] = (unit[-1] + 1) % 4                # neither neighbour continues the period
+                s[p0 + len(run)] = (unit[0] + 1) % 4
+                seq = bytes(AL[s])
+                cand = _edge_site(R, seq, K, t, l, T["lmax"], T["pe"], 0 if e == 0 else 1)
+                cand = cand[(cand > 150) & (cand < 640)]
+                if len(cand):
+                    break
+            else:
+                raise RuntimeError("no site for (t,l) = (%d,%d)" % (t, l))
+            i = int(cand[np.argmin(np.abs(cand - (p0 - (K - 1 if e == 0 else 0))))])
+            if e == 0:
+                seq = seq[:i + 4 + K - 1]                    # plen = i+4: a partner j >= i+K-1-ulen*l lies at or beyond plen
+                                                             # (but for K = 21 and runs of 17+ bases, where j may fall inside)
+            plen = len(seq) - K + 1
+            for cout in sorted(set([3, 5, cmax - 2, cmax - 1, cmax, cmax + 1])):
+                ct = T["cthres"][t, l, min(cout, cmax - 1), :, e]
+                cins = sorted(set(int(c) + dlt for c in ct for dlt in (-1, 0, 1)))
+                for cin in cins:
+                    if not 0 <= cin <= cout:
+                        continue
+                    p = np.full(plen, cout, np.uint16)
+                    if e == 0:
+                        p[i:] = cin
+                    else:
+                        p[:i] = cin
+                    out.append((KIND_EDGE, seq, p))
+                    meta.append((t, l, cout, e, cin, int(ct[0]), int(ct[1]), i))
+    return out, np.array(meta, np.int32)
+
+
+def cov_edges():
+    psets = _edge_param_sets()
+    T = [Ref.thres(h, d) for K, rl, h, d in psets]
+    arrs = dict(psets=np.array([p + (0,) for p in psets], np.int32), cthres=np.stack([t["cthres"] for t in T]), pe=np.stack([t["pe"] for t in T]),
+                lmax=np.stack([t["lmax"] for t in T]), cmax=np.array([t["cmax"] for t in T], np.int32),
+                hc_erate=np.array([t["hc_erate"] for t in T]))
+    sets, kinds, status, seqs, profs, ivs, rvs, labs, asg, erow, metas = [], [], [], [], [], [], [], [], [], [], []
+    for si, (K, rl, h, d) in enumerate(psets):
+        R = Ref(rl, h, d).wall_setup_reference()
+        O = Oracle(K, rl, h, d)
+        cases = _generator_reads(si, K, h, d, T[si]["cmax"])
+        ecases, meta = _edge_reads(R, K, T[si], np.random.default_rng(900 + si))
+        row0 = sum(len(m) for m in metas)
+        metas.append(meta)
+        n_orc = 0
+        for k, (kind, s, p) in enumerate(cases + ecases):
+            st = R.find_wall_exit_status(s, p, K)
+            assert st in (0, 1), st
+            if st == 0:
+                iv, rv = R.find_wall_rel(s, p, K)
+                lab, fin = R.classify_read(s, p, K, want_intvl=True)
+                assert len(fin) == len(iv) and np.array_equal(fin["b"], iv["b"])
+                try:                                         # not a condition, a figure: the oracle on the same reads
+                    n_orc += int(O.classify_read(s, p) != lab)
+                except OverflowError:
+                    n_orc += 1
+            else:
+                iv = rv = fin = np.zeros(0, INTVL_DTYPE)
+                lab = b""
+            sets.append(si); kinds.append(kind); status.append(st)
+            seqs.append(np.frombuffer(s, np.uint8)); profs.append(p); ivs.append(iv); rvs.append(rv)
+            labs.append(np.frombuffer(lab, np.uint8)); asg.append(fin["asgn"].copy())
+            erow.append(row0 + k - len(cases) if kind == KIND_EDGE else -1)
+        print("cov_edges set %d (K %d, H %d, D %d, CMAX %d): %d generator + %d edge reads, %d exit(1), max generated count %d, oracle != reference on %d reads"
+              % (si, K, h, d, T[si]["cmax"], len(cases), len(ecases), sum(status[-len(cases) - len(ecases):]),
+                 max(int(p.max()) for k_, _, p in cases if k_ == KIND_SYNTH), n_orc))
+
+    def cat(L, dt):
+        out = np.zeros(sum(len(x) for x in L), dt)
+        o = 0
+        for x in L:
+            out[o:o + len(x)] = x
+            o += len(x)
+        return out
+    off = lambda L: np.concatenate([[0], np.cumsum([len(x) for x in L])]).astype(np.int64)
+    g = dict(set=np.array(sets, np.int32), kind=np.array(kinds, np.int8), status=np.array(status, np.int8),
+             seq=cat(seqs, np.uint8), seq_off=off(seqs), prof=cat(profs, np.uint16), prof_off=off(profs),
+             intvl=cat(ivs, INTVL_DTYPE).view(np.uint8), intvl_off=off(ivs),
+             rintvl=cat(rvs, INTVL_DTYPE).view(np.uint8), rintvl_off=off(rvs),
+             labels=cat(labs, np.uint8), labels_off=off(labs), asgn=cat(asg, np.int8), asgn_off=off(asg),
+             edge_row=np.array(erow, np.int32), edge_meta=np.concatenate(metas), **arrs)
+    for si, (K, rl, h, d) in enumerate(psets):
+        ret, cls, differ, ntri = edge_shares(g, si, INTVL_DTYPE)
+        print("cov_edges set %d: %.1f %% of reads return; generator reads E %.1f H %.1f D %.1f R %.1f %% of labelled bases; "
+              "%.0f %% of %d (t,l,cout) differ across a threshold"
+              % (si, 100 * ret, 100 * cls["E"], 100 * cls["H"], 100 * cls["D"], 100 * cls["R"], 100 * differ, ntri))
+        assert ret >= MIN_RETURN and min(cls.values()) >= class_floor(h, d) and differ >= MIN_DIFFER
+    np.savez_compressed(os.path.join(OUT, "cov_edges.npz"), **g)
+
+
 if __name__ == "__main__":
     if not ref_available() and not os.path.exists("/root/reference/src/ClassPro.h"):
         sys.exit("oracle/_ref is not built and /root/reference is absent")
     os.makedirs(OUT, exist_ok=True)
     only = sys.argv[1:]
-    for f in (prims, context, classify, fastk_files, eval_tools, dazz_db, seeds, wall, labels):
+    for f in (prims, context, classify, fastk_files, eval_tools, dazz_db, seeds, wall, labels, thres, cov_edges):
         if not only or f.__name__ in only:
             f()
     for f in sorted(os.listdir(OUT)):

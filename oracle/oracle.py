@@ -5,6 +5,7 @@ The product (classpro_amd/) never does.
 
   Oracle  -> oracle/libclasspro_oracle.so   (restatement, oracle/classpro_oracle.c)
   Ref     -> oracle/_ref/libclasspro_ref.so (the reference's own GSL-free sources, oracle/ref_driver.c)
+             oracle/_ref/ref_thres          (the reference's calc_init_thres(NULL), oracle/ref_thres.c; a child process)
 """
 import ctypes as C
 import os
@@ -51,7 +52,8 @@ def build(force=False):
     ref = os.path.join(_HERE, "_ref", "libclasspro_ref.so")
     drv = os.path.join(_HERE, "ref_driver.c")
     if os.path.exists("/root/reference/src/ClassPro.h"):
-        st = _stale(ref, [drv, os.path.join(_HERE, "Makefile")], force)
+        deps = [drv, os.path.join(_HERE, "ref_thres.c"), os.path.join(_HERE, "Makefile")]
+        st = _stale(ref, deps, force or not os.path.exists(os.path.join(_HERE, "_ref", "ref_thres")))
         if st:
             subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
             open(st[0], "w").write(st[1] + "\n")
@@ -261,6 +263,22 @@ def ref_wall_available():
     return hasattr(L, "ref_have_wall") and L.ref_have_wall() == 1
 
 
+def ref_thres_available():
+    """True when oracle/_ref holds ref_thres, the reference's calc_init_thres(NULL) as a program."""
+    return os.path.exists(os.path.join(_HERE, "_ref", "ref_thres"))
+
+
+class RefExit(RuntimeError):
+    """The reference's own exit(1); .message is what it wrote to stderr."""
+    def __init__(self, message):
+        RuntimeError.__init__(self, message)
+        self.message = message
+
+
+THRES_HEAD = 2 + 3 + 3 * 21          # doubles in front of ref_thres's table: CMAX, HC_ERATE, lmax[3], pe[3][21]
+THRES_SHAPE = (3, 21, 256, 2, 2)
+
+
 class Ref:
     """The reference's own code (GSL-free files) via oracle/_ref/libclasspro_ref.so."""
 
@@ -311,6 +329,35 @@ class Ref:
         cov, _, cmax, hc = O.scalars()
         assert (cov[2], cov[3]) == self._setup[1:] and O.read_len == self._setup[0]
         return self.wall_setup(O.cthres(), O.pe(), O.lmax(), cmax, hc)
+
+    @staticmethod
+    def thres(h, d):
+        """The reference's calc_init_thres(NULL) (wall.c:167-243, default error model) for coverages (h, d), run as a
+        child process (oracle/_ref/ref_thres): dict(cmax, hc_erate, lmax int32[3], pe float64[3][21],
+        cthres uint8[3][21][256][2][2], zero where the reference leaves it unset).  RefExit on the reference's own
+        exit(1) ('Too high REPEAT coverage')."""
+        import tempfile
+        build()
+        with tempfile.TemporaryDirectory() as td:
+            out = os.path.join(td, "thres.bin")
+            r = subprocess.run([os.path.join(_HERE, "_ref", "ref_thres"), str(int(h)), str(int(d)), out],
+                               capture_output=True, text=True)
+            if r.returncode == 1:
+                raise RefExit(r.stderr.strip())
+            if r.returncode != 0:
+                raise RuntimeError("ref_thres %d %d: exit %d: %s" % (h, d, r.returncode, r.stderr.strip()))
+            raw = open(out, "rb").read()
+        n = int(np.prod(THRES_SHAPE))
+        assert len(raw) == 8 * THRES_HEAD + n, len(raw)
+        head = np.frombuffer(raw, np.float64, THRES_HEAD)
+        return dict(cmax=int(head[0]), hc_erate=float(head[1]), lmax=head[2:5].astype(np.int32),
+                    pe=head[5:].reshape(3, 21).copy(),
+                    cthres=np.frombuffer(raw, np.uint8, n, 8 * THRES_HEAD).reshape(THRES_SHAPE).copy())
+
+    def wall_setup_reference(self):
+        """Tables of the reference's own calc_init_thres(NULL) for this instance's (H, D): reference text end to end."""
+        t = Ref.thres(*self._setup[1:])
+        return self.wall_setup(t["cthres"], t["pe"], t["lmax"], t["cmax"], t["hc_erate"])
 
     def _wall_apply(self):
         ct, pe, lm, cmax, hc = self._wall

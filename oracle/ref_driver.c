@@ -11,16 +11,18 @@
  * the same objects the reference links into ClassPro (src/Makefile:23-24).
  *
  * wall.c: `#include <gsl/gsl_multifit.h>` (wall.c:9) cannot be satisfied -- GSL is not installed and
- * src/gsl-2.7.tar.gz is a missing blob; no stand-in header is provided.  GSL is used by wall.c:9-115 only
- * (`polynomialfit`, `load_himodel`) and reached only through `load_emodel` (120-165) <- `calc_init_thres` (167-243).
+ * src/gsl-2.7.tar.gz is a missing blob; no stand-in header is provided.  Only the -M quadratic fit needs GSL:
+ * `polynomialfit` (11-42), called by `load_himodel` (55-115) alone, which `load_emodel` (120-165) <- `calc_init_thres`
+ * (167-243) reaches only when a model file is named.  This library leaves lines 9-115 and the threshold builder out.
  * Everything else of the file compiles as it stands: oracle/Makefile `ref` pipes
  *     sed -n '1,8p;117,118p;245,1051p' wall.c      (headers; `CMAX`, `HC_ERATE`; alloc_wall_arg ... find_rel_intvl)
  * into a temporary file OUTSIDE the repo (deleted after the compile; nothing of it is committed) and this driver
  * #includes it as <wall_gslfree.inc> when REF_HAVE_WALL is defined: the reference's own text for find_wall,
  * find_gain/find_drop, correct_wall_cnt, find_rel_intvl and their helpers, no line edited, no stub.
  * `find_wall` takes the Error_Model as a PARAMETER; `ref_wall_setup` fills one from a table the caller hands in
- * (calc_init_thres itself, wall.c:167-243, calls load_emodel -> GSL and has no reference build: its table is pinned by exact integer arithmetic,
- * tests/test_first_principles.py).
+ * (calc_init_thres(NULL) itself, wall.c:167-243 with the default error model, is built as a program of its own,
+ * oracle/_ref/ref_thres from oracle/ref_thres.c: its table is what the tests hand in here, and what pins the oracle's and
+ * the product's, tests/test_oracle_thres.py).
  *
  * The globals below are the ones ClassPro.c:27-32 defines for the unity build.
  * Output: oracle/_ref/libclasspro_ref.so (git-ignored; travels to the GPU box with gpurun).

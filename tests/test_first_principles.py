@@ -1,6 +1,7 @@
-"""Checks of the restatement of calc_init_thres (wall.c:167-243: parity-unpinned in this image -- it calls load_emodel ->
-load_himodel -> GSL, wall.c:9-165, and GSL is absent; find_wall / find_rel_intvl, wall.c:245-1051, ARE pinned against the
-compiled reference: tests/test_oracle_wall.py) that do not rest on anyone's reading of the code: mathematics.
+"""Checks of the restatement of calc_init_thres (wall.c:167-243) that do not rest on anyone's reading of the code:
+mathematics.  (The table is also pinned, byte for byte, against the reference's own calc_init_thres(NULL):
+tests/test_oracle_thres.py, tests/golden/thres.npz.  Only the -M quadratic fit, wall.c:11-42, needs GSL and has no
+reference build.)
 
 calc_init_thres (wall.c:167-244) defines, for an error rate pe and an outer count cout,
     cthres[..][cout][s][SELF]   = the smallest cin with P(X > cin) < PE_THRES[s][e],  X ~ Binomial(cout, pe)
@@ -9,39 +10,48 @@ The tables of the oracle and of the product (cp_host_fill_params through the hos
 integer arithmetic on the binary values of pe and of the thresholds; a table entry may differ from the exact answer
 only where the exact tail lies within 1e-9 (relative) of the threshold, i.e. where floating-point summation order
 could legitimately decide either way: exactly the entries with pe = 0.1 and cout = 3 or 5 (0.1^3 and 0.1^5 are the
-thresholds 1e-3 and 1e-5)."""
+thresholds 1e-3 and 1e-5).  Those entries, which the mathematics waives, must be the reference's (thres.npz)."""
 import ctypes as C
 from fractions import Fraction
+from functools import lru_cache
 from math import comb
 
 import numpy as np
 import pytest
 
+from conftest import load_golden
+
 THRES = [[1e-3, 5e-2], [1e-5, 1e-5]]                      # const.c:62-63  PE_THRES[INIT|FINAL][SELF|OTHERS]
 LMAX = [20, 10, 6]                                        # wall.c:122-143
 
 
+@lru_cache(maxsize=None)
+def binomial_terms(cout, pe):
+    """P(X = x) * den for x = 0..cout and den itself, X ~ Binomial(cout, pe): integers, pe being a binary fraction"""
+    p = Fraction(pe)
+    den = p.denominator ** cout                           # common denominator of all terms
+    pn, qn = p.numerator, p.denominator - p.numerator
+    return [comb(cout, x) * pn ** x * qn ** (cout - x) for x in range(cout + 1)], den
+
+
 def exact_first_cin(cout, pe, thr):
     """smallest cin in [0,cout] with P(X > cin) < thr, exactly; also the relative distance of the nearest tail to thr"""
-    p = Fraction(pe)
-    q = 1 - p
-    den = p.denominator ** cout                           # common denominator of all terms: pe is a binary fraction
-    pn, qn = p.numerator, p.denominator - p.numerator
-    terms = [comb(cout, x) * pn ** x * qn ** (cout - x) for x in range(cout + 1)]
+    terms, den = binomial_terms(cout, pe)
     t = Fraction(thr)
     tail = sum(terms)                                     # P(X >= 0) * den
-    first, margin = None, None
+    rhs = t.numerator * den                               # the same for every cin: the nearest tail is the least |lhs - rhs|
+    first, near = None, None
     for cin in range(cout + 1):
         tail -= terms[cin]                                # P(X > cin) * den
-        lhs, rhs = tail * t.denominator, t.numerator * den
-        rel = abs(Fraction(lhs - rhs, rhs)) if rhs else None
-        margin = rel if margin is None or rel < margin else margin
+        lhs = tail * t.denominator
+        dist = abs(lhs - rhs)
+        near = dist if near is None or dist < near else near
         if first is None and lhs < rhs:
             first = cin
-    return first, margin
+    return first, (Fraction(near, rhs) if rhs else None)
 
 
-@pytest.mark.parametrize("hd", [(20, 40), (30, 60)])
+@pytest.mark.parametrize("hd", [(20, 40), (30, 60), (93, 187)])
 def test_cthres_tables_equal_exact_binomial_tails(harness, built, hd):
     from oracle.oracle import Oracle
     h, d = hd
@@ -71,6 +81,13 @@ def test_cthres_tables_equal_exact_binomial_tails(harness, built, hd):
     # rounding of exp(log-binomial) in libm.  The oracle and the product use the reference's formula with the same libm.
     assert all(l == 7 and t in (0, 1) and cout in (3, 5) for t, l, cout, s, e, got, want in near), near
     assert len(near) <= 6
+    # ... and there the reference's own calc_init_thres decides: every pe = 0.1, cout = 3 / 5 entry, waived or not
+    ref = load_golden("thres.npz")["cthres"]
+    for t, l, cout, s, e, got, want in near:
+        assert got == int(ref[t, l, cout, s, e]), (t, l, cout, s, e, got)
+    for t in (0, 1):
+        for cout in (3, 5):
+            assert np.array_equal(tab[t, 7, cout], ref[t, 7, cout]) and np.array_equal(ct[t, 7, cout], ref[t, 7, cout])
 
 
 def test_error_rate_and_globals_formulas(built):

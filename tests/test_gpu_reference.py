@@ -32,7 +32,8 @@ def reads_of_set(g, si):
 
 
 def classifier_for(g, si):
-    """A Classifier for parameter set si whose tables are the ones the reference's find_wall was handed."""
+    """A Classifier for parameter set si whose tables are the ones the reference's find_wall was handed: for the
+    default error model the reference's own calc_init_thres(NULL) (oracle/ref_thres.c), not the oracle's restatement."""
     from classpro_amd.api import Classifier
     K, rl, h, d, m = (int(x) for x in g["psets"][si])
     # the -M set: the reference's find_wall was handed the oracle's fit of the synthetic HIsim model; the product gets the
