@@ -1501,7 +1501,10 @@ def threshold_labels(batch, thresholds, K, packed=False, counts=None):
     if dev.type != "cuda":
         raise ValueError("classpro_amd runs on a HIP device only")
     n = seq_off.numel() - 1
-    total = int(seq_off[-1].item()) if n > 0 else 0
+    if isinstance(batch, Batch):                           # the host knows the size: no read-back, nothing waits for the stream
+        total = batch.total_bases
+    else:
+        total = int(seq_off[-1].item()) if n > 0 else 0
     t = (C.c_int32 * 3)(*[int(x) for x in thresholds])
     if counts is None:
         counts = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -1553,10 +1556,12 @@ class LabelAccuracy:
     def add(self, est, truth, seq_off=None):
         """Adds a batch: `est` / `truth` uint8 device tensors in the label layout and `seq_off` int64 [n+1]; or
         add(batch, truth) for a `Batch` labelled by Classifier.classify / run (its `labels` tensor is the estimate)."""
-        if isinstance(est, Batch):
-            est, seq_off = est.labels, est.seq_off
+        total = None
+        if isinstance(est, Batch):                         # the host knows the size: no read-back, nothing waits for the stream
+            est, seq_off, total = est.labels, est.seq_off, est.total_bases
         n = seq_off.numel() - 1
-        total = int(seq_off[-1].item()) if n > 0 else 0
+        if total is None:
+            total = int(seq_off[-1].item()) if n > 0 else 0
         if est.numel() < total or truth.numel() < total:
             raise ValueError("LabelAccuracy.add: a label tensor is shorter than seq_off[-1]")
         check(self.L.cp_acc_add(self.a, est.data_ptr(), truth.data_ptr(), seq_off.data_ptr(), n, total,

@@ -441,6 +441,7 @@ static int kc_create(const char *who, int K, int64_t initial_slots, int64_t filt
     { t->filter_words = kt_pow2_at_least((unsigned long long)filter_bits)/64;
       hipError_t e = hipMalloc(&t->filter,(size_t)t->filter_words*8);
       if (e == hipSuccess) e = hipMemset(t->filter,0,(size_t)t->filter_words*8);
+      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);          // the fill is on the null stream; the first mark need not be
       if (e != hipSuccess)
         { (void)hipGetLastError();
           char m[160];

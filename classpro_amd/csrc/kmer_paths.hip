@@ -179,6 +179,13 @@ __global__ void __launch_bounds__(KT_BLOCK) kp_write_kernel(const unsigned long 
   if (p0+np == total) kp_walk_end(x,pw,total,a);            // the batch ends in this lane
 }
 
+// c[0..n) = 0, n <= 64: one wave.  A counter that a kernel adds to is zeroed by this store on the same stream, never by a
+// fill of memory taken from the stream-ordered pool: kernel after kernel on one stream is the order
+// everything else here rests on.
+__global__ void __launch_bounds__(64) kp_zero_kernel(unsigned long long *c, int n)
+{ if ((int)threadIdx.x < n) c[threadIdx.x] = 0;
+}
+
 // *out += the values of v[0..n) that are not zero
 __global__ void __launch_bounds__(KT_BLOCK) kp_nonzero_kernel(const int64_t *v, int64_t n, unsigned long long *out)
 { unsigned long long c = 0;
@@ -244,7 +251,8 @@ extern "C" int cp_kmer_sorted_read_paths(const cp_kmer_sorted *s, const cp_uniti
   a.gcount = g ? g->count : 0; a.links = (g && g->loff && g->base) ? g->links : 0;
   a.segs = (kp_seg *)d_segs; a.capacity = capacity; a.seg_off = d_seg_off;
   a.cov = d_cov; a.support = d_support;
-  hipError_t e = hipMemsetAsync(ctl,0,sizeof(kp_sum),st);
+  kp_zero_kernel<<<1,64,0,st>>>(ctl,(int)(sizeof(kp_sum)/8));               // the counters: a store, not a fill (see there)
+  hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     { if (kl_lo_only(s)) kp_step_kernel<true><<<(unsigned)nblk,KT_BLOCK,0,st>>>(t,d_utg,d_at,u->count,d_seq,d_seq_off,nreads,total_bases,s->K,word,ctl);
       else kp_step_kernel<false><<<(unsigned)nblk,KT_BLOCK,0,st>>>(t,d_utg,d_at,u->count,d_seq,d_seq_off,nreads,total_bases,s->K,word,ctl);
@@ -295,7 +303,8 @@ extern "C" int cp_count_nonzero(const int64_t *d_v, int64_t n, int64_t *count, v
     { (void)hipGetLastError();
       return set_err(CP_ENOMEM,std::string(who)+": cannot allocate 8 bytes for the counter");
     }
-  hipError_t e = hipMemsetAsync(d_c,0,8,st);
+  kp_zero_kernel<<<1,64,0,st>>>(d_c,1);
+  hipError_t e = hipGetLastError();
   if (e == hipSuccess)
     { kp_nonzero_kernel<<<kt_grid((unsigned long long)n),KT_BLOCK,0,st>>>(d_v,n,d_c);
       e = hipGetLastError();

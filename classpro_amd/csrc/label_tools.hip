@@ -344,6 +344,7 @@ extern "C" int cp_acc_create(int K, double max_e_pct, double rep_pct, cp_acc **o
   hipError_t e = hipGetDevice(&a->device);
   if (e == hipSuccess) e = hipMalloc(&a->tot,LT_NTOT*sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemset(a->tot,0,LT_NTOT*sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);              // the fill is on the null stream; the first add need not be
   if (e != hipSuccess)
     { const int rc = set_err(CP_EHIP,std::string("cp_acc_create: ")+hipGetErrorString(e));
       cp_acc_destroy(a);

@@ -122,6 +122,19 @@ int64_t cp_encode_profile(const uint16_t *profile, int n, uint8_t *code, int64_t
 /* ------------------------------------------------------------------------------------------
  * Batched device path.
  * ------------------------------------------------------------------------------------------ */
+/* Streams.  A call that takes a `stream` does all of its device work -- kernels, fills, copies, its scratch from the
+ * stream-ordered pool -- in that stream's order and on no other stream: it may be given inputs that earlier work on the same
+ * stream has not written yet, and NULL is the null stream, nothing special.  "Asynchronous on `stream`" means the call
+ * returns without waiting; a call that reads something back waits for `stream` alone.  An object that is written in a
+ * stream's order (a cp_workspace, a cp_kmer_table, a cp_kmer_counts, a cp_acc) remembers the stream of the last call that
+ * queued work on it, and a call WITHOUT a stream argument that reads device state waits for that stream -- not for the
+ * device, not for the caller's current stream -- and runs what it launches there; it may be made from any host thread or
+ * under any current stream once the call that queued the work has returned.  Two calls that queue work on ONE object on
+ * two DIFFERENT streams are the caller's to order (an event, or a call of this kind in between); cp_kmer_counts_sort and
+ * cp_kmer_table_sort are the exception and wait for the table's stream themselves.  A cp_kmer_sorted, a cp_unitigs and a
+ * cp_unitig_graph are complete when the call that made them returns (each such call waits for its stream last), are only
+ * read afterwards, and so may be used on any stream at once.  tests/test_gpu_streams.py holds every call family to this on
+ * a side stream whose inputs arrive late. */
 typedef struct cp_workspace cp_workspace;          /* device scratch, grown on demand, reusable */
 int  cp_workspace_create(cp_workspace **out);
 void cp_workspace_destroy(cp_workspace *ws);
@@ -202,10 +215,12 @@ int cp_find_seeds_batch(const cp_params *p, cp_workspace *ws,
                         const uint16_t *d_prof, const int64_t *d_prof_off, const char *d_labels,
                         int nreads, int64_t total_bases, int64_t total_kmers,
                         char *d_seeds, void *stream);
+/* cp_get_rep_masks waits for the stream of the last call on `ws` (cp_workspace_check) before it copies;
+ * cp_rep_masks_capacity returns a number the host already holds when cp_find_seeds_batch returns. */
 int cp_get_rep_masks(cp_workspace *ws, int32_t *count, int64_t *cap_off, int32_t *pairs, int64_t capacity);
 int64_t cp_rep_masks_capacity(const cp_workspace *ws);
 
-/* Waits for the work queued on `ws` and returns CP_EOVERFLOW if, in ANY call on `ws` since the previous check, a read
+/* Waits for the stream of the last call that queued work on `ws` and returns CP_EOVERFLOW if, in ANY call on `ws` since the previous check, a read
  * needed more E-interval / interval / seed scratch than its capacity (the reference aborts likewise: "# E-intvls >=
  * plen", src/wall.c:783-788), CP_EINVAL for a bad code string in cp_decode_profiles.  The device-side flags are sticky
  * and are cleared by this call only.  Call after cp_classify_batch before trusting the labels. */
@@ -227,8 +242,8 @@ int cp_run_stages(const cp_params *p, cp_workspace *ws,
                   int nreads, int64_t total_bases, int64_t total_kmers,
                   char *d_labels, int last_stage, void *stream);
 
-/* Read-back of stage results of the last cp_run_stages/cp_classify_batch on `ws` (host buffers;
- * synchronises the stream).  counts: n_intvl[nreads], n_rel[nreads]; offsets into the flat arrays
+/* Read-back of stage results of the last cp_run_stages/cp_classify_batch on `ws` (host buffers; each waits for the
+ * stream of that call, through cp_workspace_check or directly, before it copies).  counts: n_intvl[nreads], n_rel[nreads]; offsets into the flat arrays
  * are the exclusive prefix sums of the per-read capacities returned in cap_off[nreads+1].
  * After a whole-path call (cp_classify_batch = CP_STAGE_LABELS) the interval records come back complete (the final classes
  * included), but the copies of the reliable intervals and the forward / backward assignments do not exist -- that path
@@ -303,7 +318,8 @@ void cp_kmer_table_destroy(cp_kmer_table *t);
  * failed-insert and occupancy counters (and, when the table grows, the growth itself). */
 int  cp_kmer_table_add(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, const char *d_labels,
                        int nreads, int64_t total_bases, void *stream);
-/* Synchronises; reports deferred device errors (CP_EINVAL, CP_EOVERFLOW) first. */
+/* Runs on and waits for the stream of the last add or consensus on `t`; reports deferred device errors (CP_EINVAL,
+ * CP_EOVERFLOW) first. */
 int  cp_kmer_table_stats(cp_kmer_table *t, cp_kmer_stats *out);
 /* Consensus labels in place: d_labels[i] becomes the consensus label of the k-mer ending at i for every counted
  * position; the K-1 leading positions and skipped k-mers keep what d_labels holds.  A k-mer that is not in the
@@ -311,7 +327,8 @@ int  cp_kmer_table_stats(cp_kmer_table *t, cp_kmer_stats *out);
 int  cp_kmer_table_consensus(cp_kmer_table *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
                              int64_t total_bases, char *d_labels, void *stream);
 /* Occupied entries in key order into host arrays (counts4 holds 4 per entry, order E, H, D, R).  Returns the number of
- * entries; when capacity is smaller than that (or an array is NULL) nothing is written. */
+ * entries; when capacity is smaller than that (or an array is NULL) nothing is written.  Runs on and waits for the stream
+ * of the last add or consensus on `t`. */
 int64_t cp_kmer_table_export(cp_kmer_table *t, uint64_t *hi, uint64_t *lo, uint32_t *counts4, int64_t capacity);
 
 /* ------------------------------------------------------------------------------------------
@@ -365,9 +382,11 @@ int  cp_kmer_counts_add(cp_kmer_counts *t, const char *d_seq, const int64_t *d_s
 int  cp_kmer_counts_profiles(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off,
                              const int64_t *d_prof_off, int nreads, int64_t total_bases, uint16_t *d_prof,
                              void *stream);
-/* The FASTK histogram of the table into a host array of 32767 (see Histogram).  Synchronises. */
+/* The FASTK histogram of the table into a host array of 32767 (see Histogram).  Runs on and waits for the stream of the
+ * last add, mark, profiles or rel_labels call on `t`. */
 int  cp_kmer_counts_hist(cp_kmer_counts *t, int64_t *hist, int64_t *ilowcnt, int64_t *ihighcnt);
-/* Synchronises; reports a deferred device error (CP_EINVAL, see Absent) first. */
+/* Waits for the stream of the last add, mark, profiles or rel_labels call on `t`; reports a deferred device error
+ * (CP_EINVAL, see Absent) first. */
 int  cp_kmer_counts_stats(cp_kmer_counts *t, cp_kmer_count_stats *out);
 
 /* ------------------------------------------------------------------------------------------
@@ -410,7 +429,7 @@ int  cp_kmer_counts_create_filtered(int K, int64_t initial_slots, int64_t filter
 /* The mark pass over a batch.  Asynchronous on `stream` except for the read-back and growth of cp_kmer_counts_add. */
 int  cp_kmer_counts_mark(cp_kmer_counts *t, const char *d_seq, const int64_t *d_seq_off, int nreads,
                          int64_t total_bases, void *stream);
-/* Synchronises; legal at any time and on any count table (filter_bits = 0 without a filter).  n_marked / n_counted: valid
+/* Runs on and waits for the stream of the last call that queued work on `t`; legal at any time and on any count table (filter_bits = 0 without a filter).  n_marked / n_counted: valid
  * k-mer occurrences of the mark / add passes so far; n_table_keys: keys that hold a slot; n_outside: keys kept outside
  * (known once the batches are added); n_false: table keys with count 1 (a slot sweep). */
 int  cp_kmer_counts_filter_stats(cp_kmer_counts *t, cp_kmer_filter_stats *out);
@@ -469,9 +488,9 @@ int  cp_kmer_counts_rel_labels(cp_kmer_counts *t, const char *d_seq, const int64
 typedef struct cp_kmer_sorted cp_kmer_sorted;
 int     cp_kmer_counts_sort(cp_kmer_counts *t, int64_t min_count, void *stream, cp_kmer_sorted **out);
 void    cp_kmer_sorted_destroy(cp_kmer_sorted *s);
-int64_t cp_kmer_sorted_size(const cp_kmer_sorted *s);
+int64_t cp_kmer_sorted_size(const cp_kmer_sorted *s);       /* host values: nothing is waited for */
 int64_t cp_kmer_sorted_bytes(const cp_kmer_sorted *s);
-/* Device pointers to size() words each, valid until destroy. */
+/* Device pointers to size() words each, valid until destroy; the words are written when the call that made `s` has returned. */
 int     cp_kmer_sorted_arrays(const cp_kmer_sorted *s, const uint64_t **d_hi, const uint64_t **d_lo,
                               const uint64_t **d_cnt);
 int     cp_kmer_sorted_ktab(cp_kmer_sorted *s, int64_t first, int64_t n, uint8_t *d_records, int64_t *d_index,
@@ -505,7 +524,8 @@ int     cp_ktab_tile(void);
  *   Histogram  cp_kmer_table_class_hist, for each class l in the order E, H, D, R: hist[l][c-1] = distinct keys with
  *              cls == l and total == c for c < 32767, hist[l][32766] = those with total >= 32767, ilowcnt[l] =
  *              hist[l][0], ihighcnt[l] = the sum of total over the keys with total >= 32767: the contract of
- *              cp_kmer_counts_hist, four times.  No min_total and no min_pct.  Synchronises.
+ *              cp_kmer_counts_hist, four times.  No min_total and no min_pct.  Runs on and waits for the stream of the
+ *              last add or consensus on the table.
  * On a canonical table the four class snapshots at min_total = 1, min_pct = 0 partition the label = -1 snapshot, which
  * is cp_kmer_counts_sort(min_count 1) of a count table fed the same reads (keys, counts, records, index), and the
  * four class histograms sum cell for cell to that table's cp_kmer_counts_hist.
@@ -593,8 +613,10 @@ int     cp_kmer_sorted_profiles(const cp_kmer_sorted *s, int canonical, const ch
  *              entries of the two operands together, never 24 bytes per operand entry.
  *   Histogram  cp_kmer_sorted_hist, the contract of cp_kmer_counts_hist over a snapshot's d_cnt: hist[c-1] = entries with
  *              count c for c < 32767, hist[32766] = those with count >= 32767, ilowcnt = hist[0], ihighcnt = the sum of
- *              the counts >= 32767.  CP_EINVAL on an unready snapshot; synchronises.  For cp_kmer_counts_sort(t, 1) it
- *              equals cp_kmer_counts_hist(t) cell for cell.
+ *              the counts >= 32767.  CP_EINVAL on an unready snapshot.  It takes no stream: a snapshot is complete when the
+ *              call that made it has returned, so there is nothing to wait for but the call's own sweep, which runs on
+ *              the null stream and is waited for.  For cp_kmer_counts_sort(t, 1) it equals cp_kmer_counts_hist(t) cell
+ *              for cell.
  */
 enum { CP_SET_AND = 0, CP_SET_OR = 1, CP_SET_SUB = 2, CP_SET_XOR = 3 };
 enum { CP_CNT_LEFT = 0, CP_CNT_SUM = 1, CP_CNT_MIN = 2, CP_CNT_MAX = 3 };
@@ -1057,6 +1079,8 @@ int     cp_kmer_sorted_unitigs(const cp_kmer_sorted *s, const int64_t *range /* 
                                uint8_t *d_adj /* device [size], overwritten, or NULL */,
                                int64_t *d_utg, int64_t *d_at /* device [size] each, overwritten, or NULL */,
                                void *stream, cp_unitigs **out /* or NULL */);
+/* The getters of a cp_unitigs and of a cp_unitig_graph return host values and device pointers to arrays that are written
+ * when the call that made the object has returned: nothing is waited for. */
 int64_t cp_unitigs_count(const cp_unitigs *u);
 int64_t cp_unitigs_bases(const cp_unitigs *u);
 int     cp_unitigs_arrays(const cp_unitigs *u, const char **d_seq, const int64_t **d_off /* [count+1] */,
@@ -1316,7 +1340,7 @@ void cp_acc_destroy(cp_acc *a);
 /* Asynchronous on `stream`. */
 int  cp_acc_add(cp_acc *a, const char *d_est, const char *d_truth, const int64_t *d_seq_off, int nreads,
                 int64_t total_bases, void *stream);
-/* Synchronises. */
+/* Waits for the stream of the last cp_acc_add on `a` (the null stream before the first), then reads the totals back. */
 int  cp_acc_read(cp_acc *a, cp_acc_stats *out);
 
 #ifdef __cplusplus

@@ -5,7 +5,8 @@ reads; closed chains run round three times; one long segment over four blocks at
 bases in one lane's chunk; a read whose every position is a head across a block edge; random read sets at K up to 63 with
 and without a count range; 200,000 keys and 2 Mbases against positions known by construction; coverage and support, their
 sums, batching and accumulation; the identities with `profiles` and `read_runs`; capacity and overflow; that everything
-passed in is only read; foreign where arrays; the argument errors.  Everything is integers and bytes: the tolerance is
+passed in is only read; foreign where arrays; the argument errors; a thousand `cp_count_nonzero` calls in a row, with a
+`read_paths` call after every tenth, that all give the one answer.  Everything is integers and bytes: the tolerance is
 zero."""
 import ctypes as C
 import random
@@ -507,3 +508,45 @@ def test_argument_errors(torch_dev):
     assert L.cp_count_nonzero(big.data_ptr(), big.numel(), C.byref(c), st) == 0 and c.value == len(range(0, 100000, 7))
     for x in (U, U9, S, S9):
         x.close()
+
+
+# ---- 8. the counters, over and over ----
+
+def test_a_thousand_counts_in_a_row_are_one_answer(torch_dev):
+    """A guard against a counter that is zeroed out of order: 1,000 consecutive cp_count_nonzero calls on
+    one vector whose non-zeros are known, a small read_paths call after every tenth so that the stream-ordered pool keeps
+    handing its memory back and forth between the two.  Every count, and every tally, coverage and support of read_paths,
+    is the oracle's.  A wrong-count check, bounded and not retried: it stops at the first mismatch and names the call.  It
+    cannot show that such a race is absent, only that it did not happen in these calls."""
+    torch = torch_dev
+    from classpro_amd._lib import lib
+    from classpro_amd.api import _stream_of
+    L = lib()
+    K = 12
+    rng = random.Random(8)
+    seqs = haplotypes(rng, K, n=600, snps=8)
+    ents = UO.table(seqs, K)
+    S = load(torch, ents, K)
+    U = S.unitigs(where=True, links=True)
+    reads = random_reads(rng, seqs, 60, 300)
+    woff, wsegs, wt, wcov, wsup = PO.Paths(ents, K).batch(reads)
+    assert wt["present"] > 1000 and wt["absent"] > 0 and wt["other"] > 0 and wt["joined"] > 10
+    batch = flat(torch, enc(reads))
+    v = torch.zeros(100001, dtype=torch.int64, device="cuda:0")
+    v[::7] = -3
+    v[5::1001] = 1 << 40
+    want = int((v != 0).sum().item())
+    assert want == len(set(range(0, 100001, 7)) | set(range(5, 100001, 1001)))
+    st = _stream_of(torch.device("cuda:0"))
+    c = C.c_int64()
+    for i in range(1000):
+        c.value = -1
+        assert L.cp_count_nonzero(v.data_ptr(), v.numel(), C.byref(c), st) == 0
+        assert c.value == want, "cp_count_nonzero call %d gave %d, not %d" % (i, c.value, want)
+        if i % 10 == 9:
+            off, segs, t = S.read_paths(U, batch, coverage=True, support=True)
+            assert {k: t[k] for k in PO.TALLY} == wt, "read_paths call %d" % (i // 10)
+            assert t["coverage"].tolist() == wcov and t["support"].tolist() == wsup, "read_paths call %d" % (i // 10)
+            assert off.tolist() == woff and len(segs["first"]) == len(wsegs), "read_paths call %d" % (i // 10)
+    U.close()
+    S.close()

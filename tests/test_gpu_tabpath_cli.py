@@ -2,7 +2,8 @@
 a closed chain, a homopolymer run, a sequence joined to its reverse complement -- and a source as FASTA and as gzipped
 FASTQ whose reads run along all of them, one of them three times round the closed chain; whole, with a count range, and
 with -b small enough for several batches.  The two stdout lines and the bytes of the .gaf and .gfa files are those of
-tests/path_oracle.py; the .gfa without its RC tags is tabgraph's file for the same table; without -o nothing is created."""
+tests/path_oracle.py; the .gfa without its RC tags is tabgraph's file for the same table; without -o nothing is created;
+eight fresh processes in a row print the same two lines."""
 import gzip
 import os
 import random
@@ -96,3 +97,16 @@ def test_nothing_created_without_o_and_verbose(case, tmp_path):
     assert re.fullmatch(r"K %d: %d entries, %d bases, \d+ batches, %d segments brought down; \d+\.\d{3} s on the device for the "
                         r"graph, \d+\.\d{3} s for the paths\n" % (K, len(ents), sum(len(x) for x in reads),
                                                                  P.batch(reads)[2]["segments"]), r.stderr), r.stderr
+
+
+def test_eight_fresh_processes_print_the_oracles_lines(case, tmp_path):
+    """A guard against a counter that is zeroed out of order: the first case of
+    test_lines_and_files_against_the_oracle eight times, each a process of its own -- the wrong count that was seen ("0 of 11
+    unitigs touched") came from the first calls of a fresh process.  A wrong-count check, bounded and not retried: it stops at
+    the first run whose lines differ.  It cannot show that such a race is absent, only that it did not happen in these runs."""
+    d, ents, reads, t = case["dir"], case["ents"], case["reads"], str(tmp_path)
+    want = PO.Paths(ents, K, None).lines(reads)
+    assert " 0 of " not in want
+    for run in range(8):
+        out, err = tool("tabpath", "-g", "-o" + os.path.join(t, "p"), os.path.join(d, "graph"), os.path.join(d, "reads.fasta"))
+        assert (out, err) == (want, ""), "run %d of 8" % run
